@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- EvoWorld per-clip denoise throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 A "step" = ONE CLIP through the hot path at BASELINE.json configs[1]: 576x1024 panorama, 25 frames, 25
 EulerDiscrete steps, CFG on (U-Net batch 2), random-init SVD-Xtend U-Net (in_channels 18), synthetic inputs
 already resident in HBM.  N>1: one process per GPU (torch.distributed.run), one independent clip per rank
 (weak scaling, no collective inside the loop; the final latents are all-gathered).  Rank 0 prints ONE JSON line.
-`value` = frames/s over the whole job = N * 25 * K / max-over-ranks(seconds).
+`value` = frames/s over the whole job = N * 25 * K / max-over-ranks(seconds); `ms_per_step` = milliseconds per timed clip.
+A plain run sets up, warms up, times the K clips and prints the line.  --dump-outputs DIR: the final latents of the last
+timed clip as DIR/<name>.npy (float32; inputs and weights are seeded, so two builds compare output for output).
+--full: also the diagnostics that take work of their own -- the per-kernel breakdown forward (roofline.kernels), the
+fp16-stream forwards (config.unet_forward_ms_fp16_stream) and the CPU baseline (cpu_baseline).
 """
 import argparse
 import json
@@ -23,6 +27,23 @@ sys.path.insert(0, ROOT)
 ALGO_TFLOP_PER_FORWARD = 154.31      # SURVEY.md §8d, config 2, dead cross-attention work removed
 PEAK_F16_DENSE_TFLOPS = 2500.0       # MI355X_MICROARCH.md: ~2.5 PF dense bf16/fp16 MFMA
 NOMINAL_CLOCK_GHZ = 2.4              # the clock the dense peak is quoted at (256 CUs x 4 SIMDs x 1024 flop/clk x 2.4 GHz = 2.5 PFLOP/s)
+DUMP_MAX_BYTES = 64 << 20            # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES):
+    """Write {name: tensor} as out_dir/<name>.npy in float32.  When the arrays together exceed max_bytes, each one is replaced by
+    a fixed seeded sample of its flattened elements (in index order, the same positions for the same shapes), its share of
+    max_bytes proportional to its size."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 4 * sum(t.numel() for t in arrays.values())
+    for name, t in arrays.items():
+        a = t.detach().float().cpu()
+        if total > max_bytes:
+            k = t.numel() * max_bytes // total
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:k].sort().values
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a.numpy())
 
 
 def source_fingerprint():
@@ -250,9 +271,12 @@ def main():
     ap.add_argument("--height", type=int, default=576)
     ap.add_argument("--width", type=int, default=1024)
     ap.add_argument("--denoise-steps", type=int, default=25)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fp16-stream", action="store_true", help="skip the extra fp16-stream forwards (profiling runs: keeps the launch count at steps x denoise-steps + 1)")
-    ap.add_argument("--cpu-baseline-full", action="store_true", help="time ONE complete full-size CPU forward (minutes) instead of the bounded sample")
+    ap.add_argument("--full", action="store_true", help="also run the diagnostics beyond the headline: per-kernel breakdown forward, "
+                                                            "fp16-stream forwards, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the final latents of the last timed clip as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-fp16-stream", action="store_true", help="with --full: skip the extra fp16-stream forwards (profiling runs: keeps the launch count at steps x denoise-steps + 1)")
+    ap.add_argument("--cpu-baseline-full", action="store_true", help="with --full: time ONE complete full-size CPU forward (minutes) instead of the bounded sample")
     ap.add_argument("--tiny", action="store_true", help="shrunken U-Net (plumbing check only; result flagged invalid)")
     ap.add_argument("--split", choices=["clip", "cfg"], default=os.environ.get("EW_BENCH_SPLIT", "clip"),
                     help="multi-GPU axis: clip = one independent clip per rank (weak scaling, default); cfg = ranks 2p, 2p+1 share clip p, "
@@ -371,9 +395,12 @@ def main():
                 raise SystemExit(f"CFG pair {q // 2} returned the latents of pair 0: pairs must work on different clips")
     from evoworld_amd import ops as _ops
     _ops.streamk_check()                      # (pipe.denoise already checked after every clip; this covers the hooked forward too)
+    if args.dump_outputs and rank == 0:       # res: every rank's latents of the last timed clip, in rank order
+        dump_outputs(args.dump_outputs, {"latents": res[0]} if len(res) == 1 else {f"latents_rank{r}": x for r, x in enumerate(res)})
 
-    kernels = kernel_breakdown(unet, pipe, latents, image_latents, ehs, plucker, T, h, w) if rank == 0 else None
-    fp16_ms = fp16_stream_forward_ms(unet, ehs, T, h, w) if rank == 0 and unet.split_residual and not args.no_fp16_stream else None
+    kernels = kernel_breakdown(unet, pipe, latents, image_latents, ehs, plucker, T, h, w) if rank == 0 and args.full else None
+    fp16_ms = (fp16_stream_forward_ms(unet, ehs, T, h, w) if rank == 0 and args.full and unet.split_residual and not args.no_fp16_stream
+               else None)
 
     if rank == 0:
         fw_ms = sum(s.elapsed_time(e) for s, e in fw_events) / max(1, len(fw_events))
@@ -409,7 +436,7 @@ def main():
                          "clock_detail": clk,
                          "kernels": kernels},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(frames=50 if args.cpu_baseline_full else 4)
         print(json.dumps(line), flush=True)
     D.barrier()

@@ -167,11 +167,33 @@ def test_bench_one_rank_over_rccl_broadcasts_weights():
     env = dict(os.environ, EW_FORCE_DIST="1", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--tiny", "--steps", "1", "--warmup", "0", "--denoise-steps", "2",
-                        "--height", "128", "--width", "256", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
+                        "--height", "128", "--width", "256", "--full", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     assert "weight broadcast to 1 rank(s)" in r.stderr
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["config"]["valid"] is False and line["value"] > 0
+    assert line["roofline"]["kernels"]                        # --full: the per-kernel breakdown forward ran
+
+
+def test_bench_plain_run_dumps_reproducible_outputs(tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps clips, leaves the diagnostics out of its line, and --dump-outputs
+    writes the last timed clip's latents; two processes with the same arguments write the same array bit for bit."""
+    import json, os, subprocess, sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "EW_FORCE_DIST")}
+    got = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--tiny", "--steps", "2", "--warmup", "0", "--denoise-steps", "2",
+                            "--height", "128", "--width", "256", "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert "cpu_baseline" not in line and line["roofline"]["kernels"] is None and line["config"]["unet_forward_ms_fp16_stream"] is None
+        assert sorted(os.listdir(tmp_path / run)) == ["latents.npy"]
+        got.append(np.load(tmp_path / run / "latents.npy"))
+    assert got[0].dtype == np.float32 and got[0].shape == (1, 25, 4, 16, 32) and np.isfinite(got[0]).all()
+    assert np.array_equal(got[0], got[1])
 
 
 def test_cfg_pair_split_matches_batched_cfg(models):
@@ -212,7 +234,7 @@ def test_bench_cfg_split_one_rank_over_rccl():
     env = dict(os.environ, EW_FORCE_DIST="1", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--tiny", "--steps", "1", "--warmup", "0", "--denoise-steps", "2",
-                        "--height", "128", "--width", "256", "--no-cpu-baseline", "--split", "cfg"], capture_output=True, text=True, env=env, timeout=600)
+                        "--height", "128", "--width", "256", "--full", "--no-cpu-baseline", "--split", "cfg"], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["value"] > 0 and line["config"]["parallelism"] == "cfg1 x dp1" and line["scaling"] == "weak"
@@ -228,7 +250,7 @@ def test_bench_two_ranks_on_one_gpu_over_gloo(split):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "EW_FORCE_DIST")}
     env.update(EW_SHARE_GPU="1", EW_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--tiny", "--steps", "1", "--warmup", "0", "--denoise-steps", "2",
-                        "--height", "128", "--width", "256", "--no-cpu-baseline", "--split", split], capture_output=True, text=True, env=env, timeout=900)
+                        "--height", "128", "--width", "256", "--full", "--no-cpu-baseline", "--split", split], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     assert "weight broadcast to 2 rank(s)" in r.stderr
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -245,7 +267,7 @@ def test_bench_two_cfg_pairs_on_one_gpu_over_gloo():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "EW_FORCE_DIST")}
     env.update(EW_SHARE_GPU="1", EW_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--tiny", "--steps", "1", "--warmup", "0", "--denoise-steps", "2",
-                        "--height", "128", "--width", "256", "--no-cpu-baseline", "--split", "cfg"], capture_output=True, text=True, env=env, timeout=1200)
+                        "--height", "128", "--width", "256", "--full", "--no-cpu-baseline", "--split", "cfg"], capture_output=True, text=True, env=env, timeout=1200)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     assert "weight broadcast to 4 rank(s)" in r.stderr
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

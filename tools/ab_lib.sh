@@ -3,7 +3,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/ab_lib; mkdir -p $O
 for s in old new old new; do
 L=""; [ $s = old ] && L=$R/$1
-EW_LIB_PATH=$L EW_BENCH_FULL_BREAKDOWN=1 EW_BENCH_BY_SHAPE=1 timeout 900 python bench.py --steps 1 --warmup 1 --denoise-steps 4 --no-cpu-baseline --no-fp16-stream > $O/bench_$s.log 2>&1
+EW_LIB_PATH=$L EW_BENCH_FULL_BREAKDOWN=1 EW_BENCH_BY_SHAPE=1 timeout 900 python bench.py --full --steps 1 --warmup 1 --denoise-steps 4 --no-cpu-baseline --no-fp16-stream > $O/bench_$s.log 2>&1
 grep '^{' $O/bench_$s.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$s forward ms', d['config']['unet_forward_ms'])"
 done
 python - <<PY

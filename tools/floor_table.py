@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-launch practical floors of one U-Net forward, from a by-shape breakdown (EW_BENCH_BY_SHAPE=1 EW_BENCH_FULL_BREAKDOWN=1 python bench.py 2> file).
+"""Per-launch practical floors of one U-Net forward, from a by-shape breakdown (EW_BENCH_BY_SHAPE=1 EW_BENCH_FULL_BREAKDOWN=1 python bench.py --full 2> file).
 
 For every launch:  t_mfma = algorithmic flops / R_MFMA,  t_hbm = ideal HBM bytes / R_HBM,  floor = max of the two, where
   R_MFMA = 1300 TFLOP/s   the rate the vendor's assembly GEMMs (hipBLASLt, rocprofv3-timed on the same boxes, DESIGN section 3.1 /

@@ -12,7 +12,7 @@ mkdir -p $REPO/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pmc_t
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmc_t -o p -- python $REPO/bench.py --steps 1 --warmup 0 --denoise-steps 1 --no-cpu-baseline --no-fp16-stream > /tmp/pmc_t.log 2>&1
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $TMPDIR/pmc_t -o p -- python $REPO/bench.py --full --steps 1 --warmup 0 --denoise-steps 1 --no-cpu-baseline --no-fp16-stream > $TMPDIR/pmc_t.log 2>&1
   python - $c $REPO <<'PY'
 import csv, glob, collections, sys, json, os
 c, repo = sys.argv[1], sys.argv[2]
@@ -55,7 +55,7 @@ out = {"recorded_at": {"source_fingerprint": bench.source_fingerprint(), "residu
                        "round": int(os.environ["EW_ROUND"][1:])},
        "bytes_per_forward": read_b + write_b, "read_bytes_per_forward": read_b, "written_bytes_per_forward": write_b,
        "fetch_correction": 2.0, "write_correction": 1.0, "calibration_on_ln_kernel": cal,
-       "method": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes over bench.py --steps 1 --warmup 0 --denoise-steps 1 (two forwards); tools/pmc_traffic.sh"}
+       "method": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes over bench.py --full --steps 1 --warmup 0 --denoise-steps 1 (two forwards); tools/pmc_traffic.sh"}
 json.dump(out, open(os.path.join(repo, "gpurun_out", os.environ["EW_ROUND"] + "_hbm_traffic.json"), "w"), indent=1)
 print(json.dumps(out))
 PY
