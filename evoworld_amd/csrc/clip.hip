@@ -98,8 +98,8 @@ __global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__
 }
 
 // Small-sequence attention: one wave per (sequence, head, query).  q,k,v: fp16 token-major rows (row stride ld, head h at
-// +h*D); D <= 128, D % 8 == 0... handled generically: lanes stride over the D dims for q.k and over keys for the softmax.
-// scores live in LDS per wave (S <= 1024).  fp32 math throughout.
+// +h*D); D % 8 == 0, D <= 256, S <= 2048 (ew_attn_small_f16 checks both): lanes stride over the D dims for q.k and over keys for
+// the softmax.  Scores and the scaled query live in LDS per wave: 4 waves x (S + D) floats, 36 KiB at the limits.  fp32 math throughout.
 __global__ __launch_bounds__(256) void attn_small_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
                                                          const f16* __restrict__ v, f16* __restrict__ o, int n_seq, int S,
                                                          int heads, int D, int ld, int ld_o, float scale) {

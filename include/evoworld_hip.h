@@ -277,7 +277,7 @@ ew_status ew_time_conv3_f32(const float* x, const float* w, const float* bias, f
  *   ew_bicubic_resize_f32  F.interpolate(mode="bicubic", align_corners=True) (A = -0.75), optional per-channel affine
  *                          out = v*scale[c] + shift[c] (folds (x+1)/2 and the CLIP mean / std normalisation)
  *   ew_vit_patchify_f16    pixel_values [N,3,S,S] -> fp16 [N*(S/P)^2, ldk] im2col of the stride-P patch embedding, K order (c,ky,kx)
- *   ew_attn_small_f16      softmax(q k^T * scale) v for short sequences (S <= 2048) and any head_dim % 8 == 0 (ViT-H: 257 x 80),
+ *   ew_attn_small_f16      softmax(q k^T * scale) v for short sequences (S <= 2048) and head_dim % 8 == 0, <= 256 (ViT-H: 257 x 80),
  *                          one wave per query, fp32 math; q,k,v token-major rows with stride ld, head h at +h*D. */
 ew_status ew_blur_axis_f32(const float* x, const float* kern, int ksize, float* out, long long planes, int H, int W, int axis,
                            void* stream);

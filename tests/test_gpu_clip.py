@@ -49,6 +49,35 @@ def test_attn_small_vs_sdpa(n_seq, S, heads, D):
     assert rel_l2(o.float().cpu(), ref.cpu()) < 1e-3
 
 
+# worst-row bounds per case: (bound, value measured on an MI355X); the bound is at most 2x the measurement
+WORST_ROW = {
+    'attn_small 3x1x2x64': (0, 0),  # measured worst row; rel-L2 0 row 0
+    'attn_small 2x257x3x80': (0.0005, 0.000252),  # measured worst row; rel-L2 0.000207 row 464
+    'attn_small 1x1025x2x128': (0.00048, 0.000243),  # measured worst row; rel-L2 0.000207 row 254
+    'attn_small 1x2048x1x256': (0.00048, 0.000244),  # measured worst row; rel-L2 0.000208 row 1329
+    'attn_small 1x2048x2x64': (0.00052, 0.000265),  # measured worst row; rel-L2 0.000208 row 905
+}
+
+
+@pytest.mark.parametrize("n_seq,S,heads,D", [(3, 1, 2, 64), (2, 257, 3, 80), (1, 1025, 2, 128), (1, 2048, 1, 256), (1, 2048, 2, 64)])
+def test_attn_small_declared_limits(n_seq, S, heads, D):
+    """ew_attn_small_f16 up to its declared limits (S <= 2048, D <= 256) with ld > 3C and ld_o > C: guarded, twice-prefilled output
+    (each head writes only its own D columns), fp64 reference"""
+    from evoworld_amd import ops
+    from kernel_checks import report, two_prefills
+    C = heads * D
+    rows = n_seq * S
+    ld, ld_o = 3 * C + 8, C + 64
+    qkv = torch.zeros(rows, ld, dtype=torch.float16, device=DEV)
+    qkv[:, :3 * C] = torch.randn(rows, 3 * C, generator=_g(3)).half().to(DEV)
+    o = two_prefills(lambda o, k: ops.attn_small(qkv, qkv[:, C:], qkv[:, 2 * C:], o, n_seq, S, heads, D, ld, ld_o, D ** -0.5),
+                     (rows, C, torch.float16, dict(ld=ld_o, pad_rows=16)))[0].view
+    q, k, v = (qkv[:, i * C:(i + 1) * C].double().reshape(n_seq, S, heads, D).transpose(1, 2) for i in range(3))
+    ref = F.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(rows, C)
+    case = f"attn_small {n_seq}x{S}x{heads}x{D}"
+    report(case, o, ref, WORST_ROW[case][0], 1e-3)
+
+
 def test_gemm_gelu_epilogue():
     from evoworld_amd import _lib, ops
     lib = _lib.load()

@@ -6,9 +6,16 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_l2
+from kernel_checks import report, two_prefills
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
+# worst-row bounds per case: (bound, value measured on an MI355X); the bound is at most 2x the measurement
+WORST_ROW = {
+    'ff_geglu320 M=129 split out': (3e-05, 1.52e-05),  # measured worst row; rel-L2 6.92e-06 row 14
+    'ff_geglu320 M=300 split out': (3e-05, 1.55e-05),  # measured worst row; rel-L2 7.04e-06 row 80
+    'ff_geglu320 M=51277 split out': (3.2e-05, 1.64e-05),  # measured worst row; rel-L2 6.95e-06 row 1284
+}
 
 
 def _g(s):
@@ -89,6 +96,27 @@ def test_fused_ff_matches_torch_and_two_gemm_path(form, M):
     assert e_ref < (3e-4 if form in ("t_ffin", "t_ff", "plain") else 1e-5 + 3e-4) and e_two < 3e-4
     if isinstance(out_a, ops.Res):        # split output: hi + lo8 carries ~19 bits
         assert e_ref < 2e-4
+
+
+@pytest.mark.parametrize("M", [129, 300, 51277])
+def test_fused_ff_ragged_rows_guarded(M):
+    """M ragged against the 128-row tile: out and out_lo guarded past the last row (the kernel takes no output stride) and twice
+    prefilled; fp64 reference (of the kernel's fp16 hidden operand) on a row sample that includes the last 128 rows"""
+    from evoworld_amd import ops
+    C = 320
+    w1, b1, w2, b2 = _weights(30)
+    x = torch.randn(M, C, generator=_g(31)).half().to(DEV)
+    pack = ops.ff_pack(w1, b1, w2)
+    h = ops.Res.from_float((torch.randn(M, C, generator=_g(32)) * 2).to(DEV))
+    spec = dict(ld=C, pad_rows=128)
+    hi, lo = two_prefills(lambda o, ol, k: ops.ff_geglu320(x, pack, b2, ops.Res(o, ol), r1=h, c_acc=0.8),
+                          (M, C, torch.float16, spec), (M, C, torch.int8, spec))
+    rows = torch.cat([torch.arange(0, max(M - 128, 0), 13), torch.arange(max(M - 128, 0), M)]).to(DEV)
+    pre = x[rows].double() @ w1.double().t() + b1.double()
+    hid = (pre[:, :1280] * F.gelu(pre[:, 1280:])).half().double()
+    ref = 0.8 * (hid @ w2.double().t() + b2.double()) + h.float()[rows].double()
+    case = f"ff_geglu320 M={M} split out"
+    report(case, ops.Res(hi.view, lo.view).float()[rows], ref, WORST_ROW[case][0], 2e-4)
 
 
 def test_fused_ff_is_deterministic_and_times():

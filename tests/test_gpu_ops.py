@@ -8,9 +8,51 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_l2
+from kernel_checks import fill_pattern, report, two_prefills
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
+# worst-row bounds per case: (bound, value measured on an MI355X); the bound is at most 2x the measurement
+WORST_ROW = {
+    'layernorm 37x64 x_out': (1.9e-06, 9.75e-07),  # measured worst row; rel-L2 6.69e-07 row 3
+    'layernorm 37x64': (0.00053, 0.000267),  # measured worst row; rel-L2 0.000213 row 6
+    'layernorm 1001x320 x_out': (1.7e-06, 8.87e-07),  # measured worst row; rel-L2 6.68e-07 row 446
+    'layernorm 1001x320': (0.00049, 0.000247),  # measured worst row; rel-L2 0.000207 row 330
+    'layernorm 9x1280 x_out': (1.4e-06, 7.18e-07),  # measured worst row; rel-L2 6.52e-07 row 1
+    'layernorm 9x1280': (0.00043, 0.000218),  # measured worst row; rel-L2 0.000209 row 0
+    'layernorm 263x2048 x_out': (1.5e-06, 7.66e-07),  # measured worst row; rel-L2 6.72e-07 row 108
+    'layernorm 263x2048': (0.00044, 0.000221),  # measured worst row; rel-L2 0.000208 row 225
+    'groupnorm concat fp16': (0.00047, 0.00024),  # measured worst row; rel-L2 0.000209 row 507
+    'groupnorm concat split ld_y+64': (2.6e-07, 1.32e-07),  # measured worst row; rel-L2 1.05e-07 row 736
+    'attn_spatial 2x8x1': (0.00068, 0.000345),  # measured worst row; rel-L2 0.000244 row 15
+    'attn_spatial_log2 2x8x1': (0.00076, 0.000384),  # measured worst row; rel-L2 0.000252 row 11
+    'attn_spatial 3x144x2': (0.00088, 0.00044),  # measured worst row; rel-L2 0.000268 row 189
+    'attn_spatial_log2 3x144x2': (0.00093, 0.000469),  # measured worst row; rel-L2 0.000278 row 332
+    'attn_spatial 2x576x3': (0.00089, 0.000448),  # measured worst row; rel-L2 0.000253 row 89
+    'attn_spatial_log2 2x576x3': (0.00088, 0.000442),  # measured worst row; rel-L2 0.000254 row 229
+    'attn_spatial 1x2304x2': (0.001, 0.000549),  # measured worst row; rel-L2 0.000249 row 625
+    'attn_spatial_log2 1x2304x2': (0.001, 0.000539),  # measured worst row; rel-L2 0.000251 row 363
+    'attn_spatial 2x200x1': (0.00086, 0.000434),  # measured worst row; rel-L2 0.000248 row 213
+    'attn_spatial_log2 2x200x1': (0.0009, 0.000454),  # measured worst row; rel-L2 0.000257 row 29
+    'attn_spatial 3x136x3': (0.00089, 0.000446),  # measured worst row; rel-L2 0.000271 row 15
+    'attn_spatial_log2 3x136x3': (0.00097, 0.00049),  # measured worst row; rel-L2 0.000275 row 22
+    'attn_spatial 1x1000x2': (0.00095, 0.000479),  # measured worst row; rel-L2 0.00025 row 66
+    'attn_spatial_log2 1x1000x2': (0.00095, 0.000476),  # measured worst row; rel-L2 0.000244 row 448
+    'attn_temporal 2x25x37x2': (0.00069, 0.000349),  # measured worst row; rel-L2 0.000252 row 1165
+    'attn_temporal 1x4x512x1': (0.00082, 0.000412),  # measured worst row; rel-L2 0.000227 row 733
+    'attn_temporal 2x1x9x3': (0, 0),  # measured worst row; rel-L2 0 row 0
+    'attn_temporal 1x32x5x1': (0.00077, 0.000388),  # measured worst row; rel-L2 0.000251 row 49
+    'attn_temporal 2x49x21x2': (0.00068, 0.000345),  # measured worst row; rel-L2 0.000257 row 576
+    'attn_temporal 1x64x7x1': (0.00072, 0.000364),  # measured worst row; rel-L2 0.000262 row 308
+    'attn_temporal 1x33x130x3': (0.00068, 0.00034),  # measured worst row; rel-L2 0.000255 row 272
+    'softmax_rows 77x1024 ld+40 split': (0.00087, 0.000436),  # measured worst row; rel-L2 0.00022 row 31
+    'softmax_rows 300x136 ld+40 hi': (0.00091, 0.000458),  # measured worst row; rel-L2 0.000192 row 19
+    'softmax_rows 9x2048 ld+40 split': (0.00063, 0.000319),  # measured worst row; rel-L2 0.000178 row 5
+}
+
+
+def _wr(case):
+    return WORST_ROW[case][0]
 
 
 def _g(seed):
@@ -276,23 +318,98 @@ def test_layernorm(ops, rows, C):
     assert rel_l2(out3.float().cpu(), F.layer_norm(full, (C,), gh.float(), bh.float(), 1e-5).cpu()) < 4e-4
 
 
+@pytest.mark.parametrize("rows,C", [(37, 64), (1001, 320), (9, 1280), (263, 2048)])
+def test_layernorm_guarded(ops, rows, C):
+    """C up to the declared limit (2048), ragged row counts: y, x_out and x_out_lo guarded past the last row and twice prefilled;
+    fp64 reference of the split input + addvec"""
+    x, g, b = rnd(rows, C, seed=11) * 2 + 0.5, rnd(C, seed=12) * 0.2 + 1, rnd(C, seed=13) * 0.1
+    gh, bh = g.half().to(DEV), b.half().to(DEV)
+    rpg = 7
+    av = rnd((rows + rpg - 1) // rpg, C, seed=14).half().to(DEV)
+    xs = ops.Res.from_float(x.to(DEV))
+    spec = dict(ld=C, pad_rows=16)
+    y, xo, xol = two_prefills(lambda y, xo, xol, k: ops.layernorm(xs, gh, bh, addvec=av, rows_per_group=rpg, x_out=ops.Res(xo, xol), out=y),
+                              (rows, C, torch.float16, spec), (rows, C, torch.float16, spec), (rows, C, torch.int8, spec))
+    full = xs.float().double() + av.double()[torch.arange(rows, device=DEV) // rpg]
+    case = f"layernorm {rows}x{C}"
+    report(case + " x_out", ops.Res(xo.view, xol.view).float(), full, _wr(case + " x_out"), 2e-6)
+    report(case, y.view, F.layer_norm(full, (C,), gh.double(), bh.double(), 1e-5), _wr(case), 4e-4)
+
+
+@pytest.mark.parametrize("split_out", [False, True])
+def test_groupnorm_guarded_concat_and_workspace(ops, split_out):
+    """two sources (the second at c_off = 640, groups straddling the seam), split inputs; output guarded (split form: ld_y = 2C + 64),
+    output AND workspace prefilled twice -- the workspace is "all written before read" (ops.WorkspacePool), so its contents must not matter"""
+    from evoworld_amd import _lib
+    lib = _lib.load()
+    n, rows, Cs = 3, 299, [640, 320]
+    C = sum(Cs)
+    xs = [ops.Res.from_float((rnd(n * rows, c, seed=50 + i, scale=1.5) + 0.3).to(DEV)) for i, c in enumerate(Cs)]
+    gh, bh = (rnd(C, seed=3) * 0.2 + 1).half().to(DEV), (rnd(C, seed=4) * 0.1).half().to(DEV)
+    nws = lib.ew_groupnorm_workspace_floats(n, rows, C, 32)
+    width = 2 * C if split_out else C
+    ld_y = 2 * C + 64 if split_out else C
+
+    def run(y, k):
+        pool = ops.WorkspacePool(DEV, floats=nws + 64)
+        fill_pattern(pool.buf, k)
+        if split_out:                                    # ops.groupnorm passes ld_y = 2C; the strided form goes through the C ABI
+            ws = pool.take(nws)
+            st = ops._stream()
+            off = 0
+            for x in xs:
+                _lib.check(lib.ew_groupnorm_stats_f16(ops._ptr(x.hi), ops._ptr(x.lo), ops._ptr(ws), n, rows, x.hi.shape[1], off, C, 32, st), "stats")
+                off += x.hi.shape[1]
+            _lib.check(lib.ew_groupnorm_finalize(ops._ptr(ws), n, rows, C, 32, st), "finalize")
+            off = 0
+            for x in xs:
+                _lib.check(lib.ew_groupnorm_apply_split_f16(ops._ptr(x.hi), ops._ptr(x.lo), ops._ptr(ws), ops._ptr(gh), ops._ptr(bh), ops._ptr(y),
+                                                            ops._ptr(y[:, C:]), ld_y, n, rows, x.hi.shape[1], off, C, 32, 1e-5, 1, st), "apply_split")
+                off += x.hi.shape[1]
+        else:
+            ops.groupnorm(xs, gh, bh, n, rows, 1e-5, True, out=y, pool=pool)
+    y = two_prefills(run, (n * rows, width, torch.float16, dict(ld=ld_y, pad_rows=64)))[0].view
+    xc = torch.cat([x.float().double() for x in xs], 1).reshape(n, rows, C).permute(0, 2, 1)
+    ref = F.silu(F.group_norm(xc, 32, gh.double(), bh.double(), 1e-5)).permute(0, 2, 1).reshape(n * rows, C)
+    got = (y[:, :C].double() + y[:, C:].double()) if split_out else y
+    case = f"groupnorm concat {'split ld_y+64' if split_out else 'fp16'}"
+    report(case, got, ref, _wr(case), 2e-6 if split_out else 4e-4)
+
+
 # ----------------------------------------------------------------------------- attention
-@pytest.mark.parametrize("n_seq,S,heads", [(2, 8, 1), (3, 144, 2), (2, 576, 3), (1, 2304, 2), (2, 200, 1)])
+@pytest.mark.parametrize("n_seq,S,heads", [(2, 8, 1), (3, 144, 2), (2, 576, 3), (1, 2304, 2), (2, 200, 1), (3, 136, 3), (1, 1000, 2)])
 def test_attn_spatial(ops, n_seq, S, heads):
+    for log2 in (False, True):
+        _attn_spatial_case(ops, n_seq, S, heads, log2)
+
+
+def _attn_spatial_case(ops, n_seq, S, heads, log2):
+    """both spatial cores on S not a multiple of 64 (partial last key / query block), with every stride wider than its data (ld_qk > 2C,
+    ld_vt > rows, ld_o > C): each head may write only its own 64 columns, nothing past the last row; two prefills of o"""
     C = heads * 64
     rows = n_seq * S
-    qk = rnd(rows, 2 * C, seed=1).half().to(DEV)
+    ld_qk, ld_vt, ld_o = 2 * C + 24, rows + 40, C + (8 if heads > 1 else 64)
+    qk32 = torch.zeros(rows, ld_qk)
+    qk32[:, :2 * C] = rnd(rows, 2 * C, seed=1)
+    qk32[: S // 2, :64] *= 4.0   # sharpen some rows so the running max moves between tiles
+    if log2:
+        qk32 *= ops.QK_LOG2_PRESCALE
+    qk = qk32.half().to(DEV)
     v = rnd(rows, C, seed=2).half().to(DEV)
-    qk[: S // 2, :64] *= 4.0   # sharpen some rows so the running max moves between tiles
-    vt = v.T.contiguous()
-    o = torch.empty(rows, C, dtype=torch.float16, device=DEV)
-    ops.attn_spatial(qk, qk[:, C:], vt, o, n_seq, S, heads, 2 * C, rows, C)
-    q = qk[:, :C].float().reshape(n_seq, S, heads, 64).transpose(1, 2)
-    k = qk[:, C:].float().reshape(n_seq, S, heads, 64).transpose(1, 2)
-    vv = v.float().reshape(n_seq, S, heads, 64).transpose(1, 2)
-    ref = F.scaled_dot_product_attention(q, k, vv).transpose(1, 2).reshape(rows, C)
+    vt = torch.zeros(C, ld_vt, dtype=torch.float16, device=DEV)
+    vt[:, :rows] = v.T
+    if log2:
+        fn = lambda o, k: ops.attn_spatial_log2(qk, qk[:, C:], vt, o, n_seq, S, heads, ld_qk, ld_vt, ld_o)
+    else:
+        fn = lambda o, k: ops.attn_spatial(qk, qk[:, C:], vt, o, n_seq, S, heads, ld_qk, ld_vt, ld_o)
+    o = two_prefills(fn, (rows, C, torch.float16, dict(ld=ld_o, pad_rows=64)))[0].view
+    q = qk[:, :C].double().reshape(n_seq, S, heads, 64).transpose(1, 2)
+    k = qk[:, C:2 * C].double().reshape(n_seq, S, heads, 64).transpose(1, 2)
+    vv = v.double().reshape(n_seq, S, heads, 64).transpose(1, 2)
+    ref = F.scaled_dot_product_attention(q, k, vv, scale=math.log(2.0) if log2 else 0.125).transpose(1, 2).reshape(rows, C)
     assert torch.isfinite(o).all()
-    assert rel_l2(o.float().cpu(), ref.cpu()) < 2e-3
+    case = f"attn_spatial{'_log2' if log2 else ''} {n_seq}x{S}x{heads}"
+    report(case, o, ref, _wr(case), 2e-3)
 
 
 @pytest.mark.parametrize("n_seq,S,heads,shift", [(2, 512, 2, 0.0), (1, 1000, 1, 0.0), (3, 136, 5, 0.0), (1, 2304, 1, -60.0), (1, 640, 2, 40.0)])
@@ -359,17 +476,43 @@ def test_attn_spatial_log2_lazy_max(ops, pattern):
 @pytest.mark.parametrize("B,T,S,heads", [(2, 25, 37, 2), (1, 4, 512, 1), (2, 1, 9, 3), (1, 32, 5, 1), (2, 49, 21, 2), (1, 64, 7, 1),
                                          (1, 33, 130, 3)])
 def test_attn_temporal(ops, B, T, S, heads):
+    """ld > 3C, ld_o > C, guarded and twice-prefilled output"""
     C = heads * 64
     rows = B * T * S
-    qkv = rnd(rows, 3 * C, seed=1).half().to(DEV)
-    o = torch.empty(rows, C, dtype=torch.float16, device=DEV)
-    ops.attn_temporal(qkv, qkv[:, C:], qkv[:, 2 * C:], o, B, T, S, heads, 3 * C, C)
+    ld, ld_o = 3 * C + 16, C + (8 if heads > 1 else 64)
+    qkv = torch.zeros(rows, ld, dtype=torch.float16, device=DEV)
+    qkv[:, :3 * C] = rnd(rows, 3 * C, seed=1).half().to(DEV)
+    o = two_prefills(lambda o, k: ops.attn_temporal(qkv, qkv[:, C:], qkv[:, 2 * C:], o, B, T, S, heads, ld, ld_o),
+                     (rows, C, torch.float16, dict(ld=ld_o, pad_rows=64)))[0].view
 
     def split(i):  # [B,T,S,h,64] -> [B,S,h,T,64]
-        return qkv[:, i * C:(i + 1) * C].float().reshape(B, T, S, heads, 64).permute(0, 2, 3, 1, 4)
+        return qkv[:, i * C:(i + 1) * C].double().reshape(B, T, S, heads, 64).permute(0, 2, 3, 1, 4)
     ref = F.scaled_dot_product_attention(split(0), split(1), split(2))            # [B,S,h,T,64]
     ref = ref.permute(0, 3, 1, 2, 4).reshape(rows, C)
-    assert rel_l2(o.float().cpu(), ref.cpu()) < 2e-3
+    case = f"attn_temporal {B}x{T}x{S}x{heads}"
+    report(case, o, ref, _wr(case), 2e-3)
+
+
+@pytest.mark.parametrize("rows,cols,split", [(77, 1024, True), (300, 136, False), (9, 2048, True)])
+def test_softmax_rows_strided(ops, rows, cols, split):
+    """ew_softmax_rows_f16 with ld > cols (the wrapper always passes ld = cols, so the call goes through ctypes directly): hi / lo
+    and out share the row stride; out guarded past the width and the last row, two prefills"""
+    import ctypes
+    from evoworld_amd import _lib
+    lib = _lib.load()
+    ld = cols + 40
+    x = torch.zeros(rows, ld)
+    x[:, :cols] = rnd(rows, cols, seed=7) * 3
+    src = ops.Res.from_float(x.to(DEV)) if split else ops.Res(x.half().to(DEV))
+
+    def run(o, k):
+        _lib.check(lib.ew_softmax_rows_f16(ctypes.c_void_p(src.hi.data_ptr()), ctypes.c_void_p(src.lo.data_ptr()) if split else None,
+                                           ctypes.c_void_p(o.data_ptr()), ctypes.c_longlong(rows), cols, ctypes.c_longlong(ld), ops._stream()),
+                   "ew_softmax_rows_f16")
+    o = two_prefills(run, (rows, cols, torch.float16, dict(ld=ld, pad_rows=8)))[0].view
+    ref = torch.softmax(src.float()[:, :cols].double(), dim=-1)
+    case = f"softmax_rows {rows}x{cols} ld+40 {'split' if split else 'hi'}"
+    report(case, o, ref, _wr(case), 1e-3)
 
 
 # ----------------------------------------------------------------------------- glue

@@ -81,7 +81,7 @@ def test_vae_encode_mode_vs_oracle(vaes):
     assert got.shape == (3, 4, 8, 16)
     e = rel_l2(got.cpu(), want)
     print(f"VAE encode (mode) rel-L2 {e:.3e}")
-    assert e < 3e-3
+    assert e < 7.8e-4                      # measured 6.25e-4 on an MI355X (1.25x)
     assert torch.equal(got, vae.encode(x.to(DEV)).latent_dist.mode())      # deterministic
 
 
@@ -94,7 +94,7 @@ def test_vae_decode_vs_oracle(vaes, n, T):
     assert got.shape == (n, 3, 64, 128)
     e = rel_l2(got.cpu(), want)
     print(f"VAE decode n={n} T={T} rel-L2 {e:.3e}")
-    assert e < 3e-3
+    assert e < 1.4e-3                      # measured 1.147e-3 (n=4, T=4) and 1.134e-3 (n=6, T=3) on an MI355X (1.22x)
 
 
 def test_vae_behind_the_pipeline_duck_type(vaes):
