@@ -12,7 +12,7 @@ from ctypes import c_char_p, c_float, c_int, c_longlong, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EW_LIB_PATH") or os.path.join(_HERE, "libevoworld_hip.so")   # EW_LIB_PATH: another build of the same ABI (A/B tools)
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 # every symbol declared in include/evoworld_hip.h
 SYMBOLS = [
@@ -25,6 +25,7 @@ SYMBOLS = [
     "ew_attn_small_f16",
     "ew_set_cu_budget", "ew_get_cu_budget", "ew_stream_create_cu_mask", "ew_stream_destroy",
     "ew_nchw_f32_to_nhwc_split_f16", "ew_euler_cfg_step_split", "ew_groupnorm_apply_split_f16", "ew_sinusoid_embed_f16",
+    "ew_pano_yaw_rotate",
 ]
 
 
@@ -109,6 +110,7 @@ def load():
         "ew_resize_aa_u8": [P, P, P, P, P, I, P, P, I, I, I, I, I, I, P],
         "ew_u8_hwc_to_f32_chw": [P, P, I, I, I, P],
         "ew_f32_chw_to_u8_hwc": [P, P, I, I, I, P],
+        "ew_pano_yaw_rotate": [P, I, P, P, I, I, I, P],
         "ew_blur_axis_f32": [P, P, I, P, LL, I, I, I, P],
         "ew_bicubic_resize_f32": [P, P, I, I, I, I, I, I, P, P, P],
         "ew_vit_patchify_f16": [P, P, I, I, I, I, P],

@@ -531,6 +531,48 @@ __global__ __launch_bounds__(256) void f32_chw_to_u8_hwc_kernel(const float* __r
     }
 }
 
+// Yaw rotation of equirectangular panoramas (Navigator.rotate_panorama, navigator_evoworld.py:466-512): a nearest-neighbour
+// gather whose source index replays torch's float32 operations one at a time -- x / W * 2 * pi, deg2rad, +, torch.remainder
+// (fmod, then + b when the signs differ), / (2 pi) * W; y / H * pi - pi/2, then (+ pi/2) / pi * H; clamp, truncate.  The pi
+// constants are the Python scalars rounded to float32, as torch rounds them; this file is built with -ffp-contract=off and
+// '/' is the IEEE division, so nothing is fused or reassociated.  The map is separable: ui depends on (view, x), vi on y.
+constexpr float kPiF = 3.14159265358979323846f, kTwoPiF = 6.28318530717958647692f, kHalfPiF = 1.57079632679489661923f;
+constexpr float kDeg2RadF = 0.017453292519943295769f;                     // at::deg2rad's M_PI_180 as a float scalar
+__device__ __forceinline__ int pano_src_col(int x, float Wf, float rad) {
+    const float lon = ((float)x / Wf) * 2.0f * kPiF;
+    float m = fmodf(lon + rad, kTwoPiF);
+    if (m < 0.f) m += kTwoPiF;                                            // b = 2 pi > 0: 'nonzero, signs differ' is m < 0
+    const float uf = (m / kTwoPiF) * Wf;
+    return (int)fminf(fmaxf(uf, 0.f), Wf - 1.f);                          // clamp (a NaN yaw lands on column 0), truncate
+}
+__device__ __forceinline__ int pano_src_row(int y, float Hf) {
+    const float lat = ((float)y / Hf) * kPiF - kHalfPiF;
+    const float vf = ((lat + kHalfPiF) / kPiF) * Hf;
+    return (int)fminf(fmaxf(vf, 0.f), Hf - 1.f);
+}
+// one block = 256 columns of one output row (v, y); U8: src uint8 [V,H,W,3] -> (x/255)*2-1 exactly as u8_hwc_to_f32_chw_kernel
+template <bool U8>
+__global__ __launch_bounds__(256) void pano_yaw_rotate_kernel(const void* __restrict__ src, const float* __restrict__ yaw_deg,
+                                                              float* __restrict__ dst, int H, int W, int nxb) {
+    const int row = (int)(blockIdx.x / nxb);                              // v * H + y
+    const int x = (int)(blockIdx.x - (unsigned)row * nxb) * 256 + threadIdx.x;
+    if (x >= W) return;
+    const int v = row / H, y = row - v * H;
+    const int ui = pano_src_col(x, (float)W, yaw_deg[v] * kDeg2RadF);
+    const int vi = pano_src_row(y, (float)H);
+    const long long HW = (long long)H * W;
+    float* d = dst + (long long)v * 3 * HW + (long long)y * W + x;
+    if (U8) {
+        const uint8_t* s = (const uint8_t*)src + ((long long)v * HW + (long long)vi * W + ui) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) d[c * HW] = ((float)s[c] / 255.0f) * 2.0f - 1.0f;
+    } else {
+        const float* s = (const float*)src + (long long)v * 3 * HW + (long long)vi * W + ui;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) d[c * HW] = s[c * HW];
+    }
+}
+
 }  // namespace
 
 // ================================================================================================ C ABI
@@ -650,6 +692,22 @@ extern "C" ew_status ew_u8_hwc_to_f32_chw(const uint8_t* src, float* dst, int V,
     hipLaunchKernelGGL(u8_hwc_to_f32_chw_kernel, dim3(grid_for((long long)V * H * W / 4 + 1)), dim3(256), 0, (hipStream_t)stream, src,
                        dst, (long long)V, H * W);
     return ew_check_launch("ew_u8_hwc_to_f32_chw");
+}
+
+extern "C" ew_status ew_pano_yaw_rotate(const void* src, int src_u8, const float* yaw_deg, float* dst, int V, int H, int W,
+                                        void* stream) {
+    EW_REQUIRE(src && yaw_deg && dst && V > 0 && H > 0 && W > 0, "ew_pano_yaw_rotate: bad args");
+    EW_REQUIRE(src_u8 == 0 || src_u8 == 1, "ew_pano_yaw_rotate: src_u8 must be 0 or 1");
+    EW_REQUIRE(H < (1 << 24) && W < (1 << 24), "ew_pano_yaw_rotate: H and W must be below 2^24 (exact float coordinates)");
+    EW_REQUIRE((((uintptr_t)yaw_deg | (uintptr_t)dst | (src_u8 ? 0 : (uintptr_t)src)) & 3) == 0, "ew_pano_yaw_rotate: alignment");
+    const int nxb = ew_cdiv(W, 256);
+    const long long nblk = (long long)V * H * nxb;
+    EW_REQUIRE(nblk < (1LL << 31) / 256, "ew_pano_yaw_rotate: grid too large");
+    if (src_u8)
+        hipLaunchKernelGGL(pano_yaw_rotate_kernel<true>, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, src, yaw_deg, dst, H, W, nxb);
+    else
+        hipLaunchKernelGGL(pano_yaw_rotate_kernel<false>, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, src, yaw_deg, dst, H, W, nxb);
+    return ew_check_launch("ew_pano_yaw_rotate");
 }
 
 extern "C" ew_status ew_f32_chw_to_u8_hwc(const float* src, uint8_t* dst, int V, int H, int W, void* stream) {

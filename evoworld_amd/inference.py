@@ -3,6 +3,8 @@
   prepare_batch_data / process_batch     <- evoworld/inference/forward_evoworld.py:119-211          (C1, single clip)
   Navigator.move_forward / navigate_curve_path / split_curve_into_segments / extend_segment
                                          <- evoworld/inference/navigator_evoworld.py:146-154,173-231,303-318,394-448  (C2)
+  Navigator.navigate_path / split_path_into_segments / rotate_panorama
+                                         <- evoworld/inference/navigator_evoworld.py:276-301,335-392,466-512  (C2, non-curve mode)
   UnifiedLoopConsistencyPipeline.process_episode / convert_pano_to_pers
                                          <- unified_loop_consistency.py:299-334,398-492               (C3, N-segment loop)
 
@@ -116,6 +118,87 @@ class Navigator:
         raise NotImplementedError("chaining windows needs decoded frames (output_type='pil'); with output_type='latent' "
                                   "run one window per call (infer_segment=True), as process_episode does")
 
+    @staticmethod
+    def split_path_into_segments(path):
+        """Straight runs between turns (navigator_evoworld.py:276-301): a row whose rotation differs from the previous one
+        (torch.allclose, atol = rtol = 1e-5) starts a new segment whose first pose is the previous position with the new
+        rotation.  -> list of [n,6] float32 tensors on the host.
+        The reference writes into its input when two consecutive rows each turn (`last_step = step` is a row view that the
+        next `last_step[3:6] = ...` writes through); its episode flow never sees that, since every call gets a fresh device
+        copy of the poses.  This runs the same steps on a private copy, so the caller's tensor is never modified."""
+        p = torch.as_tensor(path).detach().to("cpu", torch.float32, copy=True)
+        segments, current = [], []
+        last = p[0]
+        for step in p:
+            if torch.allclose(step[3:6], last[3:6], atol=1e-5):
+                current.append(step.clone())
+                last = step.clone()
+                continue
+            segments.append(current)
+            last[3:6] = step[3:6]
+            current = [last.clone(), step.clone()]
+            last = step
+        if current:
+            segments.append(current)
+        return [torch.stack(s) for s in segments]
+
+    @staticmethod
+    def rotate_panorama(image, rotation_degrees):
+        """Yaw rotation of one panorama (navigator_evoworld.py:466-512), bit-exact, one kernel (ew_pano_yaw_rotate): image fp32
+        [3,H,W] or the 8-bit frame uint8 [H,W,3] (converted x/255*2-1 in the same pass) -> fp32 [3,H,W].  Unlike a plain
+        integer roll the map is not the identity even at 0 degrees: callers rotate only for a non-zero turn, as the reference."""
+        from . import ops
+        return ops.pano_yaw_rotate(image[None].contiguous(), torch.as_tensor(rotation_degrees, dtype=torch.float32).reshape(1))[0]
+
+    @classmethod
+    def turn_start_image(cls, image, rotation_degrees):
+        """The start image of a run after a turn of `rotation_degrees` (navigator_evoworld.py:368-370): rotated when the turn is
+        non-zero, as it is; fp32 [3,H,W] or uint8 [H,W,3] (rotated and converted in one pass) -> fp32 [3,H,W]."""
+        if rotation_degrees != 0:
+            return cls.rotate_panorama(image, rotation_degrees)
+        if image.dtype == torch.uint8:
+            from . import ops
+            return ops.u8_hwc_to_f32_chw(image[None].contiguous())[0]
+        return image
+
+    @classmethod
+    def path_turn(cls, path, segment_id):
+        """The turn navigate_path applies before segment `segment_id`: seg_k[0].yaw - seg_{k-1}[-1].yaw (0 for the first)."""
+        segs = cls.split_path_into_segments(path)
+        return segs[segment_id][0][4] - segs[segment_id - 1][-1][4] if segment_id else torch.zeros(())
+
+    def navigate_path(self, path, start_image, num_inference_steps=25, memorized_images=None, infer_segment=False,
+                      segment_id=None, **pipe_kw):
+        """The non-curve mode (navigator_evoworld.py:335-392): one window per straight run of split_path_into_segments; at
+        each turn the current panorama is rotated in place by seg_k[0].yaw - seg_{k-1}[-1].yaw (only when that is non-zero),
+        then move_forward walks the run (extended to 25 poses when shorter; a longer run yields the pipeline's 25 frames).
+        With infer_segment only segment `segment_id` is generated (the skipped ones still advance the heading); otherwise
+        every segment starts from the previous one's last frame.  start_image: fp32 [3,H,W] in [-1,1] or the 8-bit frame
+        uint8 [H,W,3] (turned and converted in one kernel pass).  Leaves current_pose = the last pose of the last generated
+        segment."""
+        self.memorized_images = memorized_images.clone()
+        segments = self.split_path_into_segments(path)
+        generations, current = [], 0
+        angle = segments[0][0][4]
+        image = start_image
+        for k, segment in enumerate(segments):
+            rotation = segment[0][4] - angle
+            angle = segment[-1][4]
+            if segment_id is not None and current < segment_id and infer_segment:
+                current += 1
+                continue
+            image = self.turn_start_image(image, rotation)
+            frames, n = self.move_forward(image, segment, num_inference_steps=num_inference_steps,
+                                          use_memory=(segment_id != 0), **pipe_kw)
+            generations.append((frames, n))
+            self.current_pose = segment[-1].clone()                      # move_forward's camera_trajectory_raw[n - 1] (:229)
+            current += 1
+            if (infer_segment and current > segment_id) or k == len(segments) - 1:
+                break
+            image = self._last_frame_tensor(frames, min(n, self.num_frames))     # movement[-1] of frames[:n] (:223,383)
+        self.generations = generations
+        return generations
+
     def navigate_curve_path(self, path, start_image, num_inference_steps=25, memorized_images=None, infer_segment=False,
                             segment_id=None, **pipe_kw):
         """Windows [0:25],[24:49],... ; with infer_segment only window `segment_id` is generated (navigator :394-448);
@@ -149,8 +232,9 @@ class UnifiedLoopConsistencyPipeline:
     `depth_model(persp_u8 [F,384,512,3]) -> dict(depth, depth_conf, images, extrinsic, intrinsic)` stands for VGGT (row N4)."""
 
     def __init__(self, pipeline, depth_model, frames_from_latents=None, height=576, width=1024, num_frames=25, num_segments=3,
-                 num_inference_steps=25, pano_size=(1000, 2000), face_res=512):
+                 num_inference_steps=25, pano_size=(1000, 2000), face_res=512, curve_path=True):
         self.nav = Navigator(pipeline, height, width, num_frames)
+        self.curve_path = curve_path                    # --curve_path: navigate_curve_path; False: navigate_path (:255,285)
         self.depth_model, self.frames_from_latents = depth_model, frames_from_latents
         self.height, self.width, self.num_frames, self.num_segments = height, width, num_frames, num_segments
         self.steps = num_inference_steps
@@ -182,7 +266,10 @@ class UnifiedLoopConsistencyPipeline:
         Every generated frame is carried as the 8-bit image the reference's PIL frames hold (:418-419, navigator :214-226).
         With save_dir and save_segment_frames, the per-segment dumps of :432-453 are written: predictions_{seg}/NNN.png
         (the segment's new frames, NNN continuing at seg*(T-1)+1) and perspective_look_at_center_{seg}/NNN.png (the
-        pano->pers views fed to the depth network).  Returns all generated frames float [N,3,H,W] in [-1,1] (25 -> 49 -> 73 ...) on the 8-bit grid."""
+        pano->pers views fed to the depth network).  Returns all generated frames float [N,3,H,W] in [-1,1] (25 -> 49 -> 73 ...) on the 8-bit grid.
+        With curve_path=False segment k is the k-th straight run of Navigator.split_path_into_segments (navigate_path): its start
+        image is the last 8-bit frame rotated by the turn, and only the run's first n frames are kept (frames[:n], so the
+        counts follow the runs' lengths); ValueError when the path or the episode cannot carry num_segments segments."""
         from . import ops
         dev = start_image.device
         camera_params = np.asarray(camera_params, dtype=np.float64)
@@ -190,19 +277,34 @@ class UnifiedLoopConsistencyPipeline:
         cam_t[:, :3] *= pos_scale
         all_u8 = None
         memory = torch.zeros(self.num_frames, 3, self.height, self.width, device=dev)       # 'empty_with_traj' memory
+        if not self.curve_path:
+            runs = self.nav.split_path_into_segments(cam_t)
+            check_path_episode([len(r) for r in runs], len(camera_params), self.num_segments, self.num_frames)
         for seg in range(self.num_segments):
             start_idx, end_idx, _ = RP.calculate_segment_indices(seg)
-            first = start_image if seg == 0 else ops.u8_hwc_to_f32_chw(all_u8[-1:])[0]    # pil_to_tensor(tensor_to_pil(.)) (:418-419)
-            cond = image_latents_fn(first, memory) if image_latents_fn is not None else {}
-            gens = self.nav.navigate_curve_path(cam_t, first, num_inference_steps=self.steps, memorized_images=memory[None],
-                                                infer_segment=True, segment_id=seg, output_type="latent", **cond, **pipe_kw)
-            latents, _n = gens[-1]
+            if self.curve_path:
+                first = start_image if seg == 0 else ops.u8_hwc_to_f32_chw(all_u8[-1:])[0]    # pil_to_tensor(tensor_to_pil(.)) (:418-419)
+                cond = image_latents_fn(first, memory) if image_latents_fn is not None else {}
+                gens = self.nav.navigate_curve_path(cam_t, first, num_inference_steps=self.steps, memorized_images=memory[None],
+                                                    infer_segment=True, segment_id=seg, output_type="latent", **cond, **pipe_kw)
+            else:
+                # the last 8-bit frame: navigate_path turns it by the heading change between the two runs and converts it in
+                # one kernel pass (navigator :365-370); injected conditioning sees the same turned image
+                first = start_image if seg == 0 else all_u8[-1]
+                cond = {}
+                if image_latents_fn is not None:
+                    cond = image_latents_fn(self.nav.turn_start_image(first, self.nav.path_turn(cam_t, seg)), memory)
+                gens = self.nav.navigate_path(cam_t, first, num_inference_steps=self.steps, memorized_images=memory[None],
+                                              infer_segment=True, segment_id=seg, output_type="latent", **cond, **pipe_kw)
+            latents, n = gens[-1]
             if self.frames_from_latents is None:                                          # the pipeline's own VAE decodes (chunks of 8)
                 pipe = self.nav.pipe
                 dec = pipe.decode_latents(latents, self.num_frames, 8)[0].permute(1, 0, 2, 3)      # [T,3,H,W] in [-1,1]
             else:
                 dec = self.frames_from_latents(latents)
             frames_u8 = ops.f32_chw_to_u8_hwc(dec.float().contiguous())
+            if not self.curve_path:
+                frames_u8 = frames_u8[:n]                                               # frames[:num_frames] (navigator :223)
             if all_u8 is not None:
                 frames_u8 = frames_u8[1:]                                               # drop the duplicated first frame (:427-429)
             if save_dir and save_segment_frames:                                        # :432-435, file index continues across segments
@@ -225,6 +327,28 @@ class UnifiedLoopConsistencyPipeline:
                 memory = torch.cat([start_image[None], mem24], dim=0)                      # [episode frame 1] + 24 reprojected (:277-279)
         self.last_frames_u8 = all_u8
         return ops.u8_hwc_to_f32_chw(all_u8)
+
+
+def check_path_episode(run_lengths, n_poses, num_segments, num_frames=25):
+    """States of the non-curve episode loop that the reference cannot get through, refused before any work (ValueError naming
+    the segment): a segment beyond the path's last straight run (navigate_path generates nothing for it); a memory hand-off
+    that has fewer than 2 generated frames (segment k keeps min(run, T) frames, minus the shared first one for k > 0; one
+    frame leaves the first-and-last-point alignment without a direction, reproject_vggt_open3d_utils.py:1126-1213, and the
+    target poses singular); or one whose 24 target views (poses (seg+1)*24+1 ... +24, :487-492) run past the episode."""
+    have = 0
+    for seg in range(num_segments):
+        if seg >= len(run_lengths):
+            raise ValueError(f"segment {seg}: the path splits into only {len(run_lengths)} straight run(s) between turns")
+        have += min(run_lengths[seg], num_frames) - (1 if seg else 0)
+        if seg == num_segments - 1:
+            break
+        if have < 2:
+            raise ValueError(f"segment {seg}: the memory hand-off would align on {have} generated frame(s) (straight runs "
+                             f"of {run_lengths[:seg + 1]} poses); it needs at least 2")
+        need = (seg + 2) * 24 + 1
+        if n_poses < need:
+            raise ValueError(f"segment {seg}: the memory for segment {seg + 1} renders target poses {need - 24}..{need - 1}, "
+                             f"but the episode has {n_poses} poses")
 
 
 def _save_u8_frames(u8_hwc, d, start=0):

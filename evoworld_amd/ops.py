@@ -444,6 +444,32 @@ def f32_chw_to_u8_hwc(src):
     return dst
 
 
+def pano_yaw_rotate(src, yaw_deg):
+    """Yaw rotation of equirectangular panoramas (Navigator.rotate_panorama, navigator_evoworld.py:466-512), bit-exact:
+    src fp32 [V,3,H,W] or uint8 [V,H,W,3] (the 8-bit frames; mapped x/255*2-1 in the same pass), yaw_deg [V] degrees (a float32
+    tensor on any device, or numbers rounded to float32 as torch.tensor(..., dtype=float32) does) -> fp32 [V,3,H,W]."""
+    lib = _lib.load()
+    if src.dtype == torch.uint8:
+        _req(src, torch.uint8, "src")
+        if src.ndim != 4 or src.shape[3] != 3:
+            raise ValueError(f"src: expected uint8 [V,H,W,3], got {tuple(src.shape)}")
+        V, H, W, _ = src.shape
+    else:
+        _req(src, torch.float32, "src")
+        if src.ndim != 4 or src.shape[1] != 3:
+            raise ValueError(f"src: expected fp32 [V,3,H,W], got {tuple(src.shape)}")
+        V, _, H, W = src.shape
+    if isinstance(yaw_deg, torch.Tensor) and yaw_deg.dtype != torch.float32:
+        raise TypeError(f"yaw_deg: expected torch.float32, got {yaw_deg.dtype}")
+    yaw = torch.as_tensor(yaw_deg, dtype=torch.float32).reshape(-1).to(src.device).contiguous()
+    if yaw.numel() != V:
+        raise ValueError(f"yaw_deg: expected {V} yaws (one per panorama), got {yaw.numel()}")
+    dst = torch.empty(V, 3, H, W, dtype=torch.float32, device=src.device)
+    _lib.check(lib.ew_pano_yaw_rotate(_ptr(src), int(src.dtype == torch.uint8), _ptr(yaw), _ptr(dst), V, H, W, _stream()),
+               "ew_pano_yaw_rotate")
+    return dst
+
+
 def blur_axis(x, kern, axis):
     """x fp32 [..., H, W], kern fp32 [k] -> correlation along H (axis 0) or W (axis 1), reflect padding."""
     lib = _lib.load()

@@ -27,7 +27,7 @@ typedef int ew_status;
 #define EW_ERR_UNSUPPORTED (-2)
 #define EW_ERR_HIP (-3)
 
-#define EW_ABI_VERSION 10
+#define EW_ABI_VERSION 11
 int ew_abi_version(void);
 const char* ew_last_error(void);
 
@@ -354,6 +354,14 @@ ew_status ew_u8_hwc_to_f32_chw(const uint8_t* src, float* dst, int V, int H, int
  * round_half_even(clamp(x/2+0.5, 0, 1)*255), i.e. the pipeline's PIL output (pipeline_evoworld.py:727-732 via diffusers
  * VideoProcessor) that unified_loop_consistency.py:418-419,432-436 feeds to the next segment and to pano->pers. */
 ew_status ew_f32_chw_to_u8_hwc(const float* src, uint8_t* dst, int V, int H, int W, void* stream);
+
+/* Yaw rotation of V equirectangular panoramas, one yaw per panorama (Navigator.rotate_panorama, navigator_evoworld.py:466-512,
+ * the turn between two straight runs of navigate_path :335-392): nearest-neighbour gather dst[v,c,y,x] = src[v,c,vi(y),ui(v,x)]
+ * whose indices reproduce the reference's float32 torch operations bit for bit (the sequence is spelled out in csrc/reproject.hip).
+ * src_u8 = 0: src fp32 [V,3,H,W]; src_u8 = 1: src uint8 [V,H,W,3], converted (x/255)*2-1 in the same pass (bit-identical to
+ * ew_u8_hwc_to_f32_chw followed by the fp32 form).  yaw_deg fp32 [V] (device), degrees; dst fp32 [V,3,H,W].  H, W < 2^24;
+ * fp32 operands 4-byte aligned. */
+ew_status ew_pano_yaw_rotate(const void* src, int src_u8, const float* yaw_deg, float* dst, int V, int H, int W, void* stream);
 
 #ifdef __cplusplus
 }

@@ -66,6 +66,20 @@ def synthetic_episode(n_poses=80):
     return np.stack([0.04 * i * np.sin(i / 9), 0 * i, 0.04 * i * np.cos(i / 9), 0 * i, 95 + 3.6 * i, 0 * i], 1)
 
 
+def synthetic_path_episode(num_segments, extra=8, step=0.4):
+    """The episode of runs without --curve_path: straight runs of 25, 24, 24, ... poses joined by in-place 90-degree turns, the
+    last run `extra` poses longer.  synthetic_episode turns at every pose, which the non-curve mode splits into 2-pose runs
+    whose first hand-off has a single frame to align on (refused by evoworld_amd.inference.check_path_episode)."""
+    rows, x, z = [], 0.0, 0.0
+    for k in range(num_segments):
+        yaw = 95.0 + 90.0 * k
+        for _ in range((25 if k == 0 else 24) + (extra if k == num_segments - 1 else 0)):
+            if rows:
+                x, z = x + step * np.sin(np.deg2rad(yaw)), z + step * np.cos(np.deg2rad(yaw))
+            rows.append([x, 0.0, z, 0.0, yaw, 0.0])
+    return np.asarray(rows, np.float64)
+
+
 def _save_frames_u8(u8_hwc, d, start=0):
     from PIL import Image
     os.makedirs(d, exist_ok=True)
@@ -117,7 +131,10 @@ def run_episode(args, ep, pipe, unet, dev, out_dir, synthetic):
     from evoworld_amd.dataset import load_complete_episode_batch
     from evoworld_amd.inference import UnifiedLoopConsistencyPipeline
     from evoworld_amd.stages import load_stages
-    cam = synthetic_episode(24 * args.num_segments + 8) if synthetic else load_camera_poses(ep)     # UNSCALED
+    if synthetic:                                                                                    # UNSCALED
+        cam = synthetic_episode(24 * args.num_segments + 8) if args.curve_path else synthetic_path_episode(args.num_segments)
+    else:
+        cam = load_camera_poses(ep)
     stages = load_stages(args.stages, args, cross_attention_dim=unet._cfg["cross_attention_dim"], camera_params=cam)
     start = None if synthetic else load_complete_episode_batch(ep, args.height, args.width, dev, cam=cam)["first_frame"]
     if start is None:
@@ -126,7 +143,7 @@ def run_episode(args, ep, pipe, unet, dev, out_dir, synthetic):
     pipe.set_components(vae=stages.vae, image_encoder=stages.image_encoder, feature_extractor=stages.feature_extractor)
     loop = UnifiedLoopConsistencyPipeline(pipe, stages.depth_model, height=args.height,
                                           width=args.width, num_frames=args.num_frames, num_segments=args.num_segments,
-                                          num_inference_steps=args.num_inference_steps)
+                                          num_inference_steps=args.num_inference_steps, curve_path=args.curve_path)
     torch.cuda.synchronize()
     t0 = time.time()
     # the unscaled poses go in; process_episode derives the pos-scaled Navigator / Plücker path itself (pos_scale = 0.1);
