@@ -1,0 +1,25 @@
+#!/bin/bash
+# PSNR / SSIM of a run's per-segment dumps on the MI355X: counterpart of the reference's calculate_metrics.sh (same variables).
+# Compares $VIDEO_PATH/<episode>/predictions_gt_$SEGMENT_ID with predictions_$SEGMENT_ID and writes $VIDEO_PATH/$RESULT_PATH.
+# FVD, LPIPS and the latent MSEs need networks this project does not ship; the JSON lists them under "not_computed".
+# PAIR_BY_NAME (default: true for SEGMENT_ID > 0) pairs the frame files both folders share: a later segment holds 24 generated and
+# 25 ground-truth frames, on which the reference's shape assertion fails.
+set -e
+cd "$(dirname "$0")"
+
+CKPT=${CKPT:-MODELS/evoworld_curve_unity}
+OUTPUT_ROOT=${OUTPUT_ROOT:-output}
+VIDEO_PATH=${VIDEO_PATH:-$OUTPUT_ROOT/$(basename $CKPT)/eval_unity_curve}
+NUM_VIDEO=${NUM_VIDEO:-200}
+RESULT_PATH=${RESULT_PATH:-eval_score.json}
+SEGMENT_ID=${SEGMENT_ID:-2}  # Change this to evaluate different segments (0, 1, 2)
+if [ -z "$PAIR_BY_NAME" ]; then
+  if [ "$SEGMENT_ID" -gt 0 ]; then PAIR_BY_NAME=true; else PAIR_BY_NAME=false; fi
+fi
+
+make -s -C evoworld_amd/csrc
+
+CMD="-m evoworld_amd.metrics --data_path $VIDEO_PATH --gt_subdir predictions_gt_$SEGMENT_ID --gen_subdir predictions_$SEGMENT_ID \
+ --result_file $RESULT_PATH --test_length 25 --num_video $NUM_VIDEO"
+[ "$PAIR_BY_NAME" = true ] && CMD="$CMD --pair_by_name"
+python $CMD

@@ -12,7 +12,7 @@ from ctypes import c_char_p, c_float, c_int, c_longlong, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EW_LIB_PATH") or os.path.join(_HERE, "libevoworld_hip.so")   # EW_LIB_PATH: another build of the same ABI (A/B tools)
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 # every symbol declared in include/evoworld_hip.h
 SYMBOLS = [
@@ -26,6 +26,7 @@ SYMBOLS = [
     "ew_set_cu_budget", "ew_get_cu_budget", "ew_stream_create_cu_mask", "ew_stream_destroy",
     "ew_nchw_f32_to_nhwc_split_f16", "ew_euler_cfg_step_split", "ew_groupnorm_apply_split_f16", "ew_sinusoid_embed_f16",
     "ew_pano_yaw_rotate",
+    "ew_video_metrics_workspace_bytes", "ew_video_metrics", "ew_gt_dump_map_u8",
 ]
 
 
@@ -111,6 +112,8 @@ def load():
         "ew_u8_hwc_to_f32_chw": [P, P, I, I, I, P],
         "ew_f32_chw_to_u8_hwc": [P, P, I, I, I, P],
         "ew_pano_yaw_rotate": [P, I, P, P, I, I, I, P],
+        "ew_video_metrics": [P, P, I, I, I, I, I, I, P, P, P, P],
+        "ew_gt_dump_map_u8": [P, P, c_size_t, P],
         "ew_blur_axis_f32": [P, P, I, P, LL, I, I, I, P],
         "ew_bicubic_resize_f32": [P, P, I, I, I, I, I, I, P, P, P],
         "ew_vit_patchify_f16": [P, P, I, I, I, I, P],
@@ -122,6 +125,8 @@ def load():
     lib.ew_select_workspace_bytes.restype = c_size_t
     lib.ew_filter_compact_workspace_bytes.argtypes = [c_size_t]
     lib.ew_filter_compact_workspace_bytes.restype = c_size_t
+    lib.ew_video_metrics_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
+    lib.ew_video_metrics_workspace_bytes.restype = c_size_t
     lib.ew_set_gemm_generation.argtypes = [c_int]
     lib.ew_set_gemm_generation.restype = None
     lib.ew_get_gemm_generation.restype = c_int

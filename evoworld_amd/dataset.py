@@ -85,7 +85,8 @@ def load_single_segment_batch(episode_path, height=576, width=1024, device="cuda
 def load_complete_episode_batch(episode_path, height=576, width=1024, device="cuda", pos_scale=POS_SCALE, cam=None):
     """CameraTrajDataset(sampling 'empty_with_traj', load_complete_episode=True)[idx] as far as process_episode reads it
     (unified_loop_consistency.py:241-268): the first frame and the complete, pos-scaled trajectory.  (The reference also
-    loads every ground-truth panorama for its predictions_gt dumps; the generator never sees them.)"""
+    loads every ground-truth panorama for its predictions_gt dumps; the generator never sees them, and process_episode loads each
+    segment's window lazily through load_gt_window_u8.)"""
     cam = load_camera_poses(episode_path) if cam is None else np.asarray(cam, dtype=float)
     traj = torch.tensor(cam, dtype=torch.float32)
     traj[:, :3] *= pos_scale
@@ -95,3 +96,29 @@ def load_complete_episode_batch(episode_path, height=576, width=1024, device="cu
     else:
         first = None
     return {"first_frame": first, "cam_traj": traj[None], "camera_params": cam, "episode_path": [episode_path]}
+
+
+def load_gt_window_u8(episode_path, start_idx, end_idx, height=576, width=1024, device="cuda", n_poses=None):
+    """The ground-truth frames of one segment window, loaded lazily: panorama ids start_idx+1 .. end_idx (the reference's
+    batch['pixel_values'][0, start_idx:end_idx] of the complete episode, unified_loop_consistency.py:437-439), Pillow-exact
+    resized on the device -> uint8 [n,height,width,3].  The window stops at the first missing panorama (or at n_poses); None
+    when the episode has no panorama for the window's first id (synthetic and pose-only episodes)."""
+    from . import reprojection as RP
+    arrays = []
+    for i in range(start_idx + 1, end_idx + 1):
+        if n_poses is not None and i > n_poses:
+            break
+        f = os.path.join(episode_path, "panorama", f"{i:03}.png")
+        if not (os.path.isfile(f) or os.path.isfile(f[:-4] + ".jpg")):
+            break
+        arrays.append(_open_rgb(f))
+    if not arrays:
+        return None
+    u8 = torch.tensor(np.stack(arrays)).to(device)
+    Hi, Wi = u8.shape[1:3]
+    if (Hi, Wi) == (height, width):
+        return u8.contiguous()
+    from . import ops
+    ch = tuple(t.to(u8.device) for t in RP.resample_coeffs(Wi, width))
+    cv = tuple(t.to(u8.device) for t in RP.resample_coeffs(Hi, height))
+    return ops.resize_aa_u8(u8.contiguous(), ch, cv, height, width)

@@ -249,7 +249,7 @@ class UnifiedLoopConsistencyPipeline:
         return pers, yaws / np.pi * 180.0
 
     def process_episode(self, start_image, camera_params, image_latents_fn=None, save_dir=None, pos_scale=0.1,
-                        save_segment_frames=False, **pipe_kw):
+                        save_segment_frames=False, episode_path=None, **pipe_kw):
         """start_image float [3,H,W] in [-1,1]; camera_params [P,6] numpy: the UNSCALED RDF poses of camera_poses.txt
         (unified_loop_consistency.py:370-395), used as they are for the target yaws and the reprojection alignment; the
         Navigator / Plücker path gets the copy with xyz * pos_scale that the dataset hands out as batch['cam_traj']
@@ -269,7 +269,10 @@ class UnifiedLoopConsistencyPipeline:
         pano->pers views fed to the depth network).  Returns all generated frames float [N,3,H,W] in [-1,1] (25 -> 49 -> 73 ...) on the 8-bit grid.
         With curve_path=False segment k is the k-th straight run of Navigator.split_path_into_segments (navigate_path): its start
         image is the last 8-bit frame rotated by the turn, and only the run's first n frames are kept (frames[:n], so the
-        counts follow the runs' lengths); ValueError when the path or the episode cannot carry num_segments segments."""
+        counts follow the runs' lengths); ValueError when the path or the episode cannot carry num_segments segments.
+        With save_segment_frames and an `episode_path` whose panorama/NNN.png exist, predictions_gt_{seg}/NNN.png is written too
+        (:437-439): the window's ground-truth panoramas (ids start_idx+1 .. end_idx of calculate_segment_indices), Pillow-exact
+        resized and passed through the reference's tensor_to_pil round trip (ops.gt_dump_map_u8), numbered like predictions_{seg}."""
         from . import ops
         dev = start_image.device
         camera_params = np.asarray(camera_params, dtype=np.float64)
@@ -309,6 +312,12 @@ class UnifiedLoopConsistencyPipeline:
                 frames_u8 = frames_u8[1:]                                               # drop the duplicated first frame (:427-429)
             if save_dir and save_segment_frames:                                        # :432-435, file index continues across segments
                 _save_u8_frames(frames_u8, os.path.join(save_dir, f"predictions_{seg}"), seg * (self.num_frames - 1))
+                if episode_path is not None:                                            # :437-439
+                    from .dataset import load_gt_window_u8
+                    gt = load_gt_window_u8(episode_path, start_idx, end_idx, self.height, self.width, dev, len(camera_params))
+                    if gt is not None:
+                        _save_u8_frames(ops.gt_dump_map_u8(gt), os.path.join(save_dir, f"predictions_gt_{seg}"),
+                                        seg * (self.num_frames - 1))
             all_u8 = frames_u8 if all_u8 is None else torch.cat([all_u8, frames_u8], dim=0)
             if seg < self.num_segments - 1:
                 pers, target_yaws = self.convert_pano_to_pers(all_u8, camera_params, seg)

@@ -1,0 +1,204 @@
+"""PSNR / SSIM of generated against ground-truth videos on the device: the counterpart of the reference's
+evoworld/metrics/calculate_all_metrics.py (main :209-236, read_video_our :178-207, arguments :229-258) with
+other_metrics/calculate_psnr.py and calculate_ssim.py.
+
+Per-frame values come from one kernel pass over each frame pair (ops.video_metrics, csrc/metrics.hip); the per-timestamp mean
+and std and the overall mean are the reference's numpy aggregation over those fp64 values.  FVD, LPIPS and the latent MSEs need
+pretrained networks (I3D, LPIPS/AlexNet, the SVD VAE) that this project does not ship: they are listed under `not_computed`.
+
+    python -m evoworld_amd.metrics --data_path OUT --gt_subdir predictions_gt_2 --gen_subdir predictions_2 [--pair_by_name]
+"""
+import argparse
+import json
+import math
+import os
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+SEQUENCE = 25                  # read_video_our keeps the last 25 frames of each folder (:191)
+MAX_DECODE_THREADS = 16
+NOT_COMPUTED = {
+    "fvd": "needs the I3D network (styleganv i3d_torchscript weights) and its code, absent from this project; no network access",
+    "lpips": "needs the LPIPS network (AlexNet backbone and linear-layer weights) and its package, absent; no network access",
+    "latent_mse": "needs the VAE encoder weights (stable-video-diffusion) that map frames to latents, absent; no network access",
+    "loop_closure_latent_mse": "needs the same VAE encoder weights as latent_mse, absent; no network access",
+}
+SUPPORTED = ("psnr", "ssim")
+
+
+def psnr_from_sse(sse, n):
+    """img_psnr of calculate_psnr.py:6-15 from the frame's squared-error sum over n = C*H*W elements."""
+    mse = float(sse) / n
+    if mse < 1e-10:
+        return 100
+    return 20 * math.log10(1 / math.sqrt(mse))
+
+
+def aggregate(results, video_setting):
+    """The reference's aggregation (calculate_psnr.py / calculate_ssim.py, after the per-frame loop): results [B,T] -> dict."""
+    results = np.array(results)
+    value, value_std = {}, {}
+    for t in range(results.shape[1]):
+        value[t] = np.mean(results[:, t])
+        value_std[t] = np.std(results[:, t])
+    return {
+        "value": value,
+        "value_mean": float(np.mean(results)),
+        "value_std": value_std,
+        "video_setting": video_setting,
+        "video_setting_name": "time, channel, heigth, width",
+    }
+
+
+def _per_frame(videos1, videos2, what):
+    """[B,T,C,H,W] float in [0,1] (CPU or device) -> per-frame (sse, ssim) numpy fp64 [B,T] (None where not asked)."""
+    from . import ops
+    if videos1.shape != videos2.shape:
+        raise AssertionError(f"video shapes differ: {tuple(videos1.shape)} vs {tuple(videos2.shape)}")
+    B, T, C, H, W = videos1.shape
+    a = videos1.reshape(B * T, C, H, W).to("cuda", torch.float32).contiguous()
+    b = videos2.reshape(B * T, C, H, W).to("cuda", torch.float32).contiguous()
+    sse, ssim = ops.video_metrics(a, b, what)
+    cpu = lambda x: None if x is None else x.cpu().numpy().reshape(B, T)
+    return cpu(sse), cpu(ssim)
+
+
+def calculate_psnr(videos1, videos2):
+    """calculate_psnr(videos1, videos2) of calculate_psnr.py:18-65: [B,T,C,H,W] in [0,1] -> the reference's result dict."""
+    from . import ops
+    sse, _ = _per_frame(videos1, videos2, ops.METRIC_SSE)
+    n = int(np.prod(videos1.shape[2:]))
+    return aggregate([[psnr_from_sse(s, n) for s in row] for row in sse], videos1[0].shape)
+
+
+def calculate_ssim(videos1, videos2):
+    """calculate_ssim(videos1, videos2) of calculate_ssim.py:48-95 (C = 1 or 3; H, W >= 11) -> the reference's result dict."""
+    from . import ops
+    _, ssim = _per_frame(videos1, videos2, ops.METRIC_SSIM)
+    return aggregate(ssim, videos1[0].shape)
+
+
+def video_metrics_u8(gt, gen):
+    """uint8 [F,H,W,3] device tensors -> (psnr, ssim) numpy fp64 [F]: the per-frame values of the reference's main on frames
+    read as uint8 and divided by 255.0."""
+    from . import ops
+    sse, ssim = ops.video_metrics(gt.contiguous(), gen.contiguous())
+    n = int(np.prod(gt.shape[1:]))
+    return np.array([psnr_from_sse(s, n) for s in sse.cpu().numpy()], dtype=np.float64), ssim.cpu().numpy()
+
+
+# ------------------------------------------------------------------ the evaluation CLI
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description="PSNR / SSIM of generated against ground-truth frame folders on the GPU "
+                                            "(calculate_all_metrics.py)")
+    p.add_argument("--data_path", type=str, default="data/Segment_Consistency/test")
+    p.add_argument("--gt_subdir", type=str, default="predictions_gt_1")
+    p.add_argument("--gen_subdir", type=str, default="predictions_1")
+    p.add_argument("--result_file", type=str, default="eval_score.json", help="written under --data_path")
+    p.add_argument("--num_videos", type=int, default=100)
+    p.add_argument("--test_length", type=int, default=25, help="parsed and ignored, as in the reference")
+    p.add_argument("--metrics", type=str, default="psnr,ssim",
+                   help="comma-separated; psnr and ssim are computed, the others need networks this project lacks")
+    p.add_argument("--pair_by_name", action="store_true",
+                   help="pair the last 25 file names both folders share (segments >= 1 hold 24 generated and 25 GT frames)")
+    args = p.parse_args(argv)
+    args.result_file = os.path.join(args.data_path, args.result_file)
+    return args
+
+
+def selected_metrics(spec):
+    names = [m.strip() for m in spec.split(",") if m.strip()]
+    for m in names:
+        if m in NOT_COMPUTED:
+            raise ValueError(f"metric {m!r} cannot be computed: it {NOT_COMPUTED[m]}")
+        if m not in SUPPORTED:
+            raise ValueError(f"unknown metric {m!r} (computed: {', '.join(SUPPORTED)}; not available: {', '.join(NOT_COMPUTED)})")
+    if not names:
+        raise ValueError("--metrics selects nothing")
+    return names
+
+
+def list_episode_folders(data_path, num_videos=None):
+    """read_video_our's episode list (:185-190): the sorted sub-directories of data_path, the first num_videos of them."""
+    eps = sorted(d for d in os.listdir(data_path) if os.path.isdir(os.path.join(data_path, d)))
+    return eps[:num_videos] if num_videos else eps
+
+
+def frame_pairs(data_path, episode, gt_subdir, gen_subdir, pair_by_name=False):
+    """(gt paths, gen paths) of one episode: sorted(listdir)[-25:] of each folder (:191), or with pair_by_name the last 25 file
+    names both folders hold.  ValueError naming the episode when the two counts differ (the reference fails its shape assert)."""
+    gd, nd = os.path.join(data_path, episode, gt_subdir), os.path.join(data_path, episode, gen_subdir)
+    gt, gen = sorted(os.listdir(gd)), sorted(os.listdir(nd))
+    if pair_by_name:
+        gt = gen = sorted(set(gt) & set(gen))[-SEQUENCE:]
+        if not gt:
+            raise ValueError(f"episode {episode}: {gt_subdir} and {gen_subdir} share no file name")
+    else:
+        gt, gen = gt[-SEQUENCE:], gen[-SEQUENCE:]
+        if len(gt) != len(gen):
+            raise ValueError(f"episode {episode}: {gt_subdir} holds {len(gt)} frames and {gen_subdir} holds {len(gen)}; the "
+                             f"reference's shape assertion fails here (pair the shared frame names with --pair_by_name)")
+    return [os.path.join(gd, f) for f in gt], [os.path.join(nd, f) for f in gen]
+
+
+def _decode(path):
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.asarray(im.convert("RGB"))
+
+
+def evaluate(args, device="cuda"):
+    """main(args) of calculate_all_metrics.py:209-236 for PSNR / SSIM: one episode at a time is decoded (thread pool) and streamed
+    to the device as uint8.  Returns (result dict, timing dict)."""
+    names = selected_metrics(args.metrics)
+    episodes = list_episode_folders(args.data_path, args.num_videos)
+    if not episodes:
+        raise ValueError(f"no episode folders under {args.data_path}")
+    psnr, ssim, shape = [], [], None
+    t_decode = t_device = 0.0
+    with ThreadPoolExecutor(max_workers=min(MAX_DECODE_THREADS, os.cpu_count() or 1)) as pool:
+        for ep in episodes:
+            gp, np_ = frame_pairs(args.data_path, ep, args.gt_subdir, args.gen_subdir, args.pair_by_name)
+            t0 = time.perf_counter()
+            frames = list(pool.map(_decode, gp + np_))
+            gt, gen = np.stack(frames[:len(gp)]), np.stack(frames[len(gp):])
+            t1 = time.perf_counter()
+            if gt.shape != gen.shape:
+                raise ValueError(f"episode {ep}: ground-truth frames {gt.shape} and generated frames {gen.shape} differ")
+            if shape is not None and gt.shape != shape:
+                raise ValueError(f"episode {ep}: frames {gt.shape} differ from the first episode's {shape}")
+            shape = gt.shape
+            p, s = video_metrics_u8(torch.from_numpy(gt).to(device), torch.from_numpy(gen).to(device))
+            t_device += time.perf_counter() - t1
+            t_decode += t1 - t0
+            psnr.append(p)
+            ssim.append(s)
+    T, H, W, C = shape
+    setting = torch.Size([T, C, H, W])
+    result = {}
+    if "ssim" in names:
+        result["ssim"] = aggregate(ssim, setting)
+    if "psnr" in names:
+        result["psnr"] = aggregate(psnr, setting)
+    result["not_computed"] = dict(NOT_COMPUTED)
+    return result, {"episodes": len(episodes), "frames": len(episodes) * T, "decode_s": t_decode, "device_s": t_device}
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    os.makedirs(os.path.dirname(args.result_file) or ".", exist_ok=True)
+    result, timing = evaluate(args)
+    print(json.dumps(result, indent=4))
+    with open(args.result_file, "w") as f:
+        json.dump(result, f, indent=4)
+    print(f"metrics: {timing['episodes']} episodes, {timing['frames']} frame pairs; PNG decode {timing['decode_s']:.3f} s, "
+          f"device {timing['device_s']:.3f} s -> {args.result_file}", file=sys.stderr)
+    return result, timing
+
+
+if __name__ == "__main__":
+    main()

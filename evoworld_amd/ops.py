@@ -470,6 +470,56 @@ def pano_yaw_rotate(src, yaw_deg):
     return dst
 
 
+
+METRIC_SSE, METRIC_SSIM = 1, 2
+
+
+def video_metrics(a, b, what=METRIC_SSE | METRIC_SSIM, sse=None, ssim=None):
+    """Per-frame PSNR / SSIM inputs of frame pairs (ew_video_metrics; calculate_psnr.py:6-15, calculate_ssim.py:6-40): a, b
+    uint8 [F,H,W,C] (a pixel is float32(k) / 255.0f) or fp32 [F,C,H,W], C = 1 or 3 -> (sse, ssim), fp64 [F] device tensors
+    (None where `what` does not ask for it): sse = the frame's sum of float32 (a - b)^2 in fp64, ssim = the reference's per-frame
+    SSIM (mean over the channels).  `sse` / `ssim` may be given as fp64 [F] device views to write into."""
+    lib = _lib.load()
+    if a.dtype == torch.uint8:
+        layout = 0
+        _req(a, torch.uint8, "a")
+        _req(b, torch.uint8, "b")
+        if a.ndim != 4:
+            raise ValueError(f"a: expected uint8 [F,H,W,C], got {tuple(a.shape)}")
+        F_, H, W, C = a.shape
+    else:
+        layout = 1
+        _req(a, torch.float32, "a")
+        _req(b, torch.float32, "b")
+        if a.ndim != 4:
+            raise ValueError(f"a: expected fp32 [F,C,H,W], got {tuple(a.shape)}")
+        F_, C, H, W = a.shape
+    if b.shape != a.shape or b.device != a.device:
+        raise ValueError(f"a {tuple(a.shape)} on {a.device} and b {tuple(b.shape)} on {b.device} differ")
+    out = []
+    for flag, t, name in ((METRIC_SSE, sse, "sse"), (METRIC_SSIM, ssim, "ssim")):
+        if what & flag and t is None:
+            t = torch.empty(F_, dtype=torch.float64, device=a.device)
+        if t is not None:
+            _req(t, torch.float64, name)
+            if t.numel() != F_:
+                raise ValueError(f"{name}: expected {F_} values, got {t.numel()}")
+        out.append(t if what & flag else None)
+    ws = torch.empty(max(1, lib.ew_video_metrics_workspace_bytes(F_, C, H, W)), dtype=torch.uint8, device=a.device)
+    _lib.check(lib.ew_video_metrics(_ptr(a), _ptr(b), layout, F_, C, H, W, int(what), _ptr(out[0]), _ptr(out[1]), _ptr(ws), _stream()),
+               "ew_video_metrics")
+    return out[0], out[1]
+
+
+def gt_dump_map_u8(src):
+    """The 8-bit ground-truth frame the reference's episode mode dumps (ew_gt_dump_map_u8: k/255 -> x*2-1 -> tensor_to_pil's
+    truncating (x*0.5+0.5)*255, a fixed 256-entry map): uint8 tensor of any shape (device) -> a new one of the same shape."""
+    lib = _lib.load()
+    _req(src, torch.uint8, "src")
+    dst = torch.empty_like(src)
+    _lib.check(lib.ew_gt_dump_map_u8(_ptr(src), _ptr(dst), src.numel(), _stream()), "ew_gt_dump_map_u8")
+    return dst
+
 def blur_axis(x, kern, axis):
     """x fp32 [..., H, W], kern fp32 [k] -> correlation along H (axis 0) or W (axis 1), reflect padding."""
     lib = _lib.load()

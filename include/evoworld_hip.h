@@ -27,7 +27,7 @@ typedef int ew_status;
 #define EW_ERR_UNSUPPORTED (-2)
 #define EW_ERR_HIP (-3)
 
-#define EW_ABI_VERSION 11
+#define EW_ABI_VERSION 12
 int ew_abi_version(void);
 const char* ew_last_error(void);
 
@@ -362,6 +362,26 @@ ew_status ew_f32_chw_to_u8_hwc(const float* src, uint8_t* dst, int V, int H, int
  * ew_u8_hwc_to_f32_chw followed by the fp32 form).  yaw_deg fp32 [V] (device), degrees; dst fp32 [V,3,H,W].  H, W < 2^24;
  * fp32 operands 4-byte aligned. */
 ew_status ew_pano_yaw_rotate(const void* src, int src_u8, const float* yaw_deg, float* dst, int V, int H, int W, void* stream);
+
+/* Per-frame PSNR / SSIM inputs of video pairs (ABI 12; evoworld/metrics/calculate_all_metrics.py:222-226, which runs
+ * other_metrics/calculate_psnr.py:6-15 and calculate_ssim.py:6-40 per frame and channel in float64 on the CPU).
+ * a, b: layout 0 = uint8 [F,H,W,C] (a pixel is float32(k) / 255.0f, correctly rounded, as torch's uint8 / 255.0),
+ *       layout 1 = fp32 [F,C,H,W] (values as they are).  C = 1 or 3.  what: bit 0 SSE, bit 1 SSIM.
+ * sse [F] (fp64, device): sum over C*H*W of d*d with d = a - b and d*d both rounded to float32 (numpy on float32 arrays), summed in
+ *   fp64; the caller forms mse = sse / (C*H*W) and PSNR (100 when mse < 1e-10).
+ * ssim [F] (fp64, device): the widened values, window outer(g, g) with g = cv2.getGaussianKernel(11, 1.5) (double), 'valid' region
+ *   only ([5:-5, 5:-5]: no border handling), sigma^2 = E[x^2] - mu^2, C1 = 0.01^2, C2 = 0.03^2; the map's mean over (H-10)*(W-10)
+ *   per channel, then the mean over the channels.  Needs H, W >= 11.
+ * Fixed-order partial sums, no atomics: two calls are bit-identical.  workspace: ew_video_metrics_workspace_bytes(F, C, H, W) bytes
+ * (8-byte aligned).  Refused: C not in {1, 3}, F, H or W <= 0, H or W < 11 with SSIM, a NULL output that `what` asks for. */
+size_t ew_video_metrics_workspace_bytes(int F, int C, int H, int W);
+ew_status ew_video_metrics(const void* a, const void* b, int layout, int F, int C, int H, int W, int what, double* sse, double* ssim,
+                           void* workspace, void* stream);
+
+/* The 8-bit ground-truth frame of the episode-mode dumps predictions_gt_{seg}/NNN.png (unified_loop_consistency.py:87-93,437-439):
+ * the resized uint8 frame k -> ToTensor (k / 255) -> x*2 - 1 -> (x*0.5 + 0.5).clamp(0, 1).mul(255).byte(), every step a float32
+ * rounding and the last a truncation, i.e. a fixed 256-entry map (63 levels come out one lower).  src, dst uint8 [n]. */
+ew_status ew_gt_dump_map_u8(const uint8_t* src, uint8_t* dst, size_t n, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,129 @@
+#!/usr/bin/env python3
+"""PSNR / SSIM evaluation on the MI355X: kernel time per 25-frame 576x1024 pair and the CLI end to end.
+
+  python tools/bench_metrics.py kernel [--iters N]        ew_video_metrics on 25 seeded uint8 frame pairs (event-timed; run under
+                                                           `rocprofv3 --kernel-trace --stats` for the per-kernel split); input
+                                                           GB/s = 2 x 25 x 576 x 1024 x 3 bytes over the call time, against 8 TB/s
+  python tools/bench_metrics.py cli --root DIR [--episodes 20]   writes DIR/ep_NNN/{predictions_gt_0,predictions_0}/001..025.png and
+                                                           times evoworld_amd.metrics over them: PNG decode vs device seconds
+  python tools/bench_metrics.py episode --root DIR [--poses 80]  writes a seeded episode tree DIR/case_000 (camera_poses.txt and
+                                                           panorama/NNN.png, 500x1000) for run_unified_pipeline.sh BASE_FOLDER=DIR
+Each mode prints one JSON line."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+F, H, W = 25, 576, 1024
+HBM_TBS = 8.0
+
+
+def seeded_pair(seed, F_=F, H_=H, W_=W):
+    """ground truth: smooth moving pattern; generated: the same plus noise of a few levels (device uint8 [F,H,W,3] each)"""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    y = torch.arange(H_, device="cuda", dtype=torch.float32)[:, None, None]
+    x = torch.arange(W_, device="cuda", dtype=torch.float32)[None, :, None]
+    c = torch.arange(3, device="cuda", dtype=torch.float32)[None, None, :]
+    frames = [(128 + 100 * torch.sin(0.011 * x * (c + 1) + 0.017 * y + 0.3 * f + seed)).round().clamp(0, 255) for f in range(F_)]
+    gt = torch.stack(frames).to(torch.uint8)
+    noise = torch.randint(-8, 9, gt.shape, device="cuda", generator=g, dtype=torch.int16)
+    gen = (gt.to(torch.int16) + noise).clamp(0, 255).to(torch.uint8)
+    return gt.contiguous(), gen.contiguous()
+
+
+def bench_kernel(iters):
+    from evoworld_amd import ops
+    gt, gen = seeded_pair(0)
+    sse = torch.empty(F, dtype=torch.float64, device="cuda")
+    ssim = torch.empty(F, dtype=torch.float64, device="cuda")
+    for _ in range(5):
+        ops.video_metrics(gt, gen, sse=sse, ssim=ssim)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        ops.video_metrics(gt, gen, sse=sse, ssim=ssim)
+    e1.record()
+    torch.cuda.synchronize()
+    us = e0.elapsed_time(e1) * 1e3 / iters
+    nbytes = 2 * F * H * W * 3
+    return {"mode": "kernel", "frames": F, "shape": [H, W, 3], "us_per_call": round(us, 1), "us_per_frame": round(us / F, 2),
+            "input_GBps": round(nbytes / us / 1e3, 1), "hbm_fraction": round(nbytes / us / 1e6 / HBM_TBS, 4), "iters": iters,
+            "note": "event-timed call (both kernels + the workspace allocation); kernel time: rocprofv3 --kernel-trace --stats"}
+
+
+def write_cli_tree(root, episodes):
+    from concurrent.futures import ThreadPoolExecutor
+    from PIL import Image
+    jobs = []
+    for e in range(episodes):
+        gt, gen = (t.cpu().numpy() for t in seeded_pair(e + 1))
+        for sub, v in (("predictions_gt_0", gt), ("predictions_0", gen)):
+            d = os.path.join(root, f"ep_{e:03d}", sub)
+            os.makedirs(d, exist_ok=True)
+            jobs += [(v[t], os.path.join(d, f"{t + 1:03}.png")) for t in range(F)]
+    with ThreadPoolExecutor(16) as pool:
+        list(pool.map(lambda j: Image.fromarray(j[0]).save(j[1], compress_level=1), jobs))
+
+
+def bench_cli(root, episodes):
+    from evoworld_amd import metrics as M
+    t0 = time.perf_counter()
+    write_cli_tree(root, episodes)
+    t_write = time.perf_counter() - t0
+    argv = ["--data_path", root, "--gt_subdir", "predictions_gt_0", "--gen_subdir", "predictions_0", "--num_videos", str(episodes)]
+    M.evaluate(M.parse_args(argv + ["--num_videos", "1"]))                    # warm-up: library load, first launches
+    t0 = time.perf_counter()
+    res, timing = M.evaluate(M.parse_args(argv))
+    total = time.perf_counter() - t0
+    return {"mode": "cli", "episodes": timing["episodes"], "frame_pairs": timing["frames"], "seconds_total": round(total, 3),
+            "seconds_png_decode": round(timing["decode_s"], 3), "seconds_device": round(timing["device_s"], 3),
+            "decode_fraction": round(timing["decode_s"] / total, 3), "psnr_mean": res["psnr"]["value_mean"],
+            "ssim_mean": res["ssim"]["value_mean"], "seconds_writing_tree": round(t_write, 1),
+            "note": "device = host->device copy + both kernels + the per-frame results back, per episode"}
+
+
+def write_episode(root, poses):
+    from PIL import Image
+    ep = os.path.join(root, "case_000")
+    os.makedirs(os.path.join(ep, "panorama"), exist_ok=True)
+    with open(os.path.join(ep, "camera_poses.txt"), "w") as f:                # Unity convention, one straight walk with a slow turn
+        f.write("Frame,PosX,PosY,PosZ,RotX,RotY,RotZ\n")
+        x = z = 0.0
+        for i in range(poses):
+            yaw = 10.0 + 0.5 * i
+            if i:
+                x, z = x + 0.4 * np.sin(np.deg2rad(yaw)), z + 0.4 * np.cos(np.deg2rad(yaw))
+            f.write(f"{i + 1},{float(x)!r},1.78,{float(z)!r},0.0,{yaw!r},0.0\n")
+    yy, xx = np.mgrid[0:500, 0:1000]
+    for i in range(1, poses + 1):
+        img = np.stack([(128 + 100 * np.sin(0.013 * (xx + 9 * i) * (c + 1) + 0.02 * yy)) for c in range(3)], -1)
+        Image.fromarray(np.clip(img, 0, 255).astype(np.uint8)).save(os.path.join(ep, "panorama", f"{i:03}.png"), compress_level=1)
+    return {"mode": "episode", "episode": ep, "poses": poses}
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("mode", choices=["kernel", "cli", "episode"])
+    p.add_argument("--iters", type=int, default=50)
+    p.add_argument("--root", help="directory the cli / episode modes write their PNG trees to")
+    p.add_argument("--episodes", type=int, default=20)
+    p.add_argument("--poses", type=int, default=80)
+    a = p.parse_args()
+    if a.mode == "kernel":
+        rec = bench_kernel(a.iters)
+    elif a.mode == "cli":
+        rec = bench_cli(a.root, a.episodes)
+    else:
+        rec = write_episode(a.root, a.poses)
+    print(json.dumps(rec), flush=True)
+
+
+if __name__ == "__main__":
+    main()

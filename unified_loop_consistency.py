@@ -148,8 +148,9 @@ def run_episode(args, ep, pipe, unet, dev, out_dir, synthetic):
     t0 = time.time()
     # the unscaled poses go in; process_episode derives the pos-scaled Navigator / Plücker path itself (pos_scale = 0.1);
     # --save_frames also writes the reference's per-segment dumps predictions_{seg}/ and perspective_look_at_center_{seg}/
+    # ... and, for an episode folder with panoramas, the ground-truth windows predictions_gt_{seg}/ (:437-439)
     frames = loop.process_episode(start, cam, save_dir=out_dir if args.save_frames else None,
-                                  save_segment_frames=args.save_frames)
+                                  save_segment_frames=args.save_frames, episode_path=None if synthetic else ep)
     torch.cuda.synchronize()
     dt = time.time() - t0
     if args.save_frames:
