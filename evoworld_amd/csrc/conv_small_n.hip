@@ -132,19 +132,15 @@ __global__ __launch_bounds__(64 * WAVES, 4) void conv_small_n_kernel(const GemmP
 
 }  // namespace
 
-// true when the problem is a stride-1 "same" 3x3 conv with at most 16 output channels and a bias-only epilogue
-bool ew_conv_small_n_wants(const GemmP& p) {
-    return p.mode == EW_A_CONV3X3 && p.N <= 16 && p.N % 4 == 0 && p.stride == 1 && !p.upsample && !p.conv_shift && p.h_in == p.h_out && p.w_in == p.w_out &&
-           !p.rowbias && !p.r1 && !p.r2 && !p.out_lo && p.act == EW_ACT_NONE && p.M >= 4096 && ((p.N + 3) / 4 * 4) * (p.K * 2 + 16) + 64 <= 80 * 1024;
-}
-
-extern char g_gemm_last_kernel[64];
-
-ew_status ew_conv_small_n_dispatch(const GemmP& p, hipStream_t s) {
+// takes stride-1 "same" 3x3 convs with at most 16 output channels and a bias-only epilogue
+ew_status ew_conv_small_n_try(const GemmP& p, hipStream_t s, bool* taken) {
+    *taken = p.mode == EW_A_CONV3X3 && p.N <= 16 && p.N % 4 == 0 && p.stride == 1 && !p.upsample && !p.conv_shift && p.h_in == p.h_out && p.w_in == p.w_out &&
+             !p.rowbias && !p.r1 && !p.r2 && !p.out_lo && p.act == EW_ACT_NONE && p.M >= 4096 && ((p.N + 3) / 4 * 4) * (p.K * 2 + 16) + 64 <= 80 * 1024;
+    if (!*taken) return EW_OK;
     const int NR = (p.N + 3) / 4 * 4;
     const int lds = NR * (p.K * 2 + 16) + 64;
     const int grid = ew_cdiv(p.M, PIX_PER_WG);
-    snprintf(g_gemm_last_kernel, 64, "conv_small_n_kernel<%d>", NR);
+    ew_gemm_note_kernel("conv_small_n_kernel<%d>", NR);
 #define CSN_LAUNCH(NR_)                                                                                                 \
     do {                                                                                                                \
         static std::atomic<unsigned long long> mask{0};                                                                 \

@@ -21,9 +21,6 @@
 #include "gemm_common.h"
 #include <type_traits>
 
-
-extern char g_gemm_last_kernel[64];
-
 namespace {
 
 #define EW_WAIT_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
@@ -509,7 +506,7 @@ ew_status launch2(const GemmP& p, hipStream_t s) {
     if (tiles <= 0 || tiles > 0x7fffffffLL) { ew_set_error("ew_gemm_f16: bad grid"); return EW_ERR_INVALID_ARG; }
     int grid = (NW == 8 || BM == 256) ? ew_cu_budget() : 2 * ew_cu_budget();                   // persistent: 1 x 8-wave or 2 x 4-wave workgroups per CU (256 CUs)
     if (tiles < grid) grid = (int)((tiles + 7) / 8 * 8);
-    snprintf(g_gemm_last_kernel, 64, "gemm2_kernel<%d, %d, %d, %d, %d, %d, %d>", BM, BN, WAVES_M, WAVES_N, NSTAGE, MODE, EPI);
+    ew_gemm_note_kernel("gemm2_kernel<%d, %d, %d, %d, %d, %d, %d>", BM, BN, WAVES_M, WAVES_N, NSTAGE, MODE, EPI);
     hipLaunchKernelGGL((gemm2_kernel<BM, BN, WAVES_M, WAVES_N, NSTAGE, MODE, EPI>), dim3(grid), dim3(64 * NW), lds, s, q);
     return ew_check_launch("ew_gemm_f16(gen2)");
 }
@@ -528,42 +525,32 @@ ew_status dispatch_tile(const GemmP& p, hipStream_t s) {
     }
 }
 
-// operand sets that occur in the U-Net (evoworld_amd/unet.py); any other mask runs on the smallest compiled superset
+// run-time EPI (ew_gemm_select_epi) -> the variants compiled for MODE
 template <int MODE>
-ew_status dispatch_epi(const GemmP& p, hipStream_t s) {
-    if (p.act == EW_ACT_GEGLU) {
-        if constexpr (MODE == EW_A_DENSE) return dispatch_tile<MODE, 8>(p, s);
-        else { ew_set_error("ew_gemm_f16: GEGLU epilogue is only built for dense mode"); return EW_ERR_UNSUPPORTED; }
+ew_status dispatch_epi(const GemmP& p, int epi, hipStream_t s) {
+    constexpr bool D = MODE == EW_A_DENSE;
+    switch (epi) {        // (keep the order: hipcc emits the kernels in it)
+    case 8: if constexpr (D) return dispatch_tile<MODE, 8>(p, s); break;
+    case 16 | 2: if constexpr (!D) return dispatch_tile<MODE, 16 | 2>(p, s); break;
+    case 16 | 3: return dispatch_tile<MODE, 16 | 3>(p, s);
+    case 16 | 7: if constexpr (D) return dispatch_tile<MODE, 16 | 7>(p, s); break;
+    case 0: return dispatch_tile<MODE, 0>(p, s);
+    case 1: return dispatch_tile<MODE, 1>(p, s);
+    case 2: return dispatch_tile<MODE, 2>(p, s);
+    case 3: if constexpr (D) return dispatch_tile<MODE, 3>(p, s); break;
+    case 6: if constexpr (D) return dispatch_tile<MODE, 6>(p, s); break;
+    case 7: return dispatch_tile<MODE, 7>(p, s);
     }
-    const int mask = (p.rowbias ? 1 : 0) | (p.r1 ? 2 : 0) | (p.r2 ? 4 : 0);
-    if (p.r1_lo || p.r2_lo || p.out_lo) {           // split-fp16 residual stream
-        if constexpr (MODE == EW_A_DENSE) {
-            if ((mask & 4) == 0) return dispatch_tile<MODE, 16 | 3>(p, s);
-            return dispatch_tile<MODE, 16 | 7>(p, s);
-        } else {
-            if ((mask & 5) == 0) return dispatch_tile<MODE, 16 | 2>(p, s);
-            // row-bias + split output (round 3: the conv1 / temporal conv1 outputs of the resblocks, GroupNorm inputs whose fp16
-            // rounding was the largest remaining storage term of the parity budget); r1 may be null (zero page)
-            if ((mask & 4) == 0) return dispatch_tile<MODE, 16 | 3>(p, s);
-            ew_set_error("ew_gemm_f16: conv modes carry the split residual with row-bias / r1 only (no r2)");
-            return EW_ERR_UNSUPPORTED;
-        }
-    }
-    if (mask == 0) return dispatch_tile<MODE, 0>(p, s);
-    if (mask == 1) return dispatch_tile<MODE, 1>(p, s);
-    if (mask == 2) return dispatch_tile<MODE, 2>(p, s);
-    if constexpr (MODE == EW_A_DENSE) {
-        if (mask == 3) return dispatch_tile<MODE, 3>(p, s);
-        if (mask == 6 || mask == 4) return dispatch_tile<MODE, 6>(p, s);
-    }
-    return dispatch_tile<MODE, 7>(p, s);
+    ew_set_error("ew_gemm_f16: generation 2 has no kernel <%d, %d>", MODE, epi);
+    return EW_ERR_UNSUPPORTED;
 }
 
 }  // namespace
 
-
 ew_status ew_gemm2_dispatch(const GemmP& p, hipStream_t s) {
-    if (p.mode == EW_A_CONV3X3) return dispatch_epi<EW_A_CONV3X3>(p, s);
-    if (p.mode == EW_A_CONVT3) return dispatch_epi<EW_A_CONVT3>(p, s);
-    return dispatch_epi<EW_A_DENSE>(p, s);
+    int epi = 0;
+    if (ew_status st = ew_gemm_select_epi(p, 2, &epi)) return st;
+    if (p.mode == EW_A_CONV3X3) return dispatch_epi<EW_A_CONV3X3>(p, epi, s);
+    if (p.mode == EW_A_CONVT3) return dispatch_epi<EW_A_CONVT3>(p, epi, s);
+    return dispatch_epi<EW_A_DENSE>(p, epi, s);
 }

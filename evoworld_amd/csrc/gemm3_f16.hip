@@ -17,9 +17,6 @@
 // Requires N % 320 == 0 (the dispatcher falls back to generation 2 otherwise).
 #include "gemm_common.h"
 #include <type_traits>
-#include <mutex>
-
-extern char g_gemm_last_kernel[64];
 
 namespace {
 
@@ -61,7 +58,7 @@ constexpr int BAR_STEP = NSTEP - 1 - PD;                               // barrie
 // whole weight matrix at N = 10240) through L2 -- measured FETCH_SIZE 3.0 GB against 0.10 GB algorithmic for the level-2
 // GEGLU GEMM.  Bands of BAND tile columns make a chunk (32 / BAND) M-tiles x BAND N-tiles.
 // Each A row-tile is then fetched once per band instead of once, so banding is only switched on when the weight matrix does
-// not fit in L2 anyway (launch3: W > 3 MB; at level 0, W = 1.6 MB, bands measured -7 %, at level 2, 26 MB, +6 %).
+// not fit in L2 anyway (plan3: W > 3 MB; at level 0, W = 1.6 MB, bands measured -7 %, at level 2, 26 MB, +6 %).
 __device__ __forceinline__ void tile_coords(int id, int tiles_m, int tiles_n, int band, int& tm, int& tn) {
     if (band <= 0 || tiles_n <= band) { tm = id / tiles_n; tn = id - tm * tiles_n; return; }
     const int nb = (tiles_n + band - 1) / band;
@@ -943,233 +940,130 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm3_kernel(const GemmP p, const 
     }
 }
 
-// ---- stream-K workspace: one per (device, stream) -- launches on one stream are ordered, so consecutive GEMMs may share it ----
-struct SkDesc { unsigned epoch; int mode, epi, M, N, K; };                   // what a stream-K launch was (named when its hand-over times out)
-constexpr int SK_DESC_RING = 1024;
-struct SkWorkspace { int dev; hipStream_t stream; float* ws; unsigned* flags; unsigned epoch; SkDesc* ring; };
-constexpr int SK_SLOTS = 256;
-constexpr size_t SK_SLOT_FLOATS = (size_t)FM * FN * 4 * 64 * NW;          // 160 accumulators x 512 threads = 320 KB
-constexpr int SK_POOL = 64;                                                  // (device, stream) pairs of the whole process
-static SkWorkspace sk_pool[SK_POOL];
-static int sk_pool_used = 0;
-SkWorkspace* sk_pool_entry(int i) { return i < sk_pool_used ? &sk_pool[i] : nullptr; }
-static std::mutex sk_mutex;                                                   // the pool is shared by every host thread
-// create = false: only look the (device, stream) entry up (used while the stream is being captured into a hipGraph: allocation
-// and the flag memset must not happen there -- call ew_gemm_streamk_init(stream) before the capture to get the tail inside it)
-SkWorkspace* sk_workspace(hipStream_t stream, bool create) {
-    std::lock_guard<std::mutex> lock(sk_mutex);
-    SkWorkspace* const pool = sk_pool;
-    int& used = sk_pool_used;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    for (int i = 0; i < used; ++i)
-        if (pool[i].dev == dev && pool[i].stream == stream) return &pool[i];
-    if (!create || used == SK_POOL) return nullptr;                         // pool full: those launches run the whole-tile schedule
-    SkWorkspace w{dev, stream, nullptr, nullptr, 0, nullptr};
-    // uncached (MTYPE UC) device memory: partials and flags cross XCDs inside one kernel, and the per-XCD L2s are only coherent
-    // at kernel boundaries for ordinary allocations
-    if (hipExtMallocWithFlags((void**)&w.ws, SK_SLOTS * SK_SLOT_FLOATS * sizeof(float), hipDeviceMallocUncached) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    if (hipExtMallocWithFlags((void**)&w.flags, 2048 * sizeof(unsigned), hipDeviceMallocUncached) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(w.ws); return nullptr; }
-    if (hipMemsetAsync(w.flags, 0, 2048 * sizeof(unsigned), stream) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(w.flags); (void)hipFree(w.ws); return nullptr; }
-    w.ring = new SkDesc[SK_DESC_RING]();
-    pool[used] = w;
-    return &pool[used++];
-}
-unsigned sk_next_epoch(SkWorkspace* w, int mode, int epi, const GemmP& p) {
-    std::lock_guard<std::mutex> lock(sk_mutex);
-    const unsigned e = ++w->epoch;
-    w->ring[e % SK_DESC_RING] = SkDesc{e, mode, epi, p.M, p.N, p.K};
-    return e;
-}
+// ---- host side: one decision per call (plan3), consumed by the launch ----
+constexpr int SK_INST = BN == 320 ? 0 : 1;                               // this tile instance's stream-K workspace pool (gemm_dispatch.cpp)
+struct Plan3 {
+    int epi, grid;
+    GemmP q;                  // tiles_m / tiles_n / band filled in
+    SkP sk;                   // tiles, dp_rounds: tail split, half split or neither (tiles = 0)
+    SkWorkspace* w;           // non-null with a split: ws / flags / epoch are taken from it at the launch
+};
 
-}  // namespace
-// 0 = every stream-K hand-over so far completed; 1 = a finisher gave up waiting (results of that launch are wrong).  Synchronises.
-#if EW3_BN == 320
-int ew_gemm3_sk_status_b256();
-int ew_gemm3_sk_init_b256(hipStream_t s);
-// Allocates the stream-K workspace of (current device, stream) for both tile instances.  Optional for eager use (the first
-// launch that wants the tail allocates it); REQUIRED before capturing launches into a hipGraph, where allocation is illegal --
-// a captured launch without a workspace simply runs the whole-tile schedule.
-extern "C" ew_status ew_gemm_streamk_init(void* stream) {
-    const bool a = sk_workspace((hipStream_t)stream, true) != nullptr;
-    const bool b = ew_gemm3_sk_init_b256((hipStream_t)stream) != 0;
-    if (!a || !b) { ew_set_error("ew_gemm_streamk_init: no stream-K workspace for this (device, stream): allocation failed or all 64 process-wide pool entries are in use; launches on it run the whole-tile schedule"); return EW_ERR_HIP; }
-    return EW_OK;
-}
-extern "C" int ew_gemm_streamk_status(void) {
-    const int other = ew_gemm3_sk_status_b256();
-    if (other < 0) return other;
-    int bad = other;
-#else
-int ew_gemm3_sk_init_b256(hipStream_t s) { return sk_workspace(s, true) != nullptr; }
-int ew_gemm3_sk_status_b256() {
-    int bad = 0;
-#endif
-    std::lock_guard<std::mutex> lock(sk_mutex);      // the descriptor ring is written under the same mutex by launching threads
-    for (int i = 0; i < SK_POOL; ++i) {
-        SkWorkspace* w = sk_pool_entry(i);
-        if (!w) break;
-        unsigned word[2] = {0, 0};
-        if (hipMemcpy(word, w->flags + 1024, sizeof(word), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return -1; }
-        if (word[0]) {
-            bad = 1;
-            const SkDesc d = w->ring[word[1] % SK_DESC_RING];
-            char msg[256];
-            if (d.epoch == word[1])
-                snprintf(msg, sizeof(msg), "stream-K hand-over timed out: " EW3_KERNEL_STR "<%d, %d> M=%d N=%d K=%d (stream-K launch #%u on device %d, stream %p): the output of that launch is invalid",
-                         d.mode, d.epi, d.M, d.N, d.K, word[1], w->dev, (void*)w->stream);
-            else
-                snprintf(msg, sizeof(msg), "stream-K hand-over timed out in stream-K launch #%u on device %d, stream %p (more than %d stream-K launches ago: description no longer kept)",
-                         word[1], w->dev, (void*)w->stream, SK_DESC_RING);
-            ew_set_error("%s", msg);
-        }
-    }
-    return bad;
-}
-namespace {
-
-// half split of small problems: see launch3.  Smallest K it is used for:
-inline int sk_half_min_k() {
-    // A/B per shape at M = 7200, N = 1280 (profiles/r04_d_half_split.txt): K = 11520 conv 235 -> 222 us, K = 23040 conv 443 -> 396 us;
-    // K = 5120 dense 104 -> 115 us, K = 2560 67 -> 74, temporal K = 3840 90 -> 97 (the hand-over, 2 x 320 KB per block pair, costs more
-    // than the idle CUs there): on from K = 8192
-    return 8192;
-}
-inline bool sk_half_shape(const GemmP& p, long long tiles) {
-    const int mk = sk_half_min_k();
-    return !(p.dbg & 4) && tiles >= 8 && 2 * tiles <= ew_cu_budget() && (2 * tiles) % 8 == 0 && (p.K / BK) % 2 == 0 && p.K >= mk;
-}
-template <int MODE, int EPI>
-inline bool sk_half_applies(const GemmP& p, long long tiles) {
-    return !(MODE == EW_A_DENSE && EPI == 23) && sk_half_shape(p, tiles);
-}
-
-template <int MODE, int EPI>
-ew_status launch3(const GemmP& p, hipStream_t s) {
-    GemmP q = p;
-    q.tiles_m = ew_cdiv(p.M, BM);
-    q.tiles_n = p.N / BN;
-    q.band = ((long long)p.N * p.K * 2 > 3LL * 1024 * 1024) ? 4 : 0;
-    const size_t lds = 2 * STAGE + ITEMS_BYTES;
-    static std::atomic<unsigned long long> attr_mask{0};                   // per (kernel instantiation, device)
-    if (ew_status st = ew_ensure_dynamic_lds((const void*)gemm3_kernel<MODE, EPI>, (int)lds, attr_mask)) return st;
-    const long long tiles = (long long)q.tiles_m * q.tiles_n;
-    const int NCU = ew_cu_budget();                   // 256 unless the caller runs on a CU-masked stream (ew_set_cu_budget)
-    int grid = NCU;                                   // persistent: one 8-wave workgroup per CU
-    if (tiles < grid) grid = (int)((tiles + 7) / 8 * 8);
-    // Stream-K tail: T tiles over 256 blocks cost ceil(T/256) rounds; every C-wide output of the U-Net is 1800 / 900 / 452 tiles =
-    // 7.03 / 3.52 / 1.77 rounds paid as 8 / 4 / 2.  When the loss is worth it, the last (T mod 256) + 256 tiles are cut along K
-    // into 256 equal ranges instead (gemm3_kernel: contributor / finisher hand-over through the uncached workspace).
-    SkP sk{nullptr, nullptr, 0u, 0, 0};
-    constexpr int sk_min_k = 1280;                  // (ew_set_gemm_debug(4) forces the whole-tile schedule: the twin of the stream-K parity test)
-    // Where it pays (A/B per shape on the U-Net's problems, same box): 3x3 convs at every level (-6 ... -10 %), dense / temporal
-    // GEMMs with at most two tile columns and K >= 1280 (-4 ... -8 %).  With four tile columns (level 2) the blocks of an XCD
-    // are out of phase along K and stop sharing the A rows and W slices in L2: +7 ... +16 % -- left on the whole-tile schedule.
-    const bool sk_shape = MODE == EW_A_CONV3X3 || (q.tiles_n <= 2 && p.K >= sk_min_k);
-    if (sk_shape && !(MODE == EW_A_DENSE && EPI == 23) && !(p.dbg & 4) && grid == NCU && tiles > NCU && tiles % NCU != 0) {
-        const long long rounds = (tiles + NCU - 1) / NCU;
-        const double loss = 1.0 - (double)tiles / ((double)NCU * rounds);
-        if (loss > 0.04) {
-            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(s, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
-            SkWorkspace* w = sk_workspace(s, cap == hipStreamCaptureStatusNone);
-            if (w) {
-                sk.dp_rounds = (int)(tiles / NCU) - 1;
-                sk.tiles = (int)(tiles - (long long)NCU * sk.dp_rounds);
-                sk.ws = w->ws; sk.flags = w->flags; sk.epoch = sk_next_epoch(w, MODE, EPI, p);
-            }
-        }
-    }
-    // Half split (round 4): problems with at most 128 tiles (the deepest level: M = 7200 -> 29 x 4 = 116 tiles) leave more than
-    // half of the 256 CUs idle on the whole-tile schedule and used to run on generation 2's 256x160 tiles.  With a long K every
-    // tile is cut into two K halves instead: 2 x tiles blocks, block 2t computes the head of tile t and finishes it with the
-    // partial of block 2t+1 (same contributor / finisher hand-over as the tail split: one range = exactly half a tile).
-    if (sk_half_applies<MODE, EPI>(p, tiles) && !sk.tiles) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
-        SkWorkspace* w = sk_workspace(s, cap == hipStreamCaptureStatusNone);
-        if (w) {
-            grid = (int)(2 * tiles);
-            sk.dp_rounds = 0;
-            sk.tiles = (int)tiles;
-            sk.ws = w->ws; sk.flags = w->flags; sk.epoch = sk_next_epoch(w, MODE, EPI, p);
-        }
-    }
-    snprintf(g_gemm_last_kernel, 64, EW3_KERNEL_STR "<%d, %d>", MODE, EPI);
-    hipLaunchKernelGGL((gemm3_kernel<MODE, EPI>), dim3(grid), dim3(64 * NW), lds, s, q, sk);
-    return ew_check_launch("ew_gemm_f16(gen3)");
-}
-
-// operand sets that occur in the U-Net (evoworld_amd/unet.py); any other mask runs on the smallest compiled superset
-template <int MODE>
-ew_status dispatch_epi3(const GemmP& p, hipStream_t s) {
-    if (p.act == EW_ACT_GEGLU) {
-        if constexpr (MODE == EW_A_DENSE) return launch3<MODE, 8>(p, s);
-        else { ew_set_error("ew_gemm_f16: GEGLU epilogue is only built for dense mode"); return EW_ERR_UNSUPPORTED; }
-    }
-    const int mask = (p.rowbias ? 1 : 0) | (p.r1 ? 2 : 0) | (p.r2 ? 4 : 0);
-    if (p.r1_lo || p.r2_lo || p.out_lo) {           // split-fp16 residual stream: general path with the lo companions
-        // no residual operand (round 5): the row-bias enters through the accumulators' initial value, the epilogue only converts and stores
-        if ((mask & 6) == 0) return launch3<MODE, 16 | 1>(p, s);
-        if constexpr (MODE == EW_A_DENSE) {
-            if ((mask & 4) == 0) return launch3<MODE, 16 | 3>(p, s);
-            return launch3<MODE, 16 | 7>(p, s);
-        } else {
-            if ((mask & 5) == 0) return launch3<MODE, 16 | 2>(p, s);
-            // row-bias + split output (round 3: the conv1 / temporal conv1 outputs of the resblocks, GroupNorm inputs whose fp16
-            // rounding was the largest remaining storage term of the parity budget); r1 may be null (zero page)
-            if ((mask & 4) == 0) return launch3<MODE, 16 | 3>(p, s);
-            ew_set_error("ew_gemm_f16: conv modes carry the split residual with row-bias / r1 only (no r2)");
-            return EW_ERR_UNSUPPORTED;
-        }
-    }
-    if (mask == 0) return launch3<MODE, 0>(p, s);
-    if (mask == 1) return launch3<MODE, 1>(p, s);
-    if (mask == 2) return launch3<MODE, 2>(p, s);
-    if constexpr (MODE == EW_A_DENSE) {
-        if (mask == 3) return launch3<MODE, 3>(p, s);
-        if (mask == 6 || mask == 4) return launch3<MODE, 6>(p, s);
-    }
-    return launch3<MODE, 7>(p, s);
-}
-
-}  // namespace
-
-// true when generation 3 can run the problem AND is expected to be the faster choice (enough 256x320 tiles to fill the chip)
-bool EW3_NAME(ew_gemm3_wants)(const GemmP& p, hipStream_t s) {
+// *taken: generation 3 can run the problem AND is expected to be the faster choice (enough tiles to fill the chip, or the half split);
+// otherwise the problem goes to generation 2
+ew_status plan3(const GemmP& p, hipStream_t s, Plan3& pl, bool* taken) {
+    *taken = false;
     // smallest M: the swapped-operand V^T projections (M = C = 320 / 640 / 1280 rows of W_v against N = all tokens) measured
     // 337 -> 253 us (level 0) and 192 -> 156 us (level 1) here against generation 2's 256x160 tiles (640-byte instead of 320-byte output
     // row pieces; profiles/r04_f_sweeps.txt; round 3's threshold was 1024)
-    if (p.N % BN != 0 || p.M < 320) return false;
-    if (BN != 320 && p.N % 320 == 0) return false;                      // the 320-wide instance takes what it can
-    if ((long long)ew_cdiv(p.M, BM) * (p.N / BN) > (long long)ew_cu_budget() * (ITEMS_BYTES / 16 - 4)) return false;     // work-item table of a persistent block
+    if (p.N % BN != 0 || p.M < 320) return EW_OK;
+    if (BN != 320 && p.N % 320 == 0) return EW_OK;                      // the 320-wide instance takes what it can
+    const int NCU = ew_cu_budget();                   // 256 unless the caller runs on a CU-masked stream (ew_set_cu_budget)
+    const long long tiles = (long long)ew_cdiv(p.M, BM) * (p.N / BN);
+    if (tiles > (long long)NCU * (ITEMS_BYTES / 16 - 4)) return EW_OK;     // work-item table of a persistent block
     // GELU (CLIP's fc1) is only compiled into the plain dense variant: the erf code in every epilogue cost the conv variants
     // 11-28 spilled VGPRs (reloads inside the K loop, 4-10 % slower); anything else with GELU runs on generation 2
-    if (p.act == EW_ACT_GELU && (p.mode != EW_A_DENSE || p.rowbias || p.r1 || p.r2 || p.out_lo)) return false;
-    if (p.act == EW_ACT_SILU && (p.mode != EW_A_DENSE || p.r1 || p.r2 || p.r1_lo || p.r2_lo || p.out_lo)) return false;      // same for SiLU (round 4)
+    if (p.act == EW_ACT_GELU && (p.mode != EW_A_DENSE || p.rowbias || p.r1 || p.r2 || p.out_lo)) return EW_OK;
+    if (p.act == EW_ACT_SILU && (p.mode != EW_A_DENSE || p.r1 || p.r2 || p.r1_lo || p.r2_lo || p.out_lo)) return EW_OK;      // same for SiLU (round 4)
     // the epilogue addresses its row operands as uniform base + 32-bit byte offset
     const long long ld_max = max((long long)p.ld_out, max((long long)p.ld_r1, (long long)p.ld_r2));
-    if ((long long)p.M * ld_max * 2 >= (1LL << 32)) return false;
-    if (p.rowbias && ((long long)p.M / max(1, p.rows_per_group) + 2) * p.ld_rowbias * 2 >= (1LL << 32)) return false;
+    if ((long long)p.M * ld_max * 2 >= (1LL << 32)) return EW_OK;
+    if (p.rowbias && ((long long)p.M / max(1, p.rows_per_group) + 2) * p.ld_rowbias * 2 >= (1LL << 32)) return EW_OK;
     // one tile column and a short K: 1800 tiles = 7.03 rounds over 256 CUs cost 8, and the residual-carrying epilogue is
     // store-bound anyway -- generation 2's 256x160 tiles (14.06 -> 15 rounds) measured 5-10 % faster there
     // (re-measured on the round-5 kernels: 182.90 vs 182.99 ms per forward either way, profiles/r05_g_short_rule_ab_forward.txt)
-    if (p.mode == EW_A_DENSE && p.N == BN && p.K <= 1280 && (p.r1 || p.r2)) return false;
-    const long long tiles = (long long)ew_cdiv(p.M, BM) * (p.N / BN);
-    if (tiles * 256 >= 200LL * ew_cu_budget()) return true;      // (200 of 256 CUs busy, scaled to the CU budget)
-    // fewer tiles than CUs: generation 3 only with the half split (launch3), i.e. not for the one variant compiled without it
-    const bool epi23 = p.mode == EW_A_DENSE && p.r2 && (p.r1_lo || p.r2_lo || p.out_lo);        // dispatch_epi3: <0, 16|7>
-    if (epi23 || p.act == EW_ACT_GEGLU || !sk_half_shape(p, tiles)) return false;
-    // ... and only when launch3 can really set the split up: a (device, stream) workspace exists or may be created now (not while the
-    // stream is being captured without a prior ew_gemm_streamk_init, not with the pool full / out of memory) -- otherwise the problem would
-    // run whole tiles on fewer than half of the CUs, and generation 2 is the faster choice
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
-    return sk_workspace(s, cap == hipStreamCaptureStatusNone) != nullptr;
+    if (p.mode == EW_A_DENSE && p.N == BN && p.K <= 1280 && (p.r1 || p.r2)) return EW_OK;
+    if (ew_status st = ew_gemm_select_epi(p, 3, &pl.epi)) return st;
+    // no split for <0, 16|7> (compiled without it: SK_OK in the kernel) and under ew_set_gemm_debug(4), which forces the whole-tile
+    // schedule: the twin of the stream-K parity test
+    const bool sk_ok = !(p.mode == EW_A_DENSE && pl.epi == 23) && !(p.dbg & 4);
+    pl.q = p;
+    pl.q.tiles_m = ew_cdiv(p.M, BM); pl.q.tiles_n = p.N / BN;
+    pl.q.band = ((long long)p.N * p.K * 2 > 3LL * 1024 * 1024) ? 4 : 0;
+    pl.sk = SkP{nullptr, nullptr, 0u, 0, 0}; pl.w = nullptr;
+    if (tiles * 256 >= 200LL * NCU) {                 // (200 of 256 CUs busy, scaled to the CU budget)
+        pl.grid = NCU;                                // persistent: one 8-wave workgroup per CU
+        if (tiles < pl.grid) pl.grid = (int)((tiles + 7) / 8 * 8);
+        // Stream-K tail: T tiles over 256 blocks cost ceil(T/256) rounds; every C-wide output of the U-Net is 1800 / 900 / 452 tiles =
+        // 7.03 / 3.52 / 1.77 rounds paid as 8 / 4 / 2.  When the loss is worth it, the last (T mod 256) + 256 tiles are cut along K
+        // into 256 equal ranges instead (gemm3_kernel: contributor / finisher hand-over through the uncached workspace).
+        constexpr int sk_min_k = 1280;
+        // Where it pays (A/B per shape on the U-Net's problems, same box): 3x3 convs at every level (-6 ... -10 %), dense / temporal
+        // GEMMs with at most two tile columns and K >= 1280 (-4 ... -8 %).  With four tile columns (level 2) the blocks of an XCD
+        // are out of phase along K and stop sharing the A rows and W slices in L2: +7 ... +16 % -- left on the whole-tile schedule.
+        const bool sk_shape = p.mode == EW_A_CONV3X3 || (pl.q.tiles_n <= 2 && p.K >= sk_min_k);
+        if (sk_shape && sk_ok && tiles > NCU && tiles % NCU != 0) {
+            const long long rounds = (tiles + NCU - 1) / NCU;
+            const double loss = 1.0 - (double)tiles / ((double)NCU * rounds);
+            if (loss > 0.04 && (pl.w = ew_sk_workspace(SK_INST, s))) {       // no workspace: whole tiles
+                pl.sk.dp_rounds = (int)(tiles / NCU) - 1;
+                pl.sk.tiles = (int)(tiles - (long long)NCU * pl.sk.dp_rounds);
+            }
+        }
+    } else {
+        // Half split (round 4): problems with at most 128 tiles (the deepest level: M = 7200 -> 29 x 4 = 116 tiles) leave more than
+        // half of the 256 CUs idle on the whole-tile schedule and used to run on generation 2's 256x160 tiles.  With a long K every
+        // tile is cut into two K halves instead: 2 x tiles blocks, block 2t computes the head of tile t and finishes it with the
+        // partial of block 2t+1 (same contributor / finisher hand-over as the tail split: one range = exactly half a tile).
+        // Smallest K, A/B per shape at M = 7200, N = 1280 (profiles/r04_d_half_split.txt): K = 11520 conv 235 -> 222 us, K = 23040 conv 443 -> 396 us;
+        // K = 5120 dense 104 -> 115 us, K = 2560 67 -> 74, temporal K = 3840 90 -> 97 (the hand-over, 2 x 320 KB per block pair, costs more
+        // than the idle CUs there): on from K = 8192
+        constexpr int sk_half_min_k = 8192;
+        const bool half_shape = tiles >= 8 && 2 * tiles <= NCU && (2 * tiles) % 8 == 0 && (p.K / BK) % 2 == 0 && p.K >= sk_half_min_k;
+        if (!sk_ok || p.act == EW_ACT_GEGLU || !half_shape) return EW_OK;
+        // ... and only when the split can really be set up: a (device, stream) workspace exists or may be created now (not while the
+        // stream is being captured without a prior ew_gemm_streamk_init, not with the pool full / out of memory) -- otherwise the problem would
+        // run whole tiles on fewer than half of the CUs, and generation 2 is the faster choice
+        if (!(pl.w = ew_sk_workspace(SK_INST, s))) return EW_OK;
+        pl.grid = (int)(2 * tiles);
+        pl.sk.tiles = (int)tiles;
+    }
+    *taken = true;
+    return EW_OK;
 }
 
-ew_status EW3_NAME(ew_gemm3_dispatch)(const GemmP& p, hipStream_t s) {
-    if (p.mode == EW_A_CONV3X3) return dispatch_epi3<EW_A_CONV3X3>(p, s);
-    if (p.mode == EW_A_CONVT3) return dispatch_epi3<EW_A_CONVT3>(p, s);
-    return dispatch_epi3<EW_A_DENSE>(p, s);
+template <int MODE, int EPI>
+ew_status launch3(const Plan3& pl, hipStream_t s) {
+    const size_t lds = 2 * STAGE + ITEMS_BYTES;
+    static std::atomic<unsigned long long> attr_mask{0};                   // per (kernel instantiation, device)
+    if (ew_status st = ew_ensure_dynamic_lds((const void*)gemm3_kernel<MODE, EPI>, (int)lds, attr_mask)) return st;
+    SkP sk = pl.sk;
+    if (pl.w) ew_sk_begin(SK_INST, pl.w, MODE, EPI, pl.q, &sk);
+    ew_gemm_note_kernel(EW3_KERNEL_STR "<%d, %d>", MODE, EPI);
+    hipLaunchKernelGGL((gemm3_kernel<MODE, EPI>), dim3(pl.grid), dim3(64 * NW), lds, s, pl.q, sk);
+    return ew_check_launch("ew_gemm_f16(gen3)");
+}
+
+// run-time EPI (ew_gemm_select_epi) -> the variants compiled for MODE
+template <int MODE>
+ew_status dispatch_epi3(const Plan3& pl, hipStream_t s) {
+    constexpr bool D = MODE == EW_A_DENSE;
+    switch (pl.epi) {        // (keep the order: hipcc emits the kernels in it)
+    case 8: if constexpr (D) return launch3<MODE, 8>(pl, s); break;
+    case 16 | 1: return launch3<MODE, 16 | 1>(pl, s);
+    case 16 | 2: if constexpr (!D) return launch3<MODE, 16 | 2>(pl, s); break;
+    case 16 | 3: return launch3<MODE, 16 | 3>(pl, s);
+    case 16 | 7: if constexpr (D) return launch3<MODE, 16 | 7>(pl, s); break;
+    case 0: return launch3<MODE, 0>(pl, s);
+    case 1: return launch3<MODE, 1>(pl, s);
+    case 2: return launch3<MODE, 2>(pl, s);
+    case 3: if constexpr (D) return launch3<MODE, 3>(pl, s); break;
+    case 6: if constexpr (D) return launch3<MODE, 6>(pl, s); break;
+    case 7: return launch3<MODE, 7>(pl, s);
+    }
+    ew_set_error("ew_gemm_f16: generation 3 has no kernel <%d, %d>", MODE, pl.epi);
+    return EW_ERR_UNSUPPORTED;
+}
+
+}  // namespace
+
+const SkInstance EW3_NAME(ew_gemm3_sk) = {EW3_KERNEL_STR, (size_t)FM * FN * 4 * 64 * NW};   // slot: 160 accumulators x 512 threads = 320 KB (256-wide: 256 KB)
+
+ew_status EW3_NAME(ew_gemm3_try)(const GemmP& p, hipStream_t s, bool* taken) {
+    Plan3 pl;
+    const ew_status st = plan3(p, s, pl, taken);
+    if (st || !*taken) return st;
+    if (p.mode == EW_A_CONV3X3) return dispatch_epi3<EW_A_CONV3X3>(pl, s);
+    if (p.mode == EW_A_CONVT3) return dispatch_epi3<EW_A_CONVT3>(pl, s);
+    return dispatch_epi3<EW_A_DENSE>(pl, s);
 }

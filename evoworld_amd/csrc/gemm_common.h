@@ -1,4 +1,4 @@
-// gemm_common.h -- parameter block shared by the GEMM kernel generations.
+// gemm_common.h -- parameter block shared by the GEMM kernel generations, and what the host front end and the kernel families call of each other.
 #pragma once
 #include "common.h"
 
@@ -37,6 +37,27 @@ struct SkP {
     unsigned epoch;
     int tiles, dp_rounds;
 };
+
+// ---- host front end (gemm_dispatch.cpp): ew_gemm_f16 validates, fills GemmP and asks the kernel families in routing order ----
+// try: the family decides once per call whether it takes the problem (*taken) and, if so, launches it
+ew_status ew_conv_small_n_try(const GemmP& p, hipStream_t s, bool* taken);   // conv_small_n.hip: 3x3 convs with N <= 16 (conv_out)
+ew_status ew_gemm3_try(const GemmP& p, hipStream_t s, bool* taken);          // gemm3_f16.hip, 256x320 tile
+ew_status ew_gemm3_try_b256(const GemmP& p, hipStream_t s, bool* taken);     // gemm3_f16.hip compiled with EW3_BN=256
+ew_status ew_gemm2_dispatch(const GemmP& p, hipStream_t s);                  // gemm2_f16.hip: takes everything
+ew_status ew_gemm1_dispatch(const GemmP& p, hipStream_t s);                  // gemm_f16.hip: takes everything (the suite's cross-check)
+// epilogue variant of generations 2 and 3 (EPI bit0 row-bias, bit1 r1, bit2 r2, bit3 GEGLU, bit4 lo8 operands); EW_ERR_UNSUPPORTED
+// with the message set for operand sets no kernel is compiled for
+ew_status ew_gemm_select_epi(const GemmP& p, int generation, int* epi);
+void ew_gemm_note_kernel(const char* fmt, ...);     // records the rocprof-style name of the kernel about to be launched (ew_gemm_last_kernel)
+// Stream-K workspace pool of generation 3: one workspace per (tile instance, device, stream) -- launches on one stream are ordered,
+// so consecutive GEMMs may share it.  inst: 0 = 256x320, 1 = 256x256; each instance reports its kernel name and slot size.
+struct SkInstance { const char* kernel; size_t slot_floats; };
+extern const SkInstance ew_gemm3_sk, ew_gemm3_sk_b256;
+struct SkWorkspace;
+// the workspace of (current device, s), created now unless s is being captured into a hipGraph (allocation and the flag memset must
+// not happen there -- call ew_gemm_streamk_init(stream) before the capture to get the split inside it); nullptr if there is none
+SkWorkspace* ew_sk_workspace(int inst, hipStream_t s);
+void ew_sk_begin(int inst, SkWorkspace* w, int mode, int epi, const GemmP& p, SkP* sk);   // fills ws / flags / the next epoch for one launch
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;

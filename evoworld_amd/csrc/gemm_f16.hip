@@ -19,7 +19,6 @@
 //   * XCD-aware tile order: consecutive tile ids (N fastest) land on the same XCD so the A panel is an L2 hit.
 //   * epilogue: accumulators -> wave-private LDS patch -> row-major float4 -> fused ops -> 8-byte fp16 stores.
 #include "gemm_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -264,6 +263,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmP p) {
 
 template <int BM, int BN>
 ew_status launch(const GemmP& p, hipStream_t s) {
+    ew_gemm_note_kernel("gemm_kernel<%d, %d>", BM, BN);
     GemmP q = p;
     q.tiles_m = ew_cdiv(p.M, BM);
     q.tiles_n = ew_cdiv(p.N, BN);
@@ -278,80 +278,7 @@ ew_status launch(const GemmP& p, hipStream_t s) {
 
 }  // namespace
 
-ew_status ew_gemm2_dispatch(const GemmP& p, hipStream_t s);   // gemm2_f16.hip
-ew_status ew_gemm3_dispatch(const GemmP& p, hipStream_t s);   // gemm3_f16.hip
-bool ew_gemm3_wants(const GemmP& p, hipStream_t s);
-ew_status ew_gemm3_dispatch_b256(const GemmP& p, hipStream_t s);   // gemm3_f16.hip compiled with EW3_BN=256
-bool ew_conv_small_n_wants(const GemmP& p);                        // conv_small_n.hip: 3x3 convs with N <= 16 (conv_out)
-ew_status ew_conv_small_n_dispatch(const GemmP& p, hipStream_t s);
-bool ew_gemm3_wants_b256(const GemmP& p, hipStream_t s);
-static int g_gemm_gen = -1;
-char g_gemm_last_kernel[64] = "";          // rocprof-style name of the kernel the last ew_gemm_f16 call launched
-extern "C" const char* ew_gemm_last_kernel(void) { return g_gemm_last_kernel; }
-static int g_gemm_dbg = 0;
-extern "C" void ew_set_gemm_debug(int d) { g_gemm_dbg = d; }
-extern "C" void ew_set_gemm_generation(int gen) { g_gemm_gen = gen; }
-extern "C" int ew_get_gemm_generation(void) {
-    if (g_gemm_gen < 0) g_gemm_gen = 3;
-    return g_gemm_gen;
-}
-
-extern "C" ew_status ew_gemm_f16(const ew_gemm_args* a, void* stream) {
-    EW_REQUIRE(a != nullptr, "ew_gemm_f16: null args");
-    EW_REQUIRE(a->a && a->w && a->out && a->zero_page, "ew_gemm_f16: null a/w/out/zero_page");
-    EW_REQUIRE(a->M > 0 && a->N > 0, "ew_gemm_f16: M,N must be > 0 (M=%d N=%d)", a->M, a->N);
-    EW_REQUIRE(a->c1 > 0 && a->c1 % 64 == 0 && a->c2 >= 0 && a->c2 % 64 == 0,
-               "ew_gemm_f16: c1,c2 must be multiples of 64 (c1=%d c2=%d)", a->c1, a->c2);
-    EW_REQUIRE(a->c2 == 0 || a->a2, "ew_gemm_f16: c2 > 0 needs a2");
-    EW_REQUIRE(a->N % 4 == 0 && a->ld_out % 4 == 0, "ew_gemm_f16: N and ld_out must be multiples of 4");
-    EW_REQUIRE(a->lda % 8 == 0 && (a->c2 == 0 || a->lda2 % 8 == 0), "ew_gemm_f16: lda must be a multiple of 8");
-    EW_REQUIRE(a->rows_per_group >= 1, "ew_gemm_f16: rows_per_group must be >= 1");
-    EW_REQUIRE(!a->r1 || a->ld_r1 % 4 == 0, "ew_gemm_f16: ld_r1 must be a multiple of 4");
-    EW_REQUIRE(!a->r2 || a->ld_r2 % 4 == 0, "ew_gemm_f16: ld_r2 must be a multiple of 4");
-    int taps = 1;
-    if (a->mode == EW_A_CONV3X3) {
-        taps = 9;
-        EW_REQUIRE(a->n_img > 0 && a->h_in > 0 && a->w_in > 0 && a->h_out > 0 && a->w_out > 0 &&
-                       (a->stride == 1 || a->stride == 2) && (a->upsample == 0 || a->upsample == 1),
-                   "ew_gemm_f16: bad conv3x3 geometry");
-        EW_REQUIRE((long long)a->n_img * a->h_out * a->w_out == a->M, "ew_gemm_f16: M != n_img*h_out*w_out");
-        EW_REQUIRE(!(a->upsample && a->stride != 1), "ew_gemm_f16: upsample needs stride 1");
-        EW_REQUIRE((a->conv_shift == 0 || a->conv_shift == 1) && !(a->conv_shift && a->upsample), "ew_gemm_f16: conv_shift must be 0 or 1 (not with upsample)");
-    } else if (a->mode == EW_A_CONVT3) {
-        taps = 3;
-        EW_REQUIRE(a->tB > 0 && a->tT > 0 && a->tP > 0 && (long long)a->tB * a->tT * a->tP == a->M,
-                   "ew_gemm_f16: M != B*T*P");
-    } else {
-        EW_REQUIRE(a->mode == EW_A_DENSE, "ew_gemm_f16: unknown mode %d", a->mode);
-    }
-    EW_REQUIRE(a->act == EW_ACT_NONE || a->act == EW_ACT_SILU || a->act == EW_ACT_GEGLU || a->act == EW_ACT_GELU, "ew_gemm_f16: unknown act %d", a->act);
-    EW_REQUIRE(!a->rowbias || a->ld_rowbias % 4 == 0, "ew_gemm_f16: ld_rowbias must be a multiple of 4");
-    if (a->act == EW_ACT_GEGLU)
-        EW_REQUIRE(a->N % 128 == 0 && !a->rowbias && !a->r1 && !a->r2 && !a->out_lo, "ew_gemm_f16: GEGLU needs N %% 128 == 0 and no residuals");
-    EW_REQUIRE((!a->r1_lo || a->r1) && (!a->r2_lo || a->r2), "ew_gemm_f16: r1_lo / r2_lo need r1 / r2");
-    GemmP p;
-    p.a = (const f16*)a->a; p.a2 = (const f16*)a->a2; p.w = (const f16*)a->w; p.bias = (const f16*)a->bias;
-    p.rowbias = (const f16*)a->rowbias; p.r1 = (const f16*)a->r1; p.r2 = (const f16*)a->r2; p.out = (f16*)a->out;
-    p.zero_page = (const f16*)a->zero_page;
-    p.r1_lo = (const int8_t*)a->r1_lo; p.r2_lo = (const int8_t*)a->r2_lo; p.out_lo = (int8_t*)a->out_lo;
-    p.conv_shift = a->conv_shift;
-    p.M = a->M; p.N = a->N; p.K = taps * (a->c1 + a->c2);
-    p.c1 = a->c1; p.c2 = a->c2; p.lda = a->lda; p.lda2 = a->lda2; p.ld_out = a->ld_out; p.ld_r1 = a->ld_r1; p.ld_r2 = a->ld_r2; p.ld_rowbias = a->ld_rowbias;
-    p.mode = a->mode; p.n_img = a->n_img; p.h_in = a->h_in; p.w_in = a->w_in; p.h_out = a->h_out; p.w_out = a->w_out;
-    p.stride = a->stride; p.upsample = a->upsample; p.tB = a->tB; p.tT = a->tT; p.tP = a->tP;
-    p.rows_per_group = a->rows_per_group; p.act = a->act; p.c_acc = a->c_acc; p.c_r1 = a->c_r1; p.c_r2 = a->c_r2;
-    p.tiles_m = p.tiles_n = 0;
-    p.band = 0;
-    p.dbg = g_gemm_dbg;
-    hipStream_t s = (hipStream_t)stream;
-    // 3x3 convs with a handful of output channels (conv_out: N = 4) have their own kernel (round 6); generation 1 stays the independent cross-check
-    if (ew_get_gemm_generation() >= 2 && ew_conv_small_n_wants(p)) return ew_conv_small_n_dispatch(p, s);
-    // generation 3 (256x320 tile) where it applies and fills the chip, generation 2 otherwise
-    if (ew_get_gemm_generation() >= 3 && ew_gemm3_wants(p, s)) return ew_gemm3_dispatch(p, s);
-    if (ew_get_gemm_generation() >= 3 && ew_gemm3_wants_b256(p, s)) return ew_gemm3_dispatch_b256(p, s);
-    if (ew_get_gemm_generation() >= 2) return ew_gemm2_dispatch(p, s);
-    // generation 1 tile choice: every channel count of the U-Net is a multiple of 160 (320*k); GEGLU and odd sizes use 128
-    if (a->act != EW_ACT_GEGLU && a->N % 160 == 0) { snprintf(g_gemm_last_kernel, 64, "gemm_kernel<128, 160>"); return launch<128, 160>(p, s); }
-    snprintf(g_gemm_last_kernel, 64, "gemm_kernel<128, 128>");
-    return launch<128, 128>(p, s);
+// generation 1 tile choice: every channel count of the U-Net is a multiple of 160 (320*k); GEGLU and odd sizes use 128
+ew_status ew_gemm1_dispatch(const GemmP& p, hipStream_t s) {
+    return p.act != EW_ACT_GEGLU && p.N % 160 == 0 ? launch<128, 160>(p, s) : launch<128, 128>(p, s);
 }

@@ -109,7 +109,7 @@ void ew_set_gemm_debug(int flags);   /* bit 2 (value 4): generation 3 runs the w
  * workspace, one per (device, stream), allocated on first use: 84 MB + 67 MB for the 256-wide instance).  Deterministic: the
  * split depends on the shape only.  A consumed hand-over flag is cleared by its consumer, so a captured launch can be replayed.
  * ew_gemm_streamk_status() synchronises and returns 0 when every hand-over completed, 1 if a finisher ever timed out
- * (results of that launch are invalid), -1 on a HIP error.  EW_G3_SK=0 in the environment switches the split off. */
+ * (results of that launch are invalid), -1 on a HIP error.  ew_set_gemm_debug(4) switches the split off. */
 int ew_gemm_streamk_status(void);
 /* Allocates the stream-K workspace of (current device, stream).  Optional in eager use (the first launch that wants the tail
  * allocates it, under a mutex); call it BEFORE capturing launches into a hipGraph -- allocation is illegal during capture, and a

@@ -282,14 +282,11 @@ __global__ __launch_bounds__(64 * NW, 1) void gemm4_kernel(const GemmP p) {
 
 }  // namespace
 
-extern char g_gemm_last_kernel[64];
-
-bool ew_gemm4_wants(const GemmP& p) {
-    return p.mode == EW_A_DENSE && p.c2 == 0 && p.N % BN == 0 && p.K % BK == 0 && p.K >= 2 * BK && !p.rowbias && !p.r1 && !p.r2 && !p.out_lo &&
+// (entry in the style of the shipped families: declare it in gemm_common.h, see README.md)
+ew_status ew_gemm4_try(const GemmP& p, hipStream_t s, bool* taken) {
+    *taken = p.mode == EW_A_DENSE && p.c2 == 0 && p.N % BN == 0 && p.K % BK == 0 && p.K >= 2 * BK && !p.rowbias && !p.r1 && !p.r2 && !p.out_lo &&
            (p.act == EW_ACT_NONE || p.act == EW_ACT_GEGLU) && p.M >= 2048 && (long long)p.M * p.lda < (1LL << 31);
-}
-
-ew_status ew_gemm4_dispatch(const GemmP& p, hipStream_t s) {
+    if (!*taken) return EW_OK;
     GemmP q = p;
     q.tiles_m = ew_cdiv(p.M, BM);
     q.tiles_n = p.N / BN;
@@ -298,7 +295,7 @@ ew_status ew_gemm4_dispatch(const GemmP& p, hipStream_t s) {
     int grid = ew_cu_budget();
     if (tiles < grid) grid = (int)((tiles + 7) / 8 * 8);
     const int lds = 2 * STAGE;
-    snprintf(g_gemm_last_kernel, 64, "gemm4_kernel<%d>", p.act == EW_ACT_GEGLU ? 2 : 0);
+    ew_gemm_note_kernel("gemm4_kernel<%d>", p.act == EW_ACT_GEGLU ? 2 : 0);
     if (p.act == EW_ACT_GEGLU) {
         static std::atomic<unsigned long long> mask{0};
         if (ew_status st = ew_ensure_dynamic_lds((const void*)gemm4_kernel<2>, lds, mask)) return st;
