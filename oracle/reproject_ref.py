@@ -206,6 +206,89 @@ def equi2pers_ref(equi, rot, Hp, Wp, fov_x_deg):
     return out                                                # float; caller compares to uint8 with +-1 tolerance
 
 
+def equi2pers_ref32(equi, rot, Hp, Wp, fov_x_deg):
+    """float32 restatement of equi2pers_kernel's expression tree (evoworld_amd/csrc/geometry.hip: same operation order, one
+    rounding per operation, no FMA; numpy's float32 tan / arctan2 / arcsin stand in for the device's) -> float32 [F,Hp,Wp,3],
+    the value BEFORE the kernel's truncation to uint8.  Its distance from equi2pers_ref is the value error float32 coordinate
+    arithmetic can cause: the tests derive their 'too close to an integer to call' band from it, never from the kernel."""
+    f32 = np.float32
+    F_, He, We, _ = equi.shape
+    PI = f32(3.14159265358979323846)
+    focal = f32(Wp) / (f32(2.0) * np.tan(f32(fov_x_deg) * PI / f32(360.0), dtype=f32))
+    Wf, Hf = f32(We), f32(He)
+    px, py = np.meshgrid(np.arange(Wp, dtype=f32), np.arange(Hp, dtype=f32))
+    cxr = (px - f32(Wp) * f32(0.5)) / focal
+    cyr = (py - f32(Hp) * f32(0.5)) / focal
+    out = np.zeros((F_, Hp, Wp, 3), dtype=f32)
+    for f in range(F_):
+        R = np.asarray(rot[f], dtype=f32).reshape(9)
+        dx = (R[0] * cxr + R[1] * cyr) + R[2]
+        dy = (R[3] * cxr + R[4] * cyr) + R[5]
+        dz = (R[6] * cxr + R[7] * cyr) + R[8]
+        nrm = np.sqrt((dx * dx + dy * dy) + dz * dz)
+        lon = np.arctan2(dx, dz)
+        lat = np.arcsin(dy / nrm)
+        ui = ((lon * Wf) / (f32(2.0) * PI) + Wf * f32(0.5)) + f32(0.5)
+        uj = ((lat * Hf) / PI + Hf * f32(0.5)) + f32(0.5)
+        ui = ui - np.floor(ui / Wf) * Wf
+        uj = np.minimum(np.maximum(uj, f32(0.0)), f32(He - 1))
+        x0f, y0f = np.floor(ui), np.floor(uj)
+        ax, ay = (ui - x0f)[..., None], (uj - y0f)[..., None]
+        x0, y0 = x0f.astype(np.int64), y0f.astype(np.int64)
+        x0 = np.where(x0 >= We, x0 - We, x0)
+        x1 = np.where(x0 + 1 >= We, 0, x0 + 1)
+        y1 = np.where(y0 + 1 >= He, He - 1, y0 + 1)
+        img = equi[f].astype(f32)
+        one = f32(1.0)
+        top = img[y0, x0] * (one - ax) + img[y0, x1] * ax
+        bot = img[y1, x0] * (one - ax) + img[y1, x1] * ax
+        out[f] = top * (one - ay) + bot * ay
+        assert out[f].dtype == f32
+    return out
+
+
+def smooth_pano(He, We):
+    """uint8 [He,We,3] test panorama for the equi2pers tests: PERIODIC IN LONGITUDE (whole waves per row), so that the x wrap
+    is not a discontinuity of the content and the seam columns can be held to the same bound as every other pixel, and of
+    bounded slope.  Channel c is 127.5 + A sin(2 pi k_c x / We + phi_c) s(y) + T(y), rounded.
+    - T(y) is a triangle wave of slope +-1.2 levels per row and range +-65.  A slope above 1 in one direction matters: an
+      8-bit picture whose slope is below 1 everywhere has plateaus (2 x 2 neighbourhoods of equal pixels), on which the
+      bilinear value is EXACTLY an integer, and the truncation of an exact integer computed in float32 cannot be called.
+    - s(y) = sin(pi (y + 0.5) / He) fades the longitude term towards the poles, and the L = He // 125 rows next to each pole
+      (only the 1000-row panorama has any: 8) are one constant colour.  Within d rows of a pole, float32 asin / atan2 are off
+      by ~ 6e-8 (He / pi)^2 / d source pixels (asin's derivative at +-1, atan2 of two near-zero operands), and in an 8-bit
+      picture neighbouring pixels differ by a whole level or not at all, however gentle the slope before rounding; a cap
+      that is flat keeps those few pixels from setting the comparison band for every other one.  From row L on, T has its
+      full slope, so the row clamp stays visible.
+    - A = 0.15 He / pi (at most 60), so that s(y) adds at most 0.15 to the vertical slope and vertically adjacent pixels
+      keep differing; k_c is the largest wave count whose slope stays below g_c = (0.85, 0.6, 0.4) levels per column.
+    |gradient| <= sqrt(0.85^2 + 1.35^2) = 1.6 before rounding, < 1.5 wherever the longitude term is steep in x only;
+    values stay within [2, 253]."""
+    x = np.arange(We, dtype=np.float64)[None, :]
+    y = np.arange(He, dtype=np.float64)
+    j = np.arange(He - 1, dtype=np.float64)
+    L = He // 125
+    P = np.concatenate([[0.0], np.cumsum(1.2 * (np.minimum(j, He - 2 - j) >= L))])
+    T = (65.0 - np.abs((P + 30.0) % 260.0 - 130.0))[:, None]
+    s = (np.sin(np.pi * (y + 0.5) / He) * (np.minimum(y, He - 1 - y) > L if L else 1.0))[:, None]
+    A = min(60.0, 0.15 * He / np.pi)
+    img = np.zeros((He, We, 3), dtype=np.float64)
+    for c, (g, phi) in enumerate(((0.85, 0.3), (0.6, 1.7), (0.4, 4.1))):
+        k = max(1, int(g * We / (2 * np.pi * A)))
+        img[..., c] = 127.5 + A * np.sin(2 * np.pi * k * x / We + phi) * s + T
+    return np.rint(img).astype(np.uint8)
+
+
+def f32_to_u8_ref(x):
+    """The expression ew_f32_chw_to_u8_hwc cites (diffusers VideoProcessor): (x / 2 + 0.5).clamp(0, 1) in torch CPU float32,
+    then numpy float32 (. * 255).round().astype(uint8); numpy's round is half-to-even.  x: float32 array of any shape, no NaN
+    (astype of NaN is undefined).  Returns (uint8 array, float32 scaled values before the round)."""
+    t = (torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) / 2 + 0.5).clamp(0, 1).numpy()
+    scaled = t * np.float32(255.0)
+    assert scaled.dtype == np.float32
+    return scaled.round().astype(np.uint8), scaled
+
+
 def extract_colors_ref(images):
     c = np.transpose(images, (0, 2, 3, 1)) if (images.ndim == 4 and images.shape[1] == 3) else images
     return (c.reshape(-1, 3) * 255).astype(np.uint8)
