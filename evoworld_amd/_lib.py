@@ -12,7 +12,7 @@ from ctypes import c_char_p, c_float, c_int, c_longlong, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EW_LIB_PATH") or os.path.join(_HERE, "libevoworld_hip.so")   # EW_LIB_PATH: another build of the same ABI (A/B tools)
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 # every symbol declared in include/evoworld_hip.h
 SYMBOLS = [
@@ -27,6 +27,7 @@ SYMBOLS = [
     "ew_nchw_f32_to_nhwc_split_f16", "ew_euler_cfg_step_split", "ew_groupnorm_apply_split_f16", "ew_sinusoid_embed_f16",
     "ew_pano_yaw_rotate",
     "ew_video_metrics_workspace_bytes", "ew_video_metrics", "ew_gt_dump_map_u8",
+    "ew_equi2cube_u8",
 ]
 
 
@@ -114,6 +115,7 @@ def load():
         "ew_pano_yaw_rotate": [P, I, P, P, I, I, I, P],
         "ew_video_metrics": [P, P, I, I, I, I, I, I, P, P, P, P],
         "ew_gt_dump_map_u8": [P, P, c_size_t, P],
+        "ew_equi2cube_u8": [P, P, I, I, I, I, P],
         "ew_blur_axis_f32": [P, P, I, P, LL, I, I, I, P],
         "ew_bicubic_resize_f32": [P, P, I, I, I, I, I, I, P, P, P],
         "ew_vit_patchify_f16": [P, P, I, I, I, I, P],

@@ -5,6 +5,8 @@
                                          <- evoworld/inference/navigator_evoworld.py:146-154,173-231,303-318,394-448  (C2)
   Navigator.navigate_path / split_path_into_segments / rotate_panorama
                                          <- evoworld/inference/navigator_evoworld.py:276-301,335-392,466-512  (C2, non-curve mode)
+  Navigator.convert_panorama_to_cubemap / precompute_rotation_matrix / cubemap_to_equirectangular
+                                         <- evoworld/inference/navigator_evoworld.py:514-705,707-743,745-864  (C2, skybox export)
   UnifiedLoopConsistencyPipeline.process_episode / convert_pano_to_pers
                                          <- unified_loop_consistency.py:299-334,398-492               (C3, N-segment loop)
 
@@ -149,6 +151,54 @@ class Navigator:
         integer roll the map is not the identity even at 0 degrees: callers rotate only for a non-zero turn, as the reference."""
         from . import ops
         return ops.pano_yaw_rotate(image[None].contiguous(), torch.as_tensor(rotation_degrees, dtype=torch.float32).reshape(1))[0]
+
+    @staticmethod
+    def _clip_u8(x, what):
+        """(uint8 [V,H,W,3] device tensor, kind) of a PIL image, a device [H,W,3] frame or a [V,H,W,3] clip."""
+        if isinstance(x, torch.Tensor):
+            if x.dtype != torch.uint8 or x.ndim not in (3, 4) or x.shape[-1] != 3:
+                raise TypeError(f"{what}: expected a PIL image or a device uint8 [H,W,3] / [V,H,W,3] tensor, got {x.dtype} {tuple(x.shape)}")
+            return (x[None] if x.ndim == 3 else x), ("frame" if x.ndim == 3 else "clip")
+        arr = np.asarray(x.convert("RGB"))
+        return torch.from_numpy(arr.copy())[None].cuda(), "pil"
+
+    @staticmethod
+    def _like(t, kind):
+        if kind == "clip":
+            return t
+        if kind == "frame":
+            return t[0]
+        from PIL import Image
+        return Image.fromarray(t[0].cpu().numpy())
+
+    @classmethod
+    def convert_panorama_to_cubemap(cls, panorama_image, interpolation=True, scale_factor=2):
+        """Panorama -> (cubemap, faces) as navigator_evoworld.py:514-705, on the device: LANCZOS x scale_factor, the cube cross
+        (ew_equi2cube_u8: bilinear, or nearest with interpolation=False), LANCZOS back to (W0, int(W0*3/4)).  `cubemap` is the
+        downscaled cross; `faces` is a dict in the reference's key order right, left, top, bottom, front, back, cut from the
+        SCALED cross (edge scale_factor*W0/4).  A PIL image gives PIL images; a device uint8 [H,W,3] frame or [V,H,W,3] clip gives
+        device tensors (faces [E,E,3] / [V,E,E,3], views of the scaled cross), a whole clip in one launch per stage.
+        The panorama must be 2:1 (AssertionError otherwise, as the reference): the model's 1024x576 frames are not -- resize them
+        first, e.g. reprojection.resize_u8(frames, 512, 1024) (ops.resize_aa_u8 with Pillow's bilinear tables).
+        Reference behaviour kept: the bilinear blend is truncated, not rounded (a flat area of value A can come out A - 1), and
+        the neighbours are clipped, not wrapped, at the seam; nearest mode leaves the seam pixel whose column rounds to W black."""
+        x, kind = cls._clip_u8(panorama_image, "panorama_image")
+        cubemap, faces = RP.panorama_to_cubemap(x, interpolation, scale_factor)
+        return cls._like(cubemap, kind), {n: cls._like(f, kind) for n, f in faces.items()}
+
+    precompute_rotation_matrix = staticmethod(RP.precompute_rotation_matrix)
+
+    @classmethod
+    def cubemap_to_equirectangular(cls, cubemap_faces, output_width, output_height, scale_factor=2):
+        """Faces dict -> panorama as navigator_evoworld.py:745-864, on the device: the reference's integer gather at scale_factor
+        x the output size (host LUT in float64, ew_cube2equi_gather), then LANCZOS down when scale_factor > 1.  The dict's key
+        order does not matter; a face that is missing renders black.  PIL faces give a PIL image; device uint8 [res,res,3] /
+        [V,res,res,3] faces give a device [H,W,3] / [V,H,W,3] tensor.  The faces of one call must be square and of one size
+        (the reference also takes faces of mixed sizes; ValueError here)."""
+        conv = {n: cls._clip_u8(f, f"cubemap_faces[{n!r}]") for n, f in cubemap_faces.items()}
+        kind = next(iter(conv.values()))[1] if conv else "pil"
+        pano = RP.cubemap_to_panorama({n: t.contiguous() for n, (t, _) in conv.items()}, output_width, output_height, scale_factor)
+        return cls._like(pano, kind)
 
     @classmethod
     def turn_start_image(cls, image, rotation_degrees):

@@ -341,6 +341,43 @@ def cube2equi_gather(faces, lut, H, W):
     return pano
 
 
+def equi2cube(panos, interpolation=True, out=None):
+    """Equirectangular panoramas uint8 [V,H,W,3] (W == 2H, W % 4 == 0) -> the reference's cube cross uint8 [V,3W/4,W,3]
+    (Navigator.convert_panorama_to_cubemap's transform, navigator_evoworld.py:537-659): bilinear with truncation, or nearest
+    with interpolation=False.  One launch for all V.  `out`: a contiguous uint8 [V,3W/4,W,3] tensor to write into."""
+    lib = _lib.load()
+    _req(panos, torch.uint8, "panos")
+    if panos.ndim != 4 or panos.shape[3] != 3:
+        raise ValueError(f"panos: expected uint8 [V,H,W,3], got {tuple(panos.shape)}")
+    V, H, W, _ = panos.shape
+    if out is None:
+        out = torch.empty(V, 3 * (W // 4), W, 3, dtype=torch.uint8, device=panos.device)
+    _req(out, torch.uint8, "out")
+    if tuple(out.shape) != (V, 3 * (W // 4), W, 3):
+        raise ValueError(f"out: expected {(V, 3 * (W // 4), W, 3)}, got {tuple(out.shape)}")
+    _lib.check(lib.ew_equi2cube_u8(_ptr(panos), _ptr(out), V, H, W, int(bool(interpolation)), _stream()), "ew_equi2cube_u8")
+    return out
+
+
+def cubemap_faces_to_equi(faces, H, W):
+    """Cube faces -> panoramas uint8 [V,H,W,3] through the integer LUT of Navigator.cubemap_to_equirectangular
+    (reprojection.build_cubemap2equi_lut, cached per (W,H,res)) and ew_cube2equi_gather.  faces: a dict name -> uint8
+    [V,res,res,3] (any key order; a missing face is black, as in the reference, navigator_evoworld.py:806-852) or a stacked
+    uint8 [V,6,res,res,3] in FACE_ORDER."""
+    from .reprojection import FACE_ORDER, build_cubemap2equi_lut
+    if isinstance(faces, dict):
+        unknown = set(faces) - set(FACE_ORDER)
+        if unknown or not faces:
+            raise ValueError(f"faces: expected keys among {FACE_ORDER}, got {sorted(faces)}")
+        first = next(iter(faces.values()))
+        for n, f in faces.items():
+            if f.ndim != 4 or f.shape[1] != f.shape[2] or f.shape[3] != 3 or f.shape != first.shape:
+                raise ValueError(f"faces[{n!r}]: expected square uint8 [V,res,res,3] faces of one size, got {tuple(f.shape)}")
+        faces = torch.stack([faces[n] if n in faces else torch.zeros_like(first) for n in FACE_ORDER], dim=1)
+    lut = build_cubemap2equi_lut(W, H, faces.shape[2]).to(faces.device)
+    return cube2equi_gather(faces.contiguous(), lut, H, W)
+
+
 def select_kth(x, k):
     """x fp32 [n] on the device -> fp32 [2] device tensor (x_(k), x_(k+1)) (0-based, ascending): radix select, no sort."""
     lib = _lib.load()

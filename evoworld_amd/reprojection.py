@@ -359,17 +359,38 @@ def split_curve_into_segments(path):
 _coeff_cache = {}
 
 
-def resample_coeffs(in_size, out_size):
-    """Pillow's precompute_coeffs + normalize_coeffs_8bpc for the BILINEAR filter (support 1.0) over the full box:
-    returns (kk int32 [out, ksize], bounds int32 [out, 2] = (xmin, count)).  This is what
-    torchvision.transforms.Resize((576,1024)) does to the 1000x2000 PIL memory panoramas
-    (dataset/CameraTrajDataset.py:586-619, unified_loop_consistency.py:422); verified bit-exact against PIL itself."""
-    key = (in_size, out_size)
+def _bilinear_filter(x):
+    return max(0.0, 1.0 - abs(x))
+
+
+def _sinc(x):
+    if x == 0.0:
+        return 1.0
+    x = x * math.pi
+    return math.sin(x) / x
+
+
+def _lanczos_filter(x):
+    """Pillow's lanczos_filter: the sinc windowed by sinc(x / 3), truncated to [-3, 3)."""
+    return _sinc(x) * _sinc(x / 3) if -3.0 <= x < 3.0 else 0.0
+
+
+RESAMPLE_FILTERS = {"bilinear": (_bilinear_filter, 1.0), "lanczos": (_lanczos_filter, 3.0)}     # name -> (weight, support)
+
+
+def resample_coeffs(in_size, out_size, filter="bilinear"):
+    """Pillow's precompute_coeffs + normalize_coeffs_8bpc over the full box for the BILINEAR (support 1.0, the default) or
+    LANCZOS (support 3.0) filter: returns (kk int32 [out, ksize], bounds int32 [out, 2] = (xmin, count)), 22 fractional bits.
+    Bilinear is what torchvision.transforms.Resize((576,1024)) does to the 1000x2000 PIL memory panoramas
+    (dataset/CameraTrajDataset.py:586-619, unified_loop_consistency.py:422); LANCZOS is what the cubemap conversions bracket their
+    transform with (evoworld/inference/navigator_evoworld.py:527-530, :701-703, :858-860).  Verified bit-exact against PIL itself."""
+    key = (in_size, out_size) if filter == "bilinear" else (in_size, out_size, filter)
     if key in _coeff_cache:
         return _coeff_cache[key]
+    weight, base_support = RESAMPLE_FILTERS[filter]
     scale = in_size / out_size
     filterscale = max(scale, 1.0)
-    support = 1.0 * filterscale
+    support = base_support * filterscale
     ksize = int(math.ceil(support)) * 2 + 1
     kk = np.zeros((out_size, ksize), dtype=np.int32)
     bounds = np.zeros((out_size, 2), dtype=np.int32)
@@ -378,8 +399,13 @@ def resample_coeffs(in_size, out_size):
         center = (xx + 0.5) * scale
         xmin = max(int(center - support + 0.5), 0)
         xmax = min(int(center + support + 0.5), in_size) - xmin
-        w = np.array([max(0.0, 1.0 - abs((x + xmin - center + 0.5) * ss)) for x in range(xmax)], dtype=np.float64)
-        ww = w.sum()
+        w = np.array([weight((x + xmin - center + 0.5) * ss) for x in range(xmax)], dtype=np.float64)
+        if filter == "bilinear":
+            ww = w.sum()
+        else:                      # Pillow adds the weights one by one; numpy's sum goes pairwise from 8 terms on (LANCZOS has up to 6 * scale + 1)
+            ww = 0.0
+            for x in range(xmax):
+                ww += float(w[x])
         if ww != 0.0:
             w = w / ww
         q = w * (1 << 22)
@@ -388,6 +414,108 @@ def resample_coeffs(in_size, out_size):
     out = (torch.from_numpy(kk), torch.from_numpy(bounds))
     _coeff_cache[key] = out
     return out
+
+
+def resize_u8(frames_u8, height, width, filter="bilinear"):
+    """PIL.Image.resize((width, height), BILINEAR | LANCZOS) of uint8 [V,Hi,Wi,3] frames on the device, bit for bit; the frames
+    themselves when the size does not change (Pillow returns a copy then)."""
+    V, Hi, Wi, _ = frames_u8.shape
+    if (Hi, Wi) == (height, width):
+        return frames_u8.contiguous()
+    dev = frames_u8.device
+    ch = tuple(t.to(dev) for t in resample_coeffs(Wi, width, filter))
+    cv = tuple(t.to(dev) for t in resample_coeffs(Hi, height, filter))
+    return ops.resize_aa_u8(frames_u8.contiguous(), ch, cv, height, width)
+
+
+# ------------------------------------------------------------------ panorama <-> cubemap (navigator_evoworld.py:514-864)
+CUBEMAP_FACE_NAMES = ("right", "left", "top", "bottom", "front", "back")          # key order of the faces dict (:673)
+# (cell column, cell row) of each face in the cross (:674-687)
+CROSS_CELLS = {"right": (3, 1), "left": (1, 1), "top": (2, 0), "bottom": (2, 2), "front": (2, 1), "back": (0, 1)}
+
+
+def precompute_rotation_matrix(rx, ry, rz):
+    """Rz(rz) @ Ry(ry) @ Rx(rx), angles in degrees -> float64 [3,3] (navigator_evoworld.py:707-743)."""
+    rx, ry, rz = np.deg2rad(rx), np.deg2rad(ry), np.deg2rad(rz)
+    Rx = np.array([[1, 0, 0], [0, np.cos(rx), -np.sin(rx)], [0, np.sin(rx), np.cos(rx)]])
+    Ry = np.array([[np.cos(ry), 0, np.sin(ry)], [0, 1, 0], [-np.sin(ry), 0, np.cos(ry)]])
+    Rz = np.array([[np.cos(rz), -np.sin(rz), 0], [np.sin(rz), np.cos(rz), 0], [0, 0, 1]])
+    return Rz @ Ry @ Rx
+
+
+_cubemap_lut_cache = {}
+
+
+def build_cubemap2equi_lut(width, height, res):
+    """int16 [H,W,3] = (face id in FACE_ORDER, v_px, u_px): the integer gather of Navigator.cubemap_to_equirectangular
+    (navigator_evoworld.py:762-852) for a width x height panorama from res x res faces, in float64 numpy in the reference's order:
+    R = Rz(180) Ry(-90) Rx(90); direction from theta = x/W 2 pi - pi, phi = y/H pi - pi/2; argmax of |x|,|y|,|z| (first maximum
+    wins) with strict sign tests per face; (u * res).astype(int), clipped.  The six masks are disjoint, so the order of the
+    caller's dict cannot matter.  A pixel is claimed by no face only if the dominant component is not strictly signed (a zero
+    or NaN direction), which no finite size produces; this is asserted, so the LUT needs no 'black' entry -- a face missing
+    from the caller's dict is handed to the gather as a black face instead."""
+    key = (width, height, res)
+    if key in _cubemap_lut_cache:
+        return _cubemap_lut_cache[key]
+    R = precompute_rotation_matrix(90, -90, 180)
+    x = np.linspace(0, width - 1, width)
+    y = np.linspace(0, height - 1, height)
+    xv, yv = np.meshgrid(x, y)
+    theta = (xv / width) * 2 * np.pi - np.pi
+    phi = (yv / height) * np.pi - (np.pi / 2)
+    xs = np.cos(phi) * np.cos(theta)
+    ys = np.cos(phi) * np.sin(theta)
+    zs = np.sin(phi)
+    xs, ys, zs = R @ np.array([xs.flatten(), ys.flatten(), zs.flatten()])
+    xs, ys, zs = (a.reshape((height, width)) for a in (xs, ys, zs))
+    abs_x, abs_y, abs_z = np.abs(xs), np.abs(ys), np.abs(zs)
+    face_indices = np.argmax(np.stack([abs_x, abs_y, abs_z], axis=-1), axis=-1)
+    rules = {"right": (0, xs > 0, -zs, ys, abs_x), "left": (0, xs < 0, zs, ys, abs_x),
+             "bottom": (1, ys > 0, xs, -zs, abs_y), "top": (1, ys < 0, xs, zs, abs_y),
+             "front": (2, zs > 0, xs, ys, abs_z), "back": (2, zs < 0, -xs, ys, abs_z)}
+    lut = np.zeros((height, width, 3), dtype=np.int16)
+    claimed = np.zeros((height, width), dtype=bool)
+    for fi, name in enumerate(FACE_ORDER):
+        axis, sign, un, vn, den = rules[name]
+        mask = (face_indices == axis) & sign
+        u = (un[mask] / den[mask] + 1) / 2
+        v = (vn[mask] / den[mask] + 1) / 2
+        lut[mask, 0] = fi
+        lut[mask, 1] = np.clip((v * res).astype(int), 0, res - 1)
+        lut[mask, 2] = np.clip((u * res).astype(int), 0, res - 1)
+        claimed |= mask
+    assert claimed.all(), "cubemap -> equirect: a pixel is claimed by no face"
+    out = torch.from_numpy(lut)
+    _cubemap_lut_cache[key] = out
+    return out
+
+
+def cross_faces(cross):
+    """The six faces of a cross uint8 [V,3E,4E,3] as a dict of [V,E,E,3] views in the reference's key order (:672-693)."""
+    E = cross.shape[2] // 4
+    return {n: cross[:, r * E:(r + 1) * E, c * E:(c + 1) * E] for n, (c, r) in ((n, CROSS_CELLS[n]) for n in CUBEMAP_FACE_NAMES)}
+
+
+def panorama_to_cubemap(panos_u8, interpolation=True, scale_factor=2):
+    """convert_panorama_to_cubemap (navigator_evoworld.py:514-705) for a clip: uint8 [V,H0,W0,3] on the device ->
+    (cross uint8 [V, int(W0*3/4), W0, 3], faces dict of [V,E,E,3] views of the SCALED cross, E = scale_factor*W0/4).
+    LANCZOS x scale_factor (ew_resize_aa_u8) -> cross (ew_equi2cube_u8) -> LANCZOS back: one launch per stage for the whole clip."""
+    V, H0, W0, _ = panos_u8.shape
+    W, H = W0 * scale_factor, H0 * scale_factor
+    assert W == 2 * H, "Panorama width must be twice the height."
+    if W % 4:
+        raise ValueError(f"scaled panorama width {W} must be a multiple of 4 (cube edge = width / 4)")
+    cross = ops.equi2cube(resize_u8(panos_u8, H, W, "lanczos"), interpolation)
+    return resize_u8(cross, int(W0 * 3 / 4), W0, "lanczos"), cross_faces(cross)
+
+
+def cubemap_to_panorama(faces, output_width, output_height, scale_factor=2):
+    """cubemap_to_equirectangular (navigator_evoworld.py:745-864) for a clip: faces = dict name -> uint8 [V,res,res,3] (device; any
+    key order, a missing face renders black) -> uint8 [V,output_height,output_width,3]: integer gather at scale_factor x the
+    output size (ew_cube2equi_gather through build_cubemap2equi_lut), then LANCZOS down when scale_factor > 1."""
+    W, H = output_width * scale_factor, output_height * scale_factor
+    pano = ops.cubemap_faces_to_equi(faces, H, W)
+    return resize_u8(pano, output_height, output_width, "lanczos") if scale_factor > 1 else pano
 
 
 def memory_to_pixel_values(panos_u8, height=576, width=1024):

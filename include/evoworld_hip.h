@@ -27,7 +27,7 @@ typedef int ew_status;
 #define EW_ERR_UNSUPPORTED (-2)
 #define EW_ERR_HIP (-3)
 
-#define EW_ABI_VERSION 12
+#define EW_ABI_VERSION 13
 int ew_abi_version(void);
 const char* ew_last_error(void);
 
@@ -382,6 +382,16 @@ ew_status ew_video_metrics(const void* a, const void* b, int layout, int F, int 
  * the resized uint8 frame k -> ToTensor (k / 255) -> x*2 - 1 -> (x*0.5 + 0.5).clamp(0, 1).mul(255).byte(), every step a float32
  * rounding and the last a truncation, i.e. a fixed 256-entry map (63 levels come out one lower).  src, dst uint8 [n]. */
 ew_status ew_gt_dump_map_u8(const uint8_t* src, uint8_t* dst, size_t n, void* stream);
+
+/* Equirectangular panoramas -> the reference's cube cross (ABI 13; Navigator.convert_panorama_to_cubemap,
+ * evoworld/inference/navigator_evoworld.py:514-705, which does this in numpy on the host): pano uint8 [V,H,W,3] with W == 2 H and
+ * W % 4 == 0 -> cross uint8 [V,3E,W,3], E = W / 4.  Middle row of cells: back, left, front, right; top is cell 2 of the first row, bottom
+ * cell 2 of the third, the other six cells are written black (:551-553, :648-659); the six faces are crops of the cross (:672-693).
+ * Source coordinates are evaluated on the device in float64 in the reference's order (pixel_to_xyz :555-593, uf / vf :597-603).
+ * interpolation = 1: floor and +1 neighbours, all four clipped (no wrap at the seam), float64 four-term blend, truncated to uint8 (:605-634);
+ * interpolation = 0: round half to even, pixels whose index falls outside the panorama (uf == W on the seam) stay black (:638-646).
+ * cross 4-byte aligned; one launch for all V panoramas. */
+ew_status ew_equi2cube_u8(const uint8_t* pano, uint8_t* cross, int V, int H, int W, int interpolation, void* stream);
 
 #ifdef __cplusplus
 }
