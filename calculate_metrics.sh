@@ -1,7 +1,10 @@
 #!/bin/bash
 # PSNR / SSIM of a run's per-segment dumps on the MI355X: counterpart of the reference's calculate_metrics.sh (same variables).
 # Compares $VIDEO_PATH/<episode>/predictions_gt_$SEGMENT_ID with predictions_$SEGMENT_ID and writes $VIDEO_PATH/$RESULT_PATH.
-# FVD, LPIPS and the latent MSEs need networks this project does not ship; the JSON lists them under "not_computed".
+# FVD and the latent MSEs need networks this project does not ship, and LPIPS needs weights it does not ship either; the JSON lists
+# what was not computed under "not_computed".
+# LPIPS_WEIGHTS (optional: one file with a lpips.LPIPS state dict, or torchvision's AlexNet and the lpips package's alex.pth, as
+# .safetensors or torch checkpoints) adds LPIPS; LPIPS_CHANNEL_ORDER (default bgr, as the reference feeds its network; rgb) goes with it.
 # PAIR_BY_NAME (default: true for SEGMENT_ID > 0) pairs the frame files both folders share: a later segment holds 24 generated and
 # 25 ground-truth frames, on which the reference's shape assertion fails.
 set -e
@@ -22,4 +25,5 @@ make -s -C evoworld_amd/csrc
 CMD="-m evoworld_amd.metrics --data_path $VIDEO_PATH --gt_subdir predictions_gt_$SEGMENT_ID --gen_subdir predictions_$SEGMENT_ID \
  --result_file $RESULT_PATH --test_length 25 --num_video $NUM_VIDEO"
 [ "$PAIR_BY_NAME" = true ] && CMD="$CMD --pair_by_name"
+[ -n "$LPIPS_WEIGHTS" ] && CMD="$CMD --metrics psnr,ssim,lpips --lpips_weights $LPIPS_WEIGHTS --lpips_channel_order ${LPIPS_CHANNEL_ORDER:-bgr}"
 python $CMD

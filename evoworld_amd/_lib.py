@@ -12,7 +12,7 @@ from ctypes import c_char_p, c_float, c_int, c_longlong, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EW_LIB_PATH") or os.path.join(_HERE, "libevoworld_hip.so")   # EW_LIB_PATH: another build of the same ABI (A/B tools)
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 # every symbol declared in include/evoworld_hip.h
 SYMBOLS = [
@@ -28,6 +28,7 @@ SYMBOLS = [
     "ew_pano_yaw_rotate",
     "ew_video_metrics_workspace_bytes", "ew_video_metrics", "ew_gt_dump_map_u8",
     "ew_equi2cube_u8",
+    "ew_im2col_f16", "ew_maxpool3s2_relu_f16", "ew_lpips_head_workspace_bytes", "ew_lpips_head",
 ]
 
 
@@ -116,6 +117,9 @@ def load():
         "ew_video_metrics": [P, P, I, I, I, I, I, I, P, P, P, P],
         "ew_gt_dump_map_u8": [P, P, c_size_t, P],
         "ew_equi2cube_u8": [P, P, I, I, I, I, P],
+        "ew_im2col_f16": [P, I, P, I, I, I, I, I, I, I, I, I, I, I, I, ctypes.POINTER(c_float), P],
+        "ew_maxpool3s2_relu_f16": [P, P, I, I, I, I, I, I, P],
+        "ew_lpips_head": [P, P, P, P, P, I, I, I, I, ctypes.c_double, P, P, P],
         "ew_blur_axis_f32": [P, P, I, P, LL, I, I, I, P],
         "ew_bicubic_resize_f32": [P, P, I, I, I, I, I, I, P, P, P],
         "ew_vit_patchify_f16": [P, P, I, I, I, I, P],
@@ -129,6 +133,8 @@ def load():
     lib.ew_filter_compact_workspace_bytes.restype = c_size_t
     lib.ew_video_metrics_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
     lib.ew_video_metrics_workspace_bytes.restype = c_size_t
+    lib.ew_lpips_head_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
+    lib.ew_lpips_head_workspace_bytes.restype = c_size_t
     lib.ew_set_gemm_generation.argtypes = [c_int]
     lib.ew_set_gemm_generation.restype = None
     lib.ew_get_gemm_generation.restype = c_int

@@ -1,0 +1,213 @@
+"""LPIPS with the AlexNet backbone on the device, from weights the user supplies: the counterpart of the reference's
+evoworld/metrics/other_metrics/calculate_lpips.py (run by calculate_all_metrics.py:195-221), i.e. per frame pair
+lpips.LPIPS(net='alex', spatial=True).forward(img1, img2).mean() on frames mapped from [0,1] to [-1,1].
+
+The five convolutions run on ops.gemm (dense mode, bias vector) over the patch rows of ops.im2col; ops.maxpool3s2_relu and
+ops.lpips_head do the rest (csrc/lpips.hip).  Conv outputs stay pre-ReLU in memory: every reader applies max(x, 0) itself.  The mean
+over the bilinearly upsampled distance map is a weighted sum over the tap's own pixels (upsample_mean_weights), so no full-size map
+exists.  This project ships no weights: they come from a lpips.LPIPS state dict, or from torchvision's AlexNet plus the lpips
+package's alex.pth.
+"""
+import numpy as np
+import torch
+
+# (torchvision features index, out channels, in channels, kernel, stride, padding); a tap follows each convolution's ReLU
+CONVS = ((0, 64, 3, 11, 4, 2), (3, 192, 64, 5, 1, 2), (6, 384, 192, 3, 1, 1), (8, 256, 384, 3, 1, 1), (10, 256, 256, 3, 1, 1))
+POOL_AFTER = (True, True, False, False, False)         # MaxPool2d(3, 2) between conv1 / conv2 and conv2 / conv3
+SHIFT = (-.030, -.088, -.188)                          # lpips ScalingLayer
+SCALE = (.458, .448, .450)
+K_ALIGN = 64                                           # ew_gemm_f16 takes K in multiples of 64
+MIN_SIZE = 31                                          # smallest H, W that leave every tap at least 1 x 1
+
+
+def upsample_mean_weights(n_in, n_out):
+    """float64 [n_in]: how often F.interpolate(size=n_out, mode='bilinear', align_corners=False) counts each of n_in input samples
+    along one axis, so that mean(upsample(m)) = sum_yx wy[y] wx[x] m[y,x] / (H W).  torch's index arithmetic:
+    src = max(0, (i + 0.5) * n_in / n_out - 0.5), i0 = floor(src), i1 = min(i0 + 1, n_in - 1).  The weights sum to n_out."""
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"upsample_mean_weights: n_in, n_out = {n_in}, {n_out} must be positive")
+    i = np.arange(n_out, dtype=np.float64)
+    src = np.maximum(0.0, (i + 0.5) * (float(n_in) / float(n_out)) - 0.5)
+    i0 = np.minimum(np.floor(src).astype(np.int64), n_in - 1)
+    i1 = np.minimum(i0 + 1, n_in - 1)
+    l1 = src - i0
+    w = np.zeros(n_in, dtype=np.float64)
+    np.add.at(w, i0, 1.0 - l1)
+    np.add.at(w, i1, l1)
+    return w
+
+
+def tap_sizes(H, W):
+    """[(h, w)] of the five taps for H x W frames; ValueError when a tap would be empty."""
+    if H < MIN_SIZE or W < MIN_SIZE:
+        raise ValueError(f"LPIPS (AlexNet) needs frames of at least {MIN_SIZE} x {MIN_SIZE}: at {H} x {W} a feature map is empty")
+    out, h, w = [], H, W
+    for (_, _, _, k, s, p), pool in zip(CONVS, POOL_AFTER):
+        h, w = (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1
+        out.append((h, w))
+        if pool:
+            h, w = (h - 3) // 2 + 1, (w - 3) // 2 + 1
+    return out
+
+
+def _spec():
+    spec = {}
+    for i, (_, co, ci, k, _, _) in enumerate(CONVS):
+        spec[f"conv{i}.weight"] = (co, ci, k, k)
+        spec[f"conv{i}.bias"] = (co,)
+        spec[f"lin{i}"] = (1, co, 1, 1)
+    return spec
+
+
+def canonical_state_dict(sd):
+    """Either accepted key layout -> {conv{i}.weight, conv{i}.bias, lin{i} (i = 0..4), optional shift / scale}, validated.
+    Layouts: a full lpips.LPIPS.state_dict() (net.slice{i+1}.{idx}.weight|bias, lin{i}.model.1.weight, optional scaling_layer.shift|scale;
+    the duplicate lins.* entries are ignored), or torchvision AlexNet's features.{idx}.weight|bias merged with the lpips package's
+    alex.pth (lin{i}.model.1.weight).  KeyError lists the first missing keys; ValueError names a key of the wrong shape."""
+    out, missing = {}, []
+    for i, (idx, *_rest) in enumerate(CONVS):
+        for part in ("weight", "bias"):
+            names = (f"net.slice{i + 1}.{idx}.{part}", f"features.{idx}.{part}")
+            found = [n for n in names if n in sd]
+            if found:
+                out[f"conv{i}.{part}"] = (found[0], sd[found[0]])
+            else:
+                missing.append(" | ".join(names))
+        n = f"lin{i}.model.1.weight"
+        if n in sd:
+            out[f"lin{i}"] = (n, sd[n])
+        else:
+            missing.append(n)
+    if missing:
+        raise KeyError(f"LPIPS state dict is missing {len(missing)} keys, e.g. {missing[:3]}")
+    for k, shape in _spec().items():
+        name, t = out[k]
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
+    for k in ("shift", "scale"):
+        n = f"scaling_layer.{k}"
+        if n in sd:
+            if sd[n].numel() != 3:
+                raise ValueError(f"{n}: expected shape (1, 3, 1, 1), got {tuple(sd[n].shape)}")
+            out[k] = (n, sd[n])
+    return {k: t.detach().to("cpu", torch.float32) for k, (_, t) in out.items()}
+
+
+def pack_state_dict(sd):
+    """State dict (either layout) -> the tensors the kernels read, on the CPU: w{i} fp16 [C_out, K padded to 64] with K ordered
+    (ky, kx, c_in) as ops.im2col writes its columns, b{i} fp16 [C_out], lin{i} fp32 [C_out], shift / scale (tuples of 3 floats)."""
+    c = canonical_state_dict(sd)
+    packed = {}
+    for i, (_, co, ci, k, _, _) in enumerate(CONVS):
+        K = k * k * ci
+        w = torch.zeros(co, -(-K // K_ALIGN) * K_ALIGN, dtype=torch.float16)
+        w[:, :K] = c[f"conv{i}.weight"].permute(0, 2, 3, 1).reshape(co, K).half()
+        packed[f"w{i}"] = w
+        packed[f"b{i}"] = c[f"conv{i}.bias"].half().contiguous()
+        packed[f"lin{i}"] = c[f"lin{i}"].reshape(co).contiguous()
+    packed["shift"] = tuple(float(v) for v in c["shift"].reshape(3)) if "shift" in c else SHIFT
+    packed["scale"] = tuple(float(v) for v in c["scale"].reshape(3)) if "scale" in c else SCALE
+    return packed
+
+
+def load_state_files(paths):
+    """One or more weight files (.safetensors, or anything torch.load(..., weights_only=True) reads) merged into one state dict."""
+    if isinstance(paths, (str, bytes)) or hasattr(paths, "__fspath__"):
+        paths = [paths]
+    sd = {}
+    for p in paths:
+        if str(p).endswith(".safetensors"):
+            from safetensors.torch import load_file
+            part = load_file(str(p))
+        else:
+            part = torch.load(p, map_location="cpu", weights_only=True)
+            if isinstance(part, dict) and "state_dict" in part and isinstance(part["state_dict"], dict):
+                part = part["state_dict"]
+        sd.update(part)
+    return sd
+
+
+class LPIPSAlex:
+    """lpips.LPIPS(net='alex', spatial=True) followed by the mean over the map, per frame pair, on the device."""
+
+    def __init__(self, packed, device, chunk=4):
+        self.device = torch.device(device)
+        self.chunk = int(chunk)                    # frame pairs whose activations are alive at once
+        self.shift, self.scale = packed["shift"], packed["scale"]
+        self.w = [packed[f"w{i}"].to(self.device) for i in range(5)]
+        self.b = [packed[f"b{i}"].to(self.device) for i in range(5)]
+        self.lin = [packed[f"lin{i}"].to(self.device) for i in range(5)]
+        self._mean_w = {}
+
+    @classmethod
+    def from_state_dict(cls, sd, device="cuda", chunk=4):
+        return cls(pack_state_dict(sd), device, chunk)
+
+    @classmethod
+    def from_files(cls, paths, device="cuda", chunk=4):
+        return cls.from_state_dict(load_state_files(paths), device, chunk)
+
+    @classmethod
+    def from_random(cls, seed=0, device="cuda", chunk=4):
+        """AlexNet-shaped random weights (timing and tests; the values mean nothing): conv weights N(0, 1 / fan-in), small biases,
+        non-negative lin weights."""
+        return cls.from_state_dict(random_state_dict(seed), device, chunk)
+
+    def _weights_for(self, h, w, H, W):
+        key = (h, w, H, W)
+        if key not in self._mean_w:
+            self._mean_w[key] = (torch.from_numpy(upsample_mean_weights(h, H)).to(self.device),
+                                 torch.from_numpy(upsample_mean_weights(w, W)).to(self.device))
+        return self._mean_w[key]
+
+    def features(self, frames, channel_order="rgb"):
+        """frames uint8 [n,H,W,3] or fp32 [n,3,H,W] in [0,1] -> the five pre-ReLU conv outputs, fp16 [n,h,w,C] each.  Every image goes
+        through ew_gemm_f16 on its own, so its features do not depend on what else is in the batch."""
+        from . import ops
+        if channel_order not in ("rgb", "bgr"):
+            raise ValueError(f"channel_order {channel_order!r}: expected 'rgb' or 'bgr'")
+        taps, x = [], frames
+        for i, (_, co, ci, k, s, p) in enumerate(CONVS):
+            first = (self.shift, self.scale, channel_order == "bgr") if i == 0 else None
+            rows, ho, wo = ops.im2col(x, k, s, p, self.w[i].shape[1], relu=i >= 3, first=first)
+            n, ldk = rows.shape[0] // (ho * wo), rows.shape[1]
+            y = torch.empty(n, ho, wo, co, dtype=torch.float16, device=rows.device)
+            for j in range(n):
+                ops.gemm(rows[j * ho * wo:(j + 1) * ho * wo], self.w[i], y[j], M=ho * wo, N=co, c1=ldk, lda=ldk, bias=self.b[i])
+            taps.append(y)
+            x = ops.maxpool3s2_relu(y) if POOL_AFTER[i] else y
+        return taps
+
+    def __call__(self, a, b, channel_order="rgb", chunk=None):
+        """a, b: uint8 [F,H,W,3] or fp32 [F,3,H,W] in [0,1] on the device (channels R, G, B) -> fp64 [F] on the device.
+        channel_order 'bgr' hands the network B, G, R planes, as the reference's cv2.imread frames reach it."""
+        from . import ops
+        if a.shape != b.shape or a.dtype != b.dtype or a.device != b.device:
+            raise ValueError(f"a {tuple(a.shape)} {a.dtype} on {a.device} and b {tuple(b.shape)} {b.dtype} on {b.device} differ")
+        if a.ndim != 4 or a.dtype not in (torch.uint8, torch.float32):
+            raise ValueError(f"frames: expected uint8 [F,H,W,3] or fp32 [F,3,H,W], got {a.dtype} {tuple(a.shape)}")
+        F_ = a.shape[0]
+        H, W = (a.shape[1], a.shape[2]) if a.dtype == torch.uint8 else (a.shape[2], a.shape[3])
+        sizes = tap_sizes(H, W)
+        chunk = max(1, int(chunk or self.chunk))
+        acc = torch.zeros(F_, dtype=torch.float64, device=a.device)
+        for f0 in range(0, F_, chunk):
+            n = min(chunk, F_ - f0)
+            taps = self.features(torch.cat([a[f0:f0 + n], b[f0:f0 + n]]).contiguous(), channel_order)
+            for i, t in enumerate(taps):
+                wy, wx = self._weights_for(*sizes[i], H, W)
+                ops.lpips_head(t[:n], t[n:], self.lin[i], wy, wx, H * W, acc[f0:f0 + n])
+        ops.streamk_check()                        # results leave here: a timed-out stream-K hand-over in a convolution must not pass silently
+        return acc
+
+
+def random_state_dict(seed=0):
+    """A seeded lpips.LPIPS-layout state dict with AlexNet's shapes: conv weights scaled by 1 / sqrt(fan-in) so activations stay
+    O(1), biases N(0, 0.1^2), lin weights uniform in [0, 1) (non-negative, as the trained ones are)."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for i, (idx, co, ci, k, _, _) in enumerate(CONVS):
+        sd[f"net.slice{i + 1}.{idx}.weight"] = torch.randn(co, ci, k, k, generator=g) / float(ci * k * k) ** 0.5
+        sd[f"net.slice{i + 1}.{idx}.bias"] = 0.1 * torch.randn(co, generator=g)
+        sd[f"lin{i}.model.1.weight"] = torch.rand(1, co, 1, 1, generator=g)
+    return sd

@@ -5,8 +5,10 @@ other_metrics/calculate_psnr.py and calculate_ssim.py.
 Per-frame values come from one kernel pass over each frame pair (ops.video_metrics, csrc/metrics.hip); the per-timestamp mean
 and std and the overall mean are the reference's numpy aggregation over those fp64 values.  FVD, LPIPS and the latent MSEs need
 pretrained networks (I3D, LPIPS/AlexNet, the SVD VAE) that this project does not ship: they are listed under `not_computed`.
+LPIPS is computed as well (evoworld_amd/lpips.py, csrc/lpips.hip) when the user names a file with its weights.
 
     python -m evoworld_amd.metrics --data_path OUT --gt_subdir predictions_gt_2 --gen_subdir predictions_2 [--pair_by_name]
+                                   [--metrics psnr,ssim,lpips --lpips_weights lpips_alex.safetensors]
 """
 import argparse
 import json
@@ -82,6 +84,17 @@ def calculate_ssim(videos1, videos2):
     return aggregate(ssim, videos1[0].shape)
 
 
+def calculate_lpips(videos1, videos2, model, channel_order="rgb"):
+    """calculate_lpips(videos1, videos2, device) of calculate_lpips.py: [B,T,3,H,W] in [0,1] -> the reference's result dict, with
+    `model` an evoworld_amd.lpips.LPIPSAlex.  channel_order 'bgr' feeds the network B, G, R planes as the reference's main does."""
+    if videos1.shape != videos2.shape:
+        raise AssertionError(f"video shapes differ: {tuple(videos1.shape)} vs {tuple(videos2.shape)}")
+    B, T, C, H, W = videos1.shape
+    a = videos1.reshape(B * T, C, H, W).to(model.device, torch.float32).contiguous()
+    b = videos2.reshape(B * T, C, H, W).to(model.device, torch.float32).contiguous()
+    return aggregate(model(a, b, channel_order).cpu().numpy().reshape(B, T), videos1[0].shape)
+
+
 def video_metrics_u8(gt, gen):
     """uint8 [F,H,W,3] device tensors -> (psnr, ssim) numpy fp64 [F]: the per-frame values of the reference's main on frames
     read as uint8 and divided by 255.0."""
@@ -105,14 +118,23 @@ def parse_args(argv=None):
                    help="comma-separated; psnr and ssim are computed, the others need networks this project lacks")
     p.add_argument("--pair_by_name", action="store_true",
                    help="pair the last 25 file names both folders share (segments >= 1 hold 24 generated and 25 GT frames)")
+    p.add_argument("--lpips_weights", type=str, nargs="+", default=None, metavar="PATH",
+                   help="LPIPS (AlexNet) weights, .safetensors or a torch checkpoint: a lpips.LPIPS state dict, or torchvision's AlexNet "
+                        "and the lpips package's alex.pth as two files; allows lpips in --metrics")
+    p.add_argument("--lpips_channel_order", type=str, choices=("bgr", "rgb"), default="bgr",
+                   help="bgr (default): the network sees B, G, R planes as in the reference, whose cv2.imread frames are never "
+                        "swapped; rgb: LPIPS as its authors define it")
     args = p.parse_args(argv)
     args.result_file = os.path.join(args.data_path, args.result_file)
     return args
 
 
-def selected_metrics(spec):
+def selected_metrics(spec, lpips_weights=False):
+    """The metric names of --metrics.  lpips_weights: the user supplied LPIPS weights, which lifts the refusal of `lpips`."""
     names = [m.strip() for m in spec.split(",") if m.strip()]
     for m in names:
+        if m == "lpips" and lpips_weights:
+            continue
         if m in NOT_COMPUTED:
             raise ValueError(f"metric {m!r} cannot be computed: it {NOT_COMPUTED[m]}")
         if m not in SUPPORTED:
@@ -154,7 +176,12 @@ def _decode(path):
 def evaluate(args, device="cuda"):
     """main(args) of calculate_all_metrics.py:209-236 for PSNR / SSIM: one episode at a time is decoded (thread pool) and streamed
     to the device as uint8.  Returns (result dict, timing dict)."""
-    names = selected_metrics(args.metrics)
+    weights = getattr(args, "lpips_weights", None)
+    names = selected_metrics(args.metrics, lpips_weights=bool(weights))
+    lpips_model, lpips_order, lpips = None, getattr(args, "lpips_channel_order", "bgr"), []
+    if "lpips" in names:
+        from .lpips import LPIPSAlex
+        lpips_model = LPIPSAlex.from_files(weights, device)
     episodes = list_episode_folders(args.data_path, args.num_videos)
     if not episodes:
         raise ValueError(f"no episode folders under {args.data_path}")
@@ -172,7 +199,10 @@ def evaluate(args, device="cuda"):
             if shape is not None and gt.shape != shape:
                 raise ValueError(f"episode {ep}: frames {gt.shape} differ from the first episode's {shape}")
             shape = gt.shape
-            p, s = video_metrics_u8(torch.from_numpy(gt).to(device), torch.from_numpy(gen).to(device))
+            gt_d, gen_d = torch.from_numpy(gt).to(device), torch.from_numpy(gen).to(device)
+            p, s = video_metrics_u8(gt_d, gen_d)
+            if lpips_model is not None:
+                lpips.append(lpips_model(gt_d, gen_d, lpips_order).cpu().numpy())
             t_device += time.perf_counter() - t1
             t_decode += t1 - t0
             psnr.append(p)
@@ -184,7 +214,9 @@ def evaluate(args, device="cuda"):
         result["ssim"] = aggregate(ssim, setting)
     if "psnr" in names:
         result["psnr"] = aggregate(psnr, setting)
-    result["not_computed"] = dict(NOT_COMPUTED)
+    if lpips_model is not None:
+        result["lpips"] = aggregate(lpips, setting)
+    result["not_computed"] = {k: v for k, v in NOT_COMPUTED.items() if not (k == "lpips" and lpips_model is not None)}
     return result, {"episodes": len(episodes), "frames": len(episodes) * T, "decode_s": t_decode, "device_s": t_device}
 
 

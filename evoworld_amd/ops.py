@@ -557,6 +557,77 @@ def gt_dump_map_u8(src):
     _lib.check(lib.ew_gt_dump_map_u8(_ptr(src), _ptr(dst), src.numel(), _stream()), "ew_gt_dump_map_u8")
     return dst
 
+
+def conv_out_size(n, k, stride, pad):
+    return (n + 2 * pad - k) // stride + 1
+
+
+def im2col(src, k, stride, pad, ldk, relu=False, first=None):
+    """k x k / stride / zero-pad patch rows for a convolution on ew_gemm_f16 (ew_im2col_f16): src fp16 NHWC [n,h,w,C] (C % 8 == 0;
+    relu: read max(x, 0)) -> fp16 [n*h_out*w_out, ldk], column (ky*k + kx)*C + c, zero beyond k*k*C.  first = (shift[3], scale[3],
+    swap_rb): src is a batch of frames in [0,1], uint8 [n,h,w,3] or fp32 [n,3,h,w], mapped 2v - 1 -> (x - shift) / scale on the way
+    (network channel c reads frame channel 2 - c when swap_rb).  Returns (rows, h_out, w_out)."""
+    lib = _lib.load()
+    affine, swap = None, 0
+    if first is None:
+        _req(src, torch.float16, "src")
+        if src.ndim != 4:
+            raise ValueError(f"src: expected fp16 [n,h,w,C], got {tuple(src.shape)}")
+        kind = 0
+        n, h, w, C = src.shape
+    else:
+        shift, scale, swap = first
+        affine = (ctypes.c_float * 6)(*[float(v) for v in shift], *[float(v) for v in scale])
+        if src.dtype == torch.uint8:
+            _req(src, torch.uint8, "src")
+            kind = 1
+            n, h, w, C = src.shape if src.ndim == 4 else (0, 0, 0, 0)
+        else:
+            _req(src, torch.float32, "src")
+            kind = 2
+            n, C, h, w = src.shape if src.ndim == 4 else (0, 0, 0, 0)
+        if C != 3:
+            raise ValueError(f"src: expected uint8 [n,h,w,3] or fp32 [n,3,h,w] frames, got {tuple(src.shape)}")
+    ho, wo = conv_out_size(h, k, stride, pad), conv_out_size(w, k, stride, pad)
+    if ho < 1 or wo < 1:
+        raise ValueError(f"im2col: a {k}x{k} window (pad {pad}) does not fit {h}x{w}")
+    out = torch.empty(n * ho * wo, ldk, dtype=torch.float16, device=src.device)
+    _lib.check(lib.ew_im2col_f16(_ptr(src), kind, _ptr(out), n, h, w, C, k, stride, pad, ho, wo, ldk, int(bool(relu)), int(bool(swap)),
+                                 affine, _stream()), "ew_im2col_f16")
+    return out, ho, wo
+
+
+def maxpool3s2_relu(x):
+    """MaxPool2d(3, 2) of max(x, 0) (ew_maxpool3s2_relu_f16): fp16 NHWC [n,h,w,C], C % 8 == 0 -> [n, (h-3)//2+1, (w-3)//2+1, C]."""
+    lib = _lib.load()
+    _req(x, torch.float16, "x")
+    if x.ndim != 4 or x.shape[1] < 3 or x.shape[2] < 3:
+        raise ValueError(f"x: expected fp16 [n,h,w,C] with h, w >= 3, got {tuple(x.shape)}")
+    n, h, w, C = x.shape
+    ho, wo = (h - 3) // 2 + 1, (w - 3) // 2 + 1
+    out = torch.empty(n, ho, wo, C, dtype=torch.float16, device=x.device)
+    _lib.check(lib.ew_maxpool3s2_relu_f16(_ptr(x), _ptr(out), n, h, w, C, ho, wo, _stream()), "ew_maxpool3s2_relu_f16")
+    return out
+
+
+def lpips_head(fa, fb, lin, wy, wx, n_out, acc):
+    """One LPIPS tap of F frame pairs (ew_lpips_head): fa, fb fp16 [F,h,w,C] pre-ReLU conv outputs, lin fp32 [C], wy [h] / wx [w] fp64
+    (lpips.upsample_mean_weights on the device), n_out = H * W of the frames; acc fp64 [F] += the tap's mean over the upsampled map."""
+    lib = _lib.load()
+    _req(fa, torch.float16, "fa"); _req(fb, torch.float16, "fb"); _req(lin, torch.float32, "lin")
+    _req(wy, torch.float64, "wy"); _req(wx, torch.float64, "wx"); _req(acc, torch.float64, "acc")
+    if fa.ndim != 4 or fb.shape != fa.shape:
+        raise ValueError(f"fa {tuple(fa.shape)} / fb {tuple(fb.shape)}: expected two fp16 [F,h,w,C] tensors of one shape")
+    F_, h, w, C = fa.shape
+    if lin.numel() != C or wy.numel() != h or wx.numel() != w or acc.numel() != F_:
+        raise ValueError(f"lpips_head: lin / wy / wx / acc hold {lin.numel()}, {wy.numel()}, {wx.numel()}, {acc.numel()} values for "
+                         f"C, h, w, F = {C}, {h}, {w}, {F_}")
+    ws = torch.empty(max(1, lib.ew_lpips_head_workspace_bytes(F_, h, w, C)), dtype=torch.uint8, device=fa.device)
+    _lib.check(lib.ew_lpips_head(_ptr(fa), _ptr(fb), _ptr(lin), _ptr(wy), _ptr(wx), F_, h, w, C, float(n_out), _ptr(acc), _ptr(ws), _stream()),
+               "ew_lpips_head")
+    return acc
+
+
 def blur_axis(x, kern, axis):
     """x fp32 [..., H, W], kern fp32 [k] -> correlation along H (axis 0) or W (axis 1), reflect padding."""
     lib = _lib.load()

@@ -27,7 +27,7 @@ typedef int ew_status;
 #define EW_ERR_UNSUPPORTED (-2)
 #define EW_ERR_HIP (-3)
 
-#define EW_ABI_VERSION 13
+#define EW_ABI_VERSION 14
 int ew_abi_version(void);
 const char* ew_last_error(void);
 
@@ -392,6 +392,35 @@ ew_status ew_gt_dump_map_u8(const uint8_t* src, uint8_t* dst, size_t n, void* st
  * interpolation = 0: round half to even, pixels whose index falls outside the panorama (uf == W on the seam) stay black (:638-646).
  * cross 4-byte aligned; one launch for all V panoramas. */
 ew_status ew_equi2cube_u8(const uint8_t* pano, uint8_t* cross, int V, int H, int W, int interpolation, void* stream);
+
+/* LPIPS with the AlexNet backbone (ABI 14; evoworld/metrics/other_metrics/calculate_lpips.py, calculate_all_metrics.py:195-221:
+ * lpips.LPIPS(net='alex', spatial=True).forward(img1, img2).mean() per frame pair).  The five convolutions run on ew_gemm_f16 (dense
+ * mode, bias vector) over the patch rows of ew_im2col_f16; their outputs are stored PRE-ReLU and the three kernels below apply
+ * max(x, 0) where they read (ReLU commutes with max-pooling).  Weights come from the caller: the project ships none.
+ *
+ * ew_im2col_f16: k x k / stride / zero-pad patch gather -> out fp16 [n_img*h_out*w_out, ldk], column (ky*k + kx)*C + c, columns
+ *   [k*k*C, ldk) zero (ldk % 8 == 0: pad K to the multiple of 64 ew_gemm_f16 wants).  h_out = floor((h_in + 2 pad - k) / stride) + 1.
+ *   src_kind 0: src fp16 NHWC [n_img,h_in,w_in,C], C % 8 == 0, 16-byte aligned; relu = 1 reads max(x, 0).
+ *   src_kind 1 / 2 (the first layer): src uint8 [n_img,h_in,w_in,3] (a pixel is float32(k) / 255.0f) or fp32 [n_img,3,h_in,w_in], frames in
+ *   [0,1]: network channel c reads frame channel (swap_rb ? 2 - c : c), v -> 2v - 1 -> (x - shift[c]) / scale[c] (the [-1,1] map of
+ *   calculate_lpips.py and lpips' ScalingLayer), each step one float32 rounding, then fp16.  first_affine: HOST pointer to
+ *   {shift[3], scale[3]} (read during the call); NULL, swap_rb = 0 for src_kind 0.
+ * ew_maxpool3s2_relu_f16: MaxPool2d(3, 2) of max(x, 0), fp16 NHWC, h_out = floor((h_in - 3) / 2) + 1, C % 8 == 0.
+ * ew_lpips_head, one tap of F frame pairs: fa, fb fp16 [F, h, w, C] pre-ReLU (C % 8 == 0, <= 512); per pixel
+ *   d = sum_c lin[c] * (a_c / (|a| + 1e-10) - b_c / (|b| + 1e-10))^2 with |.| over channels, in fp32; then
+ *   acc[f] += sum_yx d[y,x] * wy[y] * wx[x] / n_out in fp64 (acc fp64 [F], read and written: zero it before the first tap).
+ *   wy [h], wx [w] (fp64, device): how often bilinear upsampling (align_corners=False) to the frame size counts each row / column, so that
+ *   with n_out = H * W this is the mean of the upsampled map without materialising it (evoworld_amd.lpips.upsample_mean_weights).
+ *   lin fp32 [C].  Two fixed-order reduction stages through `workspace` (ew_lpips_head_workspace_bytes(F, h, w, C) bytes, 8-byte aligned;
+ *   the block count depends on (h, w, C) only), no atomics: two calls are bit-identical, f's value does not depend on F, swapping fa and
+ *   fb gives the same bits, identical inputs give exactly 0. */
+enum { EW_IM2COL_F16_NHWC = 0, EW_IM2COL_U8_HWC = 1, EW_IM2COL_F32_CHW = 2 };
+ew_status ew_im2col_f16(const void* src, int src_kind, void* out, int n_img, int h_in, int w_in, int C, int k, int stride, int pad,
+                        int h_out, int w_out, int ldk, int relu, int swap_rb, const float* first_affine, void* stream);
+ew_status ew_maxpool3s2_relu_f16(const void* src, void* out, int n_img, int h_in, int w_in, int C, int h_out, int w_out, void* stream);
+size_t ew_lpips_head_workspace_bytes(int F, int h, int w, int C);
+ew_status ew_lpips_head(const void* fa, const void* fb, const float* lin, const double* wy, const double* wx, int F, int h, int w, int C,
+                        double n_out, double* acc, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

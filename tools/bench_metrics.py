@@ -8,6 +8,10 @@
                                                            times evoworld_amd.metrics over them: PNG decode vs device seconds
   python tools/bench_metrics.py episode --root DIR [--poses 80]  writes a seeded episode tree DIR/case_000 (camera_poses.txt and
                                                            panorama/NNN.png, 500x1000) for run_unified_pipeline.sh BASE_FOLDER=DIR
+  python tools/bench_metrics.py --lpips [--iters N] [--cpu_baseline]   LPIPS (AlexNet, seeded random weights) of the same 25 pairs through
+                                                           evoworld_amd.lpips: ms per clip, host clock around a synchronised call; with
+                                                           --cpu_baseline the same clip once through the fp32 PyTorch restatement
+                                                           (tests/lpips_ref.py) on this machine's CPU, and the two results compared
 Each mode prints one JSON line."""
 import argparse
 import json
@@ -56,6 +60,34 @@ def bench_kernel(iters):
     return {"mode": "kernel", "frames": F, "shape": [H, W, 3], "us_per_call": round(us, 1), "us_per_frame": round(us / F, 2),
             "input_GBps": round(nbytes / us / 1e3, 1), "hbm_fraction": round(nbytes / us / 1e6 / HBM_TBS, 4), "iters": iters,
             "note": "event-timed call (both kernels + the workspace allocation); kernel time: rocprofv3 --kernel-trace --stats"}
+
+
+def bench_lpips(iters, cpu_baseline):
+    from evoworld_amd.lpips import LPIPSAlex, random_state_dict
+    sd = random_state_dict(0)
+    model = LPIPSAlex.from_state_dict(sd, "cuda")
+    gt, gen = seeded_pair(0)
+    for _ in range(2):
+        out = model(gt, gen, "bgr")
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        out = model(gt, gen, "bgr")
+    torch.cuda.synchronize()
+    ms = (time.perf_counter() - t0) * 1e3 / iters
+    rec = {"mode": "lpips", "frames": F, "shape": [H, W, 3], "ms_per_clip": round(ms, 2), "ms_per_pair": round(ms / F, 3), "iters": iters,
+           "lpips_mean": float(out.mean()), "weights": "random (seed 0)", "chunk_pairs": model.chunk,
+           "note": "host clock around the whole call (uint8 frames already on the device), synchronised"}
+    if cpu_baseline:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import lpips_ref
+        a, b = (t.cpu().permute(0, 3, 1, 2).float() / 255.0 for t in (gt, gen))
+        t0 = time.perf_counter()
+        ref = lpips_ref.lpips_alex(a, b, sd, channel_order="bgr")
+        rec["cpu_restatement_ms_per_clip"] = round((time.perf_counter() - t0) * 1e3, 1)
+        rec["cpu_threads"] = torch.get_num_threads()
+        rec["max_rel_err_vs_cpu"] = float(((out.cpu() - ref.double()).abs() / ref.double().abs()).max())
+    return rec
 
 
 def write_cli_tree(root, episodes):
@@ -110,14 +142,20 @@ def write_episode(root, poses):
 
 def main():
     p = argparse.ArgumentParser()
-    p.add_argument("mode", choices=["kernel", "cli", "episode"])
-    p.add_argument("--iters", type=int, default=50)
+    p.add_argument("mode", nargs="?", choices=["kernel", "cli", "episode"])
+    p.add_argument("--lpips", action="store_true", help="time LPIPS (random weights) on a 25-pair 576x1024 clip")
+    p.add_argument("--cpu_baseline", action="store_true", help="with --lpips: also run the clip through tests/lpips_ref.py on the CPU")
+    p.add_argument("--iters", type=int, default=None, help="timed calls (default: 50 for kernel, 5 for --lpips)")
     p.add_argument("--root", help="directory the cli / episode modes write their PNG trees to")
     p.add_argument("--episodes", type=int, default=20)
     p.add_argument("--poses", type=int, default=80)
     a = p.parse_args()
-    if a.mode == "kernel":
-        rec = bench_kernel(a.iters)
+    if a.lpips == (a.mode is not None):
+        p.error("give one of kernel / cli / episode, or --lpips")
+    if a.lpips:
+        rec = bench_lpips(a.iters or 5, a.cpu_baseline)
+    elif a.mode == "kernel":
+        rec = bench_kernel(a.iters or 50)
     elif a.mode == "cli":
         rec = bench_cli(a.root, a.episodes)
     else:
