@@ -12,7 +12,7 @@ from ctypes import c_char_p, c_float, c_int, c_longlong, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EW_LIB_PATH") or os.path.join(_HERE, "libevoworld_hip.so")   # EW_LIB_PATH: another build of the same ABI (A/B tools)
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 # every symbol declared in include/evoworld_hip.h
 SYMBOLS = [
@@ -29,6 +29,7 @@ SYMBOLS = [
     "ew_video_metrics_workspace_bytes", "ew_video_metrics", "ew_gt_dump_map_u8",
     "ew_equi2cube_u8",
     "ew_im2col_f16", "ew_maxpool3s2_relu_f16", "ew_lpips_head_workspace_bytes", "ew_lpips_head",
+    "ew_quant_rows_fp8", "ew_gemm_fp8",
 ]
 
 
@@ -120,6 +121,8 @@ def load():
         "ew_im2col_f16": [P, I, P, I, I, I, I, I, I, I, I, I, I, I, I, ctypes.POINTER(c_float), P],
         "ew_maxpool3s2_relu_f16": [P, P, I, I, I, I, I, I, P],
         "ew_lpips_head": [P, P, P, P, P, I, I, I, I, ctypes.c_double, P, P, P],
+        "ew_quant_rows_fp8": [P, P, P, I, I, P],
+        "ew_gemm_fp8": [P, P, P, P, P, I, I, I, LL, F, P],
         "ew_blur_axis_f32": [P, P, I, P, LL, I, I, I, P],
         "ew_bicubic_resize_f32": [P, P, I, I, I, I, I, I, P, P, P],
         "ew_vit_patchify_f16": [P, P, I, I, I, I, P],

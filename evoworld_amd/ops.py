@@ -250,6 +250,41 @@ def attn_spatial_log2(q, k, vt, o, n_seq, S, heads, ld_qk, ld_vt, ld_o):
     return o
 
 
+def quant_rows_fp8(x):
+    """x fp16 [rows, K] -> (q uint8 [rows, K] holding OCP e4m3 bytes, scale fp32 [rows]): scale = amax(row) / 448 (1 for an all-zero
+    row), q = e4m3(x / scale) (ew_quant_rows_fp8).  K % 8 == 0, K <= 2048."""
+    lib = _lib.load()
+    _req(x, torch.float16, "x")
+    if x.ndim != 2:
+        raise ValueError(f"x: expected fp16 [rows, K], got {tuple(x.shape)}")
+    rows, K = x.shape
+    q = torch.empty(rows, K, dtype=torch.uint8, device=x.device)
+    scale = torch.empty(rows, dtype=torch.float32, device=x.device)
+    _lib.check(lib.ew_quant_rows_fp8(_ptr(x), _ptr(q), _ptr(scale), rows, K, _stream()), "ew_quant_rows_fp8")
+    return q, scale
+
+
+def gemm_fp8(aq, a_scale, wq, w_scale, out=None, c_acc=1.0):
+    """aq [M, K], wq [N, K] e4m3 bytes (uint8), a_scale [M], w_scale [N] fp32 -> fp16 [M, N] = (aq wq^T) * a_scale[m] * w_scale[n] * c_acc
+    (ew_gemm_fp8).  `out`: an fp16 [M, N] tensor or view with unit column stride to write into (its row stride is ld_out).
+    Swapping the (bytes, scale) pairs gives the transposed product.  K % 64 == 0, N % 4 == 0."""
+    lib = _lib.load()
+    _req(aq, torch.uint8, "aq"); _req(wq, torch.uint8, "wq"); _req(a_scale, torch.float32, "a_scale"); _req(w_scale, torch.float32, "w_scale")
+    if aq.ndim != 2 or wq.ndim != 2 or aq.shape[1] != wq.shape[1]:
+        raise ValueError(f"aq {tuple(aq.shape)} / wq {tuple(wq.shape)}: expected [M, K] and [N, K]")
+    M, K = aq.shape
+    N = wq.shape[0]
+    if a_scale.numel() != M or w_scale.numel() != N:
+        raise ValueError(f"a_scale / w_scale hold {a_scale.numel()} / {w_scale.numel()} values for M, N = {M}, {N}")
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.float16, device=aq.device)
+    if out.dtype != torch.float16 or out.device != aq.device or tuple(out.shape) != (M, N) or out.stride(1) != 1:
+        raise ValueError(f"out: expected an fp16 [{M}, {N}] device tensor with unit column stride, got {out.dtype} {tuple(out.shape)} strides {out.stride()}")
+    _lib.check(lib.ew_gemm_fp8(_ptr(aq), _ptr(a_scale), _ptr(wq), _ptr(w_scale), _ptr(out), M, N, K, out.stride(0), float(c_acc), _stream()),
+               "ew_gemm_fp8")
+    return out
+
+
 def attn_temporal(q, k, v, o, B, T, S, heads, ld, ld_o, scale=0.125):
     lib = _lib.load()
     _lib.check(lib.ew_attn_temporal_f16(_ptr(q), _ptr(k), _ptr(v), _ptr(o), B, T, S, heads, ld, ld_o, scale, _stream()),

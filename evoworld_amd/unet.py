@@ -235,7 +235,9 @@ def random_state_dict(cfg, seed=0, device="cpu"):
 class UNetSpatioTemporalConditionModel:
     def __init__(self, **config):
         cfg = dict(DEFAULT_CONFIG)
+        cfg["qkv_fp8"] = os.environ.get("EW_QKV_FP8", "0") == "1"      # a keyword argument overrides the environment switch
         cfg.update(config)
+        cfg["qkv_fp8"] = bool(cfg["qkv_fp8"])
         self._cfg = cfg
         self.config = SimpleNamespace(**cfg)
         self.arch = _arch(cfg)
@@ -249,8 +251,12 @@ class UNetSpatioTemporalConditionModel:
         mode = os.environ.get("EW_RESIDUAL", "split")
         self.split_residual = mode != "fp16"
         self.split_heads = mode == "split"     # also split the stream tensors produced WITHOUT a residual operand
-        # (BASELINE.json configs[4]'s fp8 q / k / v projections were built in rounds 2-4, measured slower than the fp16 GEMMs and 6x outside the parity
-        # tolerance, and removed in round 6: tools/experiments/fp8_qkv/; configs[4] runs fp16)
+        # qkv_fp8 (config key, default False; EW_QKV_FP8=1 sets it): BASELINE.json configs[4]'s "fp8 MFMA QKV".  The attn1 q / k / v projections of
+        # every transformer whose width is a multiple of 64 (`fp8_blocks`, filled at load time) run on ew_gemm_fp8: per-row-scaled e4m3 operands
+        # (one fp32 scale per token row, quantised once per LayerNorm output by ew_quant_rows_fp8, and one per weight row, quantised at load time),
+        # fp32 accumulation, fp16 out.  It halves the projections' operand bytes, not their MFMA time, carries its own tolerance
+        # (tests/test_gpu_fp8_qkv.py) and makes no speed claim; the fp16 default is untouched by it.
+        self.fp8_blocks = []
         # round 4: q|k projections carry sqrt(scale * log2 e) in their epilogue and the attention kernel's MFMA subtracts the running max
         # (ew_attn_spatial_log2_f16); attn_log2 = False (attribute, A/B only) restores the scale-and-shift form on ew_attn_spatial_f16
         self.attn_log2 = True
@@ -287,15 +293,17 @@ class UNetSpatioTemporalConditionModel:
 
     # ---------------- construction / loading ----------------
     @classmethod
-    def from_pretrained(cls, path, subfolder=None, device="cuda", **_ignored):
+    def from_pretrained(cls, path, subfolder=None, device="cuda", qkv_fp8=None, **_ignored):
         """diffusers folder layout: <path>/<subfolder>/config.json + diffusion_pytorch_model.safetensors
-        (unified_loop_consistency.py:190-192)."""
+        (unified_loop_consistency.py:190-192).  qkv_fp8: the config key of the same name (None: EW_QKV_FP8 decides)."""
         root = os.path.join(path, subfolder) if subfolder else path
         cfg = {}
         cj = os.path.join(root, "config.json")
         if os.path.exists(cj):
             raw = json.load(open(cj))
             cfg = {k: (tuple(v) if isinstance(v, list) else v) for k, v in raw.items() if k in DEFAULT_CONFIG}
+        if qkv_fp8 is not None:
+            cfg["qkv_fp8"] = qkv_fp8
         m = cls(**cfg)
         from safetensors.torch import load_file
         for fn in ("diffusion_pytorch_model.safetensors", "diffusion_pytorch_model.fp16.safetensors"):
@@ -409,6 +417,10 @@ class UNetSpatioTemporalConditionModel:
             idx = torch.arange(2 * n, device=dev).reshape(2, n // 16, 16).permute(1, 0, 2).reshape(-1)
             return h(w[idx]), h(b[idx])
 
+        def fp8(w):                # [O, I] fp32 -> (e4m3 bytes uint8 [O, I], fp32 scale [O]), one scale per output row, on the device
+            return ops.quant_rows_fp8(h(w))
+
+        self.fp8_blocks = []
         temb_w, temb_b, self._temb_off = [], [], {}
         off = 0
         for r in self.arch.res:
@@ -440,6 +452,9 @@ class UNetSpatioTemporalConditionModel:
         for t in self.arch.trs:
             d = {}
             c = t.ch
+            use_fp8 = self._cfg["qkv_fp8"] and c % 64 == 0      # ew_gemm_fp8 needs K % 64 == 0: other widths keep fp16 projections
+            if use_fp8:
+                self.fp8_blocks.append(t.p)
             d["ng"], d["nb"] = h(f32(t.p + ".norm.weight")), h(f32(t.p + ".norm.bias"))
             d["piw"], d["pib"] = lin2(t.p + ".proj_in", c, self.split_acts), h(f32(t.p + ".proj_in.bias"))
             d["pow"], d["pob"] = lin2(t.p + ".proj_out", c), h(f32(t.p + ".proj_out.bias"))
@@ -451,7 +466,12 @@ class UNetSpatioTemporalConditionModel:
                     d[f"{tag}_{nm}g"], d[f"{tag}_{nm}b"] = h(f32(f"{b}.{nm}.weight")), h(f32(f"{b}.{nm}.bias"))
                 q, k_, v = f32(b + ".attn1.to_q.weight"), f32(b + ".attn1.to_k.weight"), f32(b + ".attn1.to_v.weight")
                 if tag == "s":
-                    d["s_qk"], d["s_v"] = h(torch.cat([q, k_])), h(v)
+                    if use_fp8:     # (bytes, scales) packs in place of the fp16 matrices: they travel through packed_tensors() like any other tuple
+                        d["s_qk8"], d["s_v8"] = fp8(torch.cat([q, k_])), fp8(v)
+                    else:
+                        d["s_qk"], d["s_v"] = h(torch.cat([q, k_])), h(v)
+                elif use_fp8:
+                    d["t_qkv8"] = fp8(torch.cat([q, k_, v]))
                 else:
                     d["t_qkv"] = h(torch.cat([q, k_, v]))
                 d[f"{tag}_ow"], d[f"{tag}_ob"] = h(f32(b + ".attn1.to_out.0.weight")), h(f32(b + ".attn1.to_out.0.bias"))
@@ -582,9 +602,16 @@ class UNetSpatioTemporalConditionModel:
         h = self._lin2(hn, d["piw"], d["pib"], self._res(rows, C, dev, head=True))
         # --- spatial BasicTransformerBlock ---
         n1 = ops.layernorm(h, d["s_norm1g"], d["s_norm1b"])
-        qk = ops.linear(n1, d["s_qk"], c_acc=ops.QK_LOG2_PRESCALE if self.attn_log2 else 1.0)
-        vt = torch.empty(C, rows, dtype=torch.float16, device=dev)
-        ops.gemm(d["s_v"], n1, vt, M=C, N=rows, c1=C, lda=C)      # V^T = W_v X^T (swapped operands)
+        prescale = ops.QK_LOG2_PRESCALE if self.attn_log2 else 1.0
+        if "s_qk8" in d:          # qkv_fp8: n1 is quantised once (one scale per token) and feeds both projections
+            n1q, n1s = ops.quant_rows_fp8(n1)
+            qk = ops.gemm_fp8(n1q, n1s, *d["s_qk8"], c_acc=prescale)
+            vt = ops.gemm_fp8(*d["s_v8"], n1q, n1s)                   # V^T = W_v X^T (swapped roles) -> [C, rows]
+            del n1q, n1s
+        else:
+            qk = ops.linear(n1, d["s_qk"], c_acc=prescale)
+            vt = torch.empty(C, rows, dtype=torch.float16, device=dev)
+            ops.gemm(d["s_v"], n1, vt, M=C, N=rows, c1=C, lda=C)      # V^T = W_v X^T (swapped operands)
         ao = torch.empty(rows, C, dtype=torch.float16, device=dev)
         if self.attn_log2:
             ops.attn_spatial_log2(qk, qk[:, C:], vt, ao, N, S, t.heads, 2 * C, rows, C)
@@ -620,7 +647,7 @@ class UNetSpatioTemporalConditionModel:
                             rows_per_group=S, ld_rowbias=C)
             del ffh
         n1 = ops.layernorm(hm, d["t_norm1g"], d["t_norm1b"])
-        qkv = ops.linear(n1, d["t_qkv"])
+        qkv = ops.gemm_fp8(*ops.quant_rows_fp8(n1), *d["t_qkv8"]) if "t_qkv8" in d else ops.linear(n1, d["t_qkv"])
         ops.attn_temporal(qkv, qkv[:, C:], qkv[:, 2 * C:], ao, B, T, S, t.heads, 3 * C, C)
         del qkv
         hm = ops.linear(ao, d["t_ow"], d["t_ob"], out=Res.empty(rows, C, dev, False), rowbias=cv_t, rows_per_group=T * S,

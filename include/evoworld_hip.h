@@ -27,7 +27,7 @@ typedef int ew_status;
 #define EW_ERR_UNSUPPORTED (-2)
 #define EW_ERR_HIP (-3)
 
-#define EW_ABI_VERSION 14
+#define EW_ABI_VERSION 15
 int ew_abi_version(void);
 const char* ew_last_error(void);
 
@@ -287,10 +287,22 @@ ew_status ew_vit_patchify_f16(const float* x, void* out, int N, int S, int P, in
 ew_status ew_attn_small_f16(const void* q, const void* k, const void* v, void* o, int n_seq, int S, int heads, int D, int ld,
                             int ld_o, float scale, void* stream);
 
-/* (ABI 3-9 exported ew_quant_rows_fp8 / ew_gemm_fp8: optional fp8 (OCP e4m3) q / k / v projections for BASELINE.json configs[4].  Measured slower
- * than the fp16 generation-3 GEMMs in rounds 2-4 (2062 vs 1950 ms per forward at the configs[4] size; the projections are HBM- / epilogue-bound,
- * halving operand bytes buys nothing) and 6x outside the parity tolerance: removed from the library in ABI 10 -- configs[4] runs fp16.  The
- * kernels and their test live on under tools/experiments/fp8_qkv/.) */
+/* Optional fp8 (OCP e4m3) q / k / v projections (ABI 15; BASELINE.json configs[4]: "fp16 U-Net + fp8 MFMA QKV").  Replaces, when the model is
+ * built with qkv_fp8, the Attention.to_q / to_k / to_v Linear calls of `attn1` reached from diffusers' BasicTransformerBlock and
+ * TemporalBasicTransformerBlock (instantiated through evoworld/trainer/unet_plucker.py:126-244); everything else of the blocks stays fp16.
+ * Off by default: it changes the numerics contract (tests/test_gpu_fp8_qkv.py states its tolerance) and makes no speed claim -- the non-scaled
+ * fp8 MFMA runs at the fp16 rate on gfx950, what the path halves is operand bytes.  (ABI 3-9 exported the pair without c_acc; ABI 10-14 did not
+ * export it.)
+ *   ew_quant_rows_fp8  x fp16 [rows, K] -> q e4m3 bytes [rows, K] + scale fp32 [rows]: scale = amax(row) / 448 (1 for an all-zero row),
+ *                      q = e4m3(x * (1 / scale)), round to nearest even.  K % 8 == 0, K <= 2048; x, q 16- / 8-byte aligned rows.
+ *   ew_gemm_fp8        out[m][n] = fp16((sum_k a[m][k] * w[n][k]) * a_scale[m] * w_scale[n] * c_acc), fp32 accumulation on
+ *                      v_mfma_f32_16x16x32_fp8_fp8.  a [M, K], w [N, K] e4m3 bytes (row stride K), a_scale [M], w_scale [N] fp32, out fp16 with
+ *                      row stride ld_out >= N.  c_acc: the factor ew_gemm_args.c_acc is on the fp16 path (the log2 prescale of the spatial q|k
+ *                      projection).  Swapping (a, a_scale) with (w, w_scale) gives the transposed product (V^T = W_v X^T).
+ *                      K % 64 == 0, N % 4 == 0, ld_out % 4 == 0; a, w, w_scale 16-byte aligned, out 8-byte aligned. */
+ew_status ew_quant_rows_fp8(const void* x, void* q, float* scale, int rows, int K, void* stream);
+ew_status ew_gemm_fp8(const void* a, const float* a_scale, const void* w, const float* w_scale, void* out, int M, int N, int K,
+                      long long ld_out, float c_acc, void* stream);
 
 /* Plücker embedding: out[n, 0:3, y, x] = R_n d(y,x); out[n, 3:6] = t_n x (R_n d)  (fp32).
  * rays [H,W,3] fp32, c2w [N,3,4] fp32 -> out [N,6,H,W] fp32.

@@ -26,6 +26,7 @@ CMD="unified_loop_consistency.py --unet_path $CKPT --svd_path $CKPT --base_folde
 [ "$CURVE_PATH" = true ] && CMD="$CMD --curve_path"
 [ "$RANDOM_INIT" = true ] && CMD="$CMD --random_init"
 [ -n "$STAGES" ] && CMD="$CMD --stages $STAGES"
+[ "$QKV_FP8" = 1 ] && CMD="$CMD --qkv_fp8"      # opt-in fp8 (e4m3) q / k / v projections: BASELINE.json configs[4]
 
 if [ "$NUM_GPUS" -gt 1 ]; then
   python -m torch.distributed.run --nnodes=1 --nproc-per-node "$NUM_GPUS" --master-addr 127.0.0.1 --master-port ${MASTER_PORT:-29511} $CMD

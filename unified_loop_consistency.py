@@ -8,6 +8,7 @@ Same flags as the reference.  Additions (all optional):
   --random_init              random U-Net weights of the full architecture instead of loading --unet_path
   --num_inference_steps N    (reference fixes 25)
   --height/--width           (reference fixes 576x1024)
+  --qkv_fp8                  fp8 (e4m3) q / k / v projections in the U-Net's self-attention (BASELINE.json configs[4]); default off = fp16
 
 Launch on N GPUs:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 unified_loop_consistency.py ...
 """
@@ -41,6 +42,7 @@ def parse_arguments(argv=None):
     p.add_argument("--num_inference_steps", type=int, default=25)
     p.add_argument("--height", type=int, default=576)
     p.add_argument("--width", type=int, default=1024)
+    p.add_argument("--qkv_fp8", action="store_true", help="fp8 (e4m3) q/k/v projections in the U-Net self-attention (opt-in; default fp16)")
     return p.parse_args(argv)
 
 
@@ -172,18 +174,19 @@ def main(argv=None):
     os.makedirs(args.save_dir, exist_ok=True)
     # rank 0 reads (or draws) the weights; the other ranks receive the packed set once over RCCL / xGMI
     sub = "unet" if os.path.isdir(os.path.join(args.unet_path, "unet")) else None
+    fp8 = {"qkv_fp8": True} if args.qkv_fp8 else {}      # absent: the model's own default (fp16, or what EW_QKV_FP8 says); every rank builds the same layout
     if rank == 0 or world == 1:
         if args.random_init:
-            unet = UNetSpatioTemporalConditionModel.from_random(seed=args.seed, device=dev, num_frames=args.num_frames)
+            unet = UNetSpatioTemporalConditionModel.from_random(seed=args.seed, device=dev, num_frames=args.num_frames, **fp8)
         else:
-            unet = UNetSpatioTemporalConditionModel.from_pretrained(args.unet_path, subfolder=sub, device=dev)
+            unet = UNetSpatioTemporalConditionModel.from_pretrained(args.unet_path, subfolder=sub, device=dev, **fp8)
     else:
         cfg = {"num_frames": args.num_frames}
         cj = os.path.join(args.unet_path, sub or "", "config.json")
         if not args.random_init and os.path.exists(cj):
             from evoworld_amd.unet import DEFAULT_CONFIG
             cfg = {k: (tuple(v) if isinstance(v, list) else v) for k, v in json.load(open(cj)).items() if k in DEFAULT_CONFIG}
-        unet = UNetSpatioTemporalConditionModel.from_zeros(device=dev, **cfg)
+        unet = UNetSpatioTemporalConditionModel.from_zeros(device=dev, **cfg, **fp8)
     if world > 1:
         unet.broadcast_weights(src=0)
     pipe = StableVideoDiffusionPipeline(unet=unet)
