@@ -18,28 +18,15 @@
 //   * the DMA pieces of a K-tile are issued between the MFMAs of two half-steps instead of back to back after the barrier.
 // Generation 3 (gemm3_f16.hip, 256x320 tile) is the default where it applies; this generation handles the other shapes.
 // Same argument block, same addressing modes (dense / conv3x3 / temporal 3-tap, dual source, zero page) as gen 1.
-#include "gemm_common.h"
-#include <type_traits>
+#include "gemm_gen23.h"
 
 namespace {
 
-#define EW_WAIT_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-// gfx9 s_waitcnt simm16: vmcnt[3:0]=bits3:0, expcnt=bits6:4, lgkmcnt=bits11:8, vmcnt[5:4]=bits15:14.  The BUILTIN form is
-// used for lgkmcnt so that hipcc's own waitcnt model knows the LDS queue is empty (an inline-asm wait is opaque to it).
-#define EW_WAIT_LGKM0() __builtin_amdgcn_s_waitcnt(0xC07F)
-#define EW_COMPILER_FENCE() asm volatile("" ::: "memory")
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// EPI: compile-time epilogue operand set -- bit0 row-bias, bit1 residual r1, bit2 residual r2, bit3 GEGLU.  An operand
+// EPI: compile-time epilogue operand set -- bit0 row-bias, bit1 residual r1, bit2 residual r2, bit3 GEGLU, bit4 lo8 operands.  An operand
 // that is compiled in but absent at run time is read from the zero page with stride 0 (so a superset kernel is always valid).
 template <int BM, int BN, int WAVES_M, int WAVES_N, int NSTAGE, int MODE, int EPI>
-__global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (WAVES_M * WAVES_N == 4 && BM == 256) ? 1 : 2) void gemm2_kernel(const GemmP p) {
-    constexpr int NW = WAVES_M * WAVES_N;                  // 8 waves, 1 workgroup/CU  -or-  4 waves, 2 workgroups/CU
+__global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void gemm2_kernel(const GemmP p) {
+    constexpr int NW = WAVES_M * WAVES_N;                  // 8 waves, 1 workgroup/CU
     constexpr int BK = 64;
     constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;
     constexpr int FM = WM / 16, FN = WN / 16;
@@ -49,7 +36,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (WAVES_M * WAVES_N == 4 && 
     constexpr int GB_FULL = B_GROUPS / NW;                 // W row-groups every wave owns
     constexpr int STAGE = (BM + BN) * 128;
     constexpr int A_BYTES = BM * 128;
-    static_assert((NW == 8 || NW == 4) && (WM == 64 || WM == 128) && A_GROUPS % NW == 0 && (NSTAGE == 2 || NSTAGE == 3), "config");
+    static_assert(NW == 8 && NSTAGE == 3, "only the 8-wave / 3-stage configurations are instantiated (dispatch_tile)");
+    static_assert((WM == 64 || WM == 128) && A_GROUPS % NW == 0, "config");
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x;
@@ -64,7 +52,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (WAVES_M * WAVES_N == 4 && 
     const int total_tiles = p.tiles_m * p.tiles_n;
     const int seq0 = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
     const int n_my = seq0 < total_tiles ? (total_tiles - 1 - seq0) / G + 1 : 0;
-    const int C = p.c1 + p.c2;
     const int nk = p.K / BK;
     const int V = n_my * nk;                                                     // virtual K-tile stream length
     if (V == 0) return;
@@ -81,7 +68,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (WAVES_M * WAVES_N == 4 && 
     int a_ctr[GA];                         // centre-tap pixel (row) index in the source tensors
     int a_mask[GA];                        // bits 0..8 tap validity, bits 16..27 upsample (dy,dx) codes
     const f16* b_ptr[GB];
-    constexpr int NTAP = MODE == EW_A_CONV3X3 ? 9 : (MODE == EW_A_CONVT3 ? 3 : 1);
+    constexpr int NTAP = ew_a_ntap<MODE>;
 
     auto loader_new_tile = [&]() __attribute__((always_inline)) {
         const int id = ld_i * G + seq0;
@@ -159,10 +146,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (WAVES_M * WAVES_N == 4 && 
         st_base = st_second ? p.a2 : p.a;
         st_ld = st_second ? p.lda2 : p.lda;
         st_ch = st_second ? cc - p.c1 : cc;
-        int dpix = 0;                                                       // wave-uniform tap delta in pixels
-        if constexpr (MODE == EW_A_CONV3X3) dpix = (st_tap / 3 - 1) * p.w_in + (st_tap % 3 - 1);
-        else if constexpr (MODE == EW_A_CONVT3) dpix = (st_tap - 1) * p.tP;
-        st_dl = (long long)dpix * st_ld + st_ch;
+        st_dl = (long long)ew_a_tap_delta<MODE>(p, st_tap) * st_ld + st_ch;
         st_koff = (size_t)ld_kt * BK;
         // K order is CHANNEL-CHUNK major, tap minor: the taps of one 64-channel chunk re-read (shifted) the same input
         // lines, so the chunk's footprint (~66 KB per workgroup) is fetched from HBM/MALL once and re-hit in L2 for the
@@ -204,15 +188,12 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (WAVES_M * WAVES_N == 4 && 
     // the NST output stores of the tile just finished were issued AFTER the DMA we wait for -- vmcnt counts in issue
     // order, so they are allowed to stay in flight too and the wave does not stall on store acknowledgements.
     auto wait_landed = [&](bool more_in_flight, bool stores_behind) __attribute__((always_inline)) {
-        if constexpr (NSTAGE == 2) { wait_vmcnt<0>(); return; }         // nothing newer than the tile we wait for
-        else {
-            if (!more_in_flight) { wait_vmcnt<0>(); return; }
-            if constexpr (GB > GB_FULL) {
-                if (has_tail) { if (stores_behind) { if (lo_out) wait_vmcnt<GA + GB_FULL + 1 + NST2>(); else wait_vmcnt<GA + GB_FULL + 1 + NST>(); } else wait_vmcnt<GA + GB_FULL + 1>(); }
-                else { if (stores_behind) { if (lo_out) wait_vmcnt<GA + GB_FULL + NST2>(); else wait_vmcnt<GA + GB_FULL + NST>(); } else wait_vmcnt<GA + GB_FULL>(); }
-            } else {
-                if (stores_behind) { if (lo_out) wait_vmcnt<GA + GB_FULL + NST2>(); else wait_vmcnt<GA + GB_FULL + NST>(); } else wait_vmcnt<GA + GB_FULL>();
-            }
+        if (!more_in_flight) { ew_wait_vmcnt<0>(); return; }
+        if constexpr (GB > GB_FULL) {
+            if (has_tail) { if (stores_behind) { if (lo_out) ew_wait_vmcnt<GA + GB_FULL + 1 + NST2>(); else ew_wait_vmcnt<GA + GB_FULL + 1 + NST>(); } else ew_wait_vmcnt<GA + GB_FULL + 1>(); }
+            else { if (stores_behind) { if (lo_out) ew_wait_vmcnt<GA + GB_FULL + NST2>(); else ew_wait_vmcnt<GA + GB_FULL + NST>(); } else ew_wait_vmcnt<GA + GB_FULL>(); }
+        } else {
+            if (stores_behind) { if (lo_out) ew_wait_vmcnt<GA + GB_FULL + NST2>(); else ew_wait_vmcnt<GA + GB_FULL + NST>(); } else ew_wait_vmcnt<GA + GB_FULL>();
         }
     };
 
@@ -273,16 +254,12 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (WAVES_M * WAVES_N == 4 && 
     // and the DMA is issued after the epilogue's closing barrier.
     int staged = 0;                                  // stream positions whose DMA has been issued
     for (; staged < NSTAGE && staged < V; ++staged) stage(smem + staged * STAGE);
-    if (V > 1) {
-        if constexpr (NSTAGE == 3) { if (V > 2) wait_landed(true, false); else { wait_vmcnt<0>(); } }
-        else wait_vmcnt<0>();
+    if (V > 1) {       // (two levels on purpose: collapsed to wait_landed(V > 2, false) every kernel's code changes)
+        if (V > 2) wait_landed(true, false); else ew_wait_vmcnt<0>();
     } else {
-        wait_vmcnt<0>();
+        ew_wait_vmcnt<0>();
     }
-    if constexpr (NSTAGE == 2) { /* both tiles waited: simplest, once per launch */ }
-    EW_COMPILER_FENCE();
-    __builtin_amdgcn_s_barrier();
-    EW_COMPILER_FENCE();
+    ew_block_barrier();
     read_frags(smem, so0, af0, bf0);
 
     int cur_i = 0, cur_kt = 0;
@@ -294,7 +271,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (WAVES_M * WAVES_N == 4 && 
         const char* cur = smem + s_cur * STAGE;
         const bool tile_end = cur_kt == nk - 1;
         // ---- half-step 0: MFMA on k[0,32), fetch fragments of k[32,64)
-        EW_WAIT_LGKM0();   // af0/bf0 (read one half-step ago) have landed: free, and it lets the MFMAs below start
+        ew_wait_lgkm0();   // af0/bf0 (read one half-step ago) have landed: free, and it lets the MFMAs below start
                            // without waiting for the reads issued next (hipcc otherwise emits lgkmcnt(0) after them)
         read_frags(cur, so1, af1, bf1);
         __builtin_amdgcn_sched_barrier(0);   // keep the reads AHEAD of the MFMAs (hipcc otherwise sinks them to the end)
@@ -305,10 +282,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (WAVES_M * WAVES_N == 4 && 
         // the half-step-1 MFMAs, which would expose the LDS latency of the reads just issued.
         wait_landed(v + 2 < staged, stores_behind);
         stores_behind = false;
-        EW_WAIT_LGKM0();
-        EW_COMPILER_FENCE();
-        __builtin_amdgcn_s_barrier();
-        EW_COMPILER_FENCE();
+        ew_wait_lgkm0();
+        ew_block_barrier();
         read_frags(smem + s_nxt * STAGE, so0, af0, bf0);
         const bool st_now = !tile_end && staged < V;                             // slot of v is free from here on
         if (st_now) {
@@ -483,10 +458,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (WAVES_M * WAVES_N == 4 && 
             {
                 if (stores_behind) epilogue(std::true_type{}); else epilogue(std::false_type{});
                 // the patch lives in the ring slot the NEXT DMA (stage at the top of the next position) will overwrite
-                EW_WAIT_LGKM0();
-                EW_COMPILER_FENCE();
-                __builtin_amdgcn_s_barrier();
-                EW_COMPILER_FENCE();
+                ew_wait_lgkm0();
+                ew_block_barrier();
             }
             if (staged < V) { stage(smem + s_prev * STAGE); ++staged; }   // the DMA deferred at this tile's last barrier
         }
@@ -504,7 +477,7 @@ ew_status launch2(const GemmP& p, hipStream_t s) {
     if (ew_status st = ew_ensure_dynamic_lds((const void*)gemm2_kernel<BM, BN, WAVES_M, WAVES_N, NSTAGE, MODE, EPI>, (int)lds, attr_mask)) return st;
     const long long tiles = (long long)q.tiles_m * q.tiles_n;
     if (tiles <= 0 || tiles > 0x7fffffffLL) { ew_set_error("ew_gemm_f16: bad grid"); return EW_ERR_INVALID_ARG; }
-    int grid = (NW == 8 || BM == 256) ? ew_cu_budget() : 2 * ew_cu_budget();                   // persistent: 1 x 8-wave or 2 x 4-wave workgroups per CU (256 CUs)
+    int grid = ew_cu_budget();                                             // persistent: one 8-wave workgroup per CU (256 CUs)
     if (tiles < grid) grid = (int)((tiles + 7) / 8 * 8);
     ew_gemm_note_kernel("gemm2_kernel<%d, %d, %d, %d, %d, %d, %d>", BM, BN, WAVES_M, WAVES_N, NSTAGE, MODE, EPI);
     hipLaunchKernelGGL((gemm2_kernel<BM, BN, WAVES_M, WAVES_N, NSTAGE, MODE, EPI>), dim3(grid), dim3(64 * NW), lds, s, q);
@@ -525,24 +498,10 @@ ew_status dispatch_tile(const GemmP& p, hipStream_t s) {
     }
 }
 
-// run-time EPI (ew_gemm_select_epi) -> the variants compiled for MODE
+// run-time EPI (ew_gemm_select_epi) -> the variants compiled for MODE (the list: ew_gemm_visit_variant)
 template <int MODE>
 ew_status dispatch_epi(const GemmP& p, int epi, hipStream_t s) {
-    constexpr bool D = MODE == EW_A_DENSE;
-    switch (epi) {        // (keep the order: hipcc emits the kernels in it)
-    case 8: if constexpr (D) return dispatch_tile<MODE, 8>(p, s); break;
-    case 16 | 2: if constexpr (!D) return dispatch_tile<MODE, 16 | 2>(p, s); break;
-    case 16 | 3: return dispatch_tile<MODE, 16 | 3>(p, s);
-    case 16 | 7: if constexpr (D) return dispatch_tile<MODE, 16 | 7>(p, s); break;
-    case 0: return dispatch_tile<MODE, 0>(p, s);
-    case 1: return dispatch_tile<MODE, 1>(p, s);
-    case 2: return dispatch_tile<MODE, 2>(p, s);
-    case 3: if constexpr (D) return dispatch_tile<MODE, 3>(p, s); break;
-    case 6: if constexpr (D) return dispatch_tile<MODE, 6>(p, s); break;
-    case 7: return dispatch_tile<MODE, 7>(p, s);
-    }
-    ew_set_error("ew_gemm_f16: generation 2 has no kernel <%d, %d>", MODE, epi);
-    return EW_ERR_UNSUPPORTED;
+    return ew_gemm_visit_variant<2, MODE>(epi, [&](auto e) { return dispatch_tile<MODE, decltype(e)::value>(p, s); });
 }
 
 }  // namespace

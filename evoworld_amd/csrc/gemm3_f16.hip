@@ -15,14 +15,10 @@
 //     wave-private fp32 LDS patch in two 80-column passes, as in generation 2.
 // Same argument block and A addressing modes (dense / conv3x3 / temporal 3-tap, dual source, zero page) as gen 1/2.
 // Requires N % 320 == 0 (the dispatcher falls back to generation 2 otherwise).
-#include "gemm_common.h"
-#include <type_traits>
+#include "gemm_gen23.h"
 
 namespace {
 
-#define EW3_WAIT_LGKM0() __builtin_amdgcn_s_waitcnt(0xC07F)
-#define EW3_FENCE() asm volatile("" ::: "memory")
-#define EW3_WAIT_VM0() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 #define EW3_LDS(ptr) (*(const f16x8*)(ptr))
 
 // The file is compiled twice (Makefile): EW3_BN = 320 (every channel count of the U-Net) and EW3_BN = 256 (gemm3b_f16.o: the VAE's
@@ -44,7 +40,6 @@ static_assert(BN % 64 == 0 && FN % 2 == 0 && (FM * FN) % 8 == 0, "tile geometry"
 constexpr int A_BYTES = BM * 128, STAGE = (BM + BN) * 128;
 constexpr int GA = BM / 8 / NW, GB = BN / 8 / NW, NP = GA + GB;        // 4 + 5 DMA pieces per wave per K-tile
 constexpr int NSTEP = 2 * FN;                                          // 20 steps (k-half, W fragment) per K-tile
-#define EW3_PIN() __builtin_amdgcn_sched_barrier(0)
 constexpr int ITEMS_BYTES = 8192;                                      // work-item table: up to 512 (tile, k0, k1) entries per block
 constexpr int PD = 2;                                         // W fragments are read PD steps ahead of their MFMAs (ring of 4)
 constexpr int BAR_STEP = NSTEP - 1 - PD;                               // barrier after the step that issues the tile's last read
@@ -143,7 +138,7 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm3_kernel(const GemmP p, const 
     const int slot = (lane & 7) ^ srow;
 
     // ---------------- loader state (one K-tile ahead of the MFMA stream, across output tiles) ----------------
-    constexpr int NTAP = MODE == EW_A_CONV3X3 ? 9 : (MODE == EW_A_CONVT3 ? 3 : 1);
+    constexpr int NTAP = ew_a_ntap<MODE>;
     int ld_w = 0, ld_kt = 0, ld_k1 = 0, ld_tap = 0, ld_cc = 0;   // ld_kt == ld_k1: the next stage_begin opens work item ld_w
     int a_ctr[GA];                         // centre-tap pixel (row) index in the source tensors, relative to the wave's reference pixel a_ref
     int a_mask[GA];                        // bits 0..8 tap validity, bits 16..27 upsample (dy,dx) codes
@@ -253,9 +248,7 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm3_kernel(const GemmP p, const 
         st_base = second ? p.a2 : p.a;
         st_ld = second ? p.lda2 : p.lda;
         st_ch = second ? cc - p.c1 : cc;
-        int dpix = 0;                                                       // wave-uniform tap delta in pixels
-        if constexpr (MODE == EW_A_CONV3X3) dpix = (st_tap / 3 - 1) * p.w_in + (st_tap % 3 - 1);
-        else if constexpr (MODE == EW_A_CONVT3) dpix = (st_tap - 1) * p.tP;
+        int dpix = ew_a_tap_delta<MODE>(p, st_tap);                         // wave-uniform tap delta in pixels
         if constexpr (MODE == EW_A_CONV3X3) { if (p.upsample) dpix = 0; }          // per-row deltas instead (stage_piece)
         const char* ua = (const char*)st_base + ((long long)(a_ref + dpix) * st_ld + st_ch) * 2;
         st_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)ua, 0, 0x7fffffff, 0x00020000);
@@ -341,10 +334,8 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm3_kernel(const GemmP p, const 
 #pragma unroll
     for (int k = 0; k < NP; ++k) stage_piece(k);
     int staged = 1;
-    EW3_WAIT_VM0();
-    EW3_FENCE();
-    __builtin_amdgcn_s_barrier();
-    EW3_FENCE();
+    ew_wait_vmcnt<0>();
+    ew_block_barrier();
     int cur_w = 0, cur_id, cur_kt, cur_k1;
     EW3_GET_ITEM(0, cur_id, cur_kt, cur_k1);
     cur_w = 1;
@@ -391,19 +382,17 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm3_kernel(const GemmP p, const 
             if (t < NP) {
                 if (pend_now) stage_piece(t);
             }
-            EW3_PIN();
+            ew_pin();
 #pragma unroll
             for (int i = 0; i < FM; ++i)
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bfr[t & 3], af[kh][i], acc[i][j], 0, 0, 0);   // D[n][m]
-            EW3_PIN();
+            ew_pin();
             if (t == BAR_STEP) {
                 // every fragment read of K-tile v has been issued; publish K-tile v+1 and free this slot.  Unconditional
                 // (also on the last position, where the prefetched fragments are stale and never used).
-                EW3_WAIT_VM0();
-                EW3_WAIT_LGKM0();
-                EW3_FENCE();
-                __builtin_amdgcn_s_barrier();
-                EW3_FENCE();
+                ew_wait_vmcnt<0>();
+                ew_wait_lgkm0();
+                ew_block_barrier();
             }
         }
         s_cur ^= 1;
@@ -632,6 +621,10 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm3_kernel(const GemmP p, const 
                                 else if constexpr (R1) x += p.c_r1 * (float)q1v[st][e];
                                 if constexpr (R2 && LO) x += p.c_r2 * ew_split_dec(q2v[st][e], ew_sbyte(q2l[st][e >> 2], e & 3));
                                 else if constexpr (R2) x += p.c_r2 * (float)q2v[st][e];
+                                // split output without a residual: x is a bare product, and hipcc folded it into the fp16 conversion (one rounding of
+                                // the exact product) for one of its two uses only -- near a rounding tie the stored hi and the hi the lo8 byte was
+                                // encoded against then differed by one fp16 ulp (c_acc != 1).  Keep x the fp32-rounded product for both.
+                                if constexpr (LO && !R1 && !R2) asm("" : "+v"(x));
                                 o[e] = (f16)x;
                                 if constexpr (LO) s8[e] = ew_split_enc(x, o[e]);
                             }
@@ -700,9 +693,7 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm3_kernel(const GemmP p, const 
                     // the partial of the replay and not for the stale flag of the previous run
                     __hip_atomic_store(fl, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
-                EW3_FENCE();
-                __builtin_amdgcn_s_barrier();
-                EW3_FENCE();
+                ew_block_barrier();
                 // The partial comes in through the LDS-DMA path into the stage the K loop has just released (9 KB per wave: eight
                 // 1 KB pieces in flight, no VGPRs), then one fragment at a time is read back and added: five round trips to memory,
                 // and no register demand on top of the 160 live accumulators (ten fragments in VGPRs cost <0,23> 18 more spills).
@@ -715,19 +706,19 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm3_kernel(const GemmP p, const 
                 for (int b0 = 0; b0 < FM * FN; b0 += SKU) {
 #pragma unroll
                     for (int u = 0; u < SKU; ++u) glds16((const f16*)(wsp + (b0 + u) * (64 * NW)), stg + u * 1024);
-                    EW3_WAIT_VM0();
-                    EW3_FENCE();
+                    ew_wait_vmcnt<0>();
+                    ew_fence();
 #pragma unroll
                     for (int u = 0; u < SKU; ++u) {
                         const int f = b0 + u;
                         acc[f / FN][f % FN] += *(const f32x4*)(stg + u * 1024 + lane_o * 16);
                     }
-                    EW3_WAIT_LGKM0();
-                    EW3_FENCE();
+                    ew_wait_lgkm0();
+                    ew_fence();
                 }
                 // the staging regions (8 KB per wave) overlap the other waves' epilogue patches (5.25 KB per wave) in the same stage
                 __builtin_amdgcn_s_barrier();
-                EW3_FENCE();
+                ew_fence();
             }
             if (sk_contribute) {
                 // stream-K contributor: accumulators -> slot seq0 of the uncached workspace in [fragment][thread] order (16 B per
@@ -743,18 +734,14 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm3_kernel(const GemmP p, const 
                         wsp[(i * FN + j) * (64 * NW)] = acc[i][j];
                         __builtin_amdgcn_sched_barrier(0);
                     }
-                EW3_WAIT_VM0();
-                EW3_FENCE();
-                __builtin_amdgcn_s_barrier();
-                EW3_FENCE();
+                ew_wait_vmcnt<0>();
+                ew_block_barrier();
                 if (tid == 0) __hip_atomic_store(sk.flags + seq0, sk.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             } else if constexpr (!RES_LDS) {
                 if (full) epilogue(std::true_type{}); else epilogue(std::false_type{});
                 // the patch lives in the slot the next position's DMA will overwrite
-                EW3_WAIT_LGKM0();
-                EW3_FENCE();
-                __builtin_amdgcn_s_barrier();
-                EW3_FENCE();
+                ew_wait_lgkm0();
+                ew_block_barrier();
             } else {
                 res_run = true;
             }
@@ -783,7 +770,6 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm3_kernel(const GemmP p, const 
                 char* const stage_done = smem + (s_cur ^ 1) * STAGE;      // stage just consumed (free since this position's barrier)
                 const bool deferred = pend;                               // K-tile v+1 exists and has not been staged yet
                 const bool exact = full && (!LO || p.out_lo);       // every store instruction of a fragment is issued
-#define EW3_VMCNT(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
                 auto res_phase = [&](auto phase_tag) __attribute__((always_inline)) {
                     constexpr int PH = decltype(phase_tag)::value;        // 0: fragments 0 .. FM-2 (one residual) or all (two), 1: fragment FM-1 (one residual)
                     int lane_e = tid & 63;                                // opaque copy: keeps the per-lane constants out of the main loop
@@ -878,9 +864,9 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm3_kernel(const GemmP p, const 
                             for (int i = 0; i < FM - 1; ++i) {
                                 // batch i landed?  issued after it so far: B(i+1), and the stores of fragment i-1 (between B(i) .. no: see order)
                                 // order: B0 B1 | S0 B2 | S1 B3 | S2 ...  -> newer than B(i): i == 0: B1;  i >= 1: S(i-1), B(i+1)
-                                if (i == 0 || !exact) EW3_VMCNT(BI); else EW3_VMCNT(BI + SI);
+                                if (i == 0 || !exact) ew_wait_vmcnt<BI>(); else ew_wait_vmcnt<BI + SI>();
                                 process(i);
-                                EW3_FENCE();
+                                ew_fence();
                                 if (i + 2 < FM) issue(i + 2);
                             }
                         } else {
@@ -889,27 +875,25 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm3_kernel(const GemmP p, const 
                             issue(0);
 #pragma unroll
                             for (int i = 0; i < FM; ++i) {
-                                EW3_VMCNT(0);
+                                ew_wait_vmcnt<0>();
                                 process(i);
-                                EW3_FENCE();
+                                ew_fence();
                                 if (i + 1 < FM) issue(i + 1);
                             }
                         }
                     } else if constexpr (NOPD == 1) {
                         // fragment FM-1 (its zone is in stage_done): newer than its batch are the stores of fragment FM-2 and, when staged,
                         // the 9 pieces of K-tile v+1
-                        if (exact) { if (deferred) EW3_VMCNT(SI + NP); else EW3_VMCNT(SI); }
-                        else { if (deferred) EW3_VMCNT(NP); else EW3_VMCNT(0); }
+                        if (exact) { if (deferred) ew_wait_vmcnt<SI + NP>(); else ew_wait_vmcnt<SI>(); }
+                        else { if (deferred) ew_wait_vmcnt<NP>(); else ew_wait_vmcnt<0>(); }
                         process(FM - 1);
                     }
                 };
                 if (res_run) res_phase(std::integral_constant<int, 0>{});
                 if (deferred) {
                     // every wave has read what it needs from stage_next (fragments 0 .. FM-2 done): stage K-tile v+1 there
-                    EW3_WAIT_LGKM0();
-                    EW3_FENCE();
-                    __builtin_amdgcn_s_barrier();
-                    EW3_FENCE();
+                    ew_wait_lgkm0();
+                    ew_block_barrier();
                     stage_begin(stage_next);
                     ++staged;
 #pragma unroll
@@ -917,11 +901,9 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm3_kernel(const GemmP p, const 
                 }
                 if (res_run) res_phase(std::integral_constant<int, 1>{});
                 // K-tile v+1 landed (newer: the stores of the last fragment), every wave done with its landing zones
-                if (NOPD == 1 && res_run && exact) EW3_VMCNT(SI); else EW3_WAIT_VM0();
-                EW3_WAIT_LGKM0();
-                EW3_FENCE();
-                __builtin_amdgcn_s_barrier();
-                EW3_FENCE();
+                if (NOPD == 1 && res_run && exact) ew_wait_vmcnt<SI>(); else ew_wait_vmcnt<0>();
+                ew_wait_lgkm0();
+                ew_block_barrier();
             }
             // Every path above only READS the accumulators; they are cleared here, once, for the next work item (clearing them
             // inside each path gave the allocator a three-way merge of 160 registers: copies and ~280 spilled VGPRs).
@@ -1034,25 +1016,10 @@ ew_status launch3(const Plan3& pl, hipStream_t s) {
     return ew_check_launch("ew_gemm_f16(gen3)");
 }
 
-// run-time EPI (ew_gemm_select_epi) -> the variants compiled for MODE
+// run-time EPI (ew_gemm_select_epi) -> the variants compiled for MODE (the list: ew_gemm_visit_variant)
 template <int MODE>
 ew_status dispatch_epi3(const Plan3& pl, hipStream_t s) {
-    constexpr bool D = MODE == EW_A_DENSE;
-    switch (pl.epi) {        // (keep the order: hipcc emits the kernels in it)
-    case 8: if constexpr (D) return launch3<MODE, 8>(pl, s); break;
-    case 16 | 1: return launch3<MODE, 16 | 1>(pl, s);
-    case 16 | 2: if constexpr (!D) return launch3<MODE, 16 | 2>(pl, s); break;
-    case 16 | 3: return launch3<MODE, 16 | 3>(pl, s);
-    case 16 | 7: if constexpr (D) return launch3<MODE, 16 | 7>(pl, s); break;
-    case 0: return launch3<MODE, 0>(pl, s);
-    case 1: return launch3<MODE, 1>(pl, s);
-    case 2: return launch3<MODE, 2>(pl, s);
-    case 3: if constexpr (D) return launch3<MODE, 3>(pl, s); break;
-    case 6: if constexpr (D) return launch3<MODE, 6>(pl, s); break;
-    case 7: return launch3<MODE, 7>(pl, s);
-    }
-    ew_set_error("ew_gemm_f16: generation 3 has no kernel <%d, %d>", MODE, pl.epi);
-    return EW_ERR_UNSUPPORTED;
+    return ew_gemm_visit_variant<3, MODE>(pl.epi, [&](auto e) { return launch3<MODE, decltype(e)::value>(pl, s); });
 }
 
 }  // namespace
