@@ -1,67 +1,116 @@
-"""ctypes binding of libevoworld_hip.so (the C ABI in include/evoworld_hip.h).
+"""ctypes binding of libevoworld_hip.so, derived from include/evoworld_hip.h.
+
+The header is the only description of the C ABI.  `Header` parses it once at import -- every ew_* prototype, the two argument
+structs, the EW_* defines and the enum members -- and everything the binding needs comes from that parse: argtypes / restype of
+every function (`bind`), the ctypes.Structure classes (GemmArgs, FfArgs), ABI_VERSION, the error codes and enum values (module
+attributes under their header names).  A type without a mapping raises; nothing defaults to int.
 
 The library is built in-tree by `make -C evoworld_amd/csrc` (or __graft_entry__.build()).  Loading fails
 loudly -- there is no CPU / PyTorch fallback for the product path.
 """
+import contextlib
 import ctypes
 import os
+import re
 
 import torch  # noqa: F401  MUST precede the CDLL below: torch bundles its own libamdhip64.so.7; loading ours first
 #                     would pull /opt/rocm's copy and leave two HIP runtimes in the process ("no ROCm-capable device").
-from ctypes import c_char_p, c_float, c_int, c_longlong, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EW_LIB_PATH") or os.path.join(_HERE, "libevoworld_hip.so")   # EW_LIB_PATH: another build of the same ABI (A/B tools)
-ABI_VERSION = 15
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "evoworld_hip.h")
 
-# every symbol declared in include/evoworld_hip.h
-SYMBOLS = [
-    "ew_abi_version", "ew_last_error", "ew_gemm_f16", "ew_set_gemm_generation", "ew_get_gemm_generation", "ew_set_gemm_debug", "ew_gemm_last_kernel", "ew_gemm_streamk_status", "ew_gemm_streamk_init", "ew_ff_geglu320_f16", "ew_groupnorm_workspace_floats", "ew_groupnorm_stats_f16", "ew_groupnorm_finalize", "ew_groupnorm_apply_f16",
-    "ew_layernorm_f16", "ew_attn_spatial_f16", "ew_attn_spatial_log2_f16", "ew_attn_temporal_f16", "ew_nchw_f32_to_nhwc_f16",
-    "ew_nhwc_f16_to_nchw_f32", "ew_softmax_rows_f16", "ew_time_conv3_f32", "ew_euler_cfg_step", "ew_plucker_embed", "ew_cube2equi_gather",
-    "ew_depth_unproject", "ew_select_workspace_bytes", "ew_select_kth_f32", "ew_filter_compact_workspace_bytes",
-    "ew_filter_compact", "ew_splat_cubemap", "ew_splat_resolve", "ew_equi2pers", "ew_resize_aa_u8",
-    "ew_u8_hwc_to_f32_chw", "ew_f32_chw_to_u8_hwc", "ew_blur_axis_f32", "ew_bicubic_resize_f32", "ew_vit_patchify_f16",
-    "ew_attn_small_f16",
-    "ew_set_cu_budget", "ew_get_cu_budget", "ew_stream_create_cu_mask", "ew_stream_destroy",
-    "ew_nchw_f32_to_nhwc_split_f16", "ew_euler_cfg_step_split", "ew_groupnorm_apply_split_f16", "ew_sinusoid_embed_f16",
-    "ew_pano_yaw_rotate",
-    "ew_video_metrics_workspace_bytes", "ew_video_metrics", "ew_gt_dump_map_u8",
-    "ew_equi2cube_u8",
-    "ew_im2col_f16", "ew_maxpool3s2_relu_f16", "ew_lpips_head_workspace_bytes", "ew_lpips_head",
-    "ew_quant_rows_fp8", "ew_gemm_fp8",
-]
-
-
-class GemmArgs(ctypes.Structure):
-    """struct ew_gemm_args (include/evoworld_hip.h)."""
-    _fields_ = [
-        ("a", c_void_p), ("a2", c_void_p), ("w", c_void_p), ("bias", c_void_p), ("rowbias", c_void_p),
-        ("r1", c_void_p), ("r2", c_void_p), ("out", c_void_p), ("zero_page", c_void_p),
-        ("M", c_int), ("N", c_int), ("c1", c_int), ("c2", c_int), ("lda", c_int), ("lda2", c_int),
-        ("ld_out", c_int), ("ld_r1", c_int), ("ld_r2", c_int), ("ld_rowbias", c_int), ("mode", c_int),
-        ("n_img", c_int), ("h_in", c_int), ("w_in", c_int), ("h_out", c_int), ("w_out", c_int),
-        ("stride", c_int), ("upsample", c_int), ("tB", c_int), ("tT", c_int), ("tP", c_int),
-        ("rows_per_group", c_int), ("act", c_int), ("c_acc", c_float), ("c_r1", c_float), ("c_r2", c_float),
-        ("r1_lo", c_void_p), ("r2_lo", c_void_p), ("out_lo", c_void_p), ("conv_shift", c_int),
-    ]
-
-
-class FfArgs(ctypes.Structure):
-    """struct ew_ff_args (include/evoworld_hip.h)."""
-    _fields_ = [
-        ("x", c_void_p), ("w1p", c_void_p), ("b1p", c_void_p), ("w2p", c_void_p), ("b2", c_void_p), ("rowbias", c_void_p),
-        ("r1", c_void_p), ("r1_lo", c_void_p), ("r2", c_void_p), ("r2_lo", c_void_p), ("out", c_void_p), ("out_lo", c_void_p),
-        ("zero_page", c_void_p), ("M", c_int), ("C", c_int), ("hidden", c_int), ("rows_per_group", c_int), ("ld_rowbias", c_int),
-        ("c_acc", c_float), ("c_r1", c_float), ("c_r2", c_float),
-    ]
-
-
-_lib = None
+_SCALARS = {"int": ctypes.c_int, "ew_status": ctypes.c_int, "unsigned": ctypes.c_uint, "long long": ctypes.c_longlong,
+            "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double}
 
 
 class EvoWorldHipError(RuntimeError):
     pass
+
+
+def strip_comments(text):
+    return re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+
+
+def _typed_name(decl):
+    """'const void* a' -> ('const void*', 'a'): the C type normalised to single spaces with '*' attached to it"""
+    m = re.fullmatch(r"(.*[\s*])(\w+)", decl.strip(), flags=re.S)
+    if not m:
+        raise EvoWorldHipError(f"evoworld_hip.h: cannot read the declaration '{decl.strip()}'")
+    return re.sub(r"\s*\*\s*", "*", " ".join(m.group(1).split())), m.group(2)
+
+
+class Header:
+    """The parse of evoworld_hip.h.  As C text: `functions` {name: (return type, [parameter types])} and `struct_fields`
+    {struct: [(type, field)]}; `constants` {EW_*: int} (defines and enum members); as ctypes: `structs` {struct: Structure class}
+    and `signatures` {name: (restype, argtypes)}."""
+
+    def __init__(self, text):
+        text = strip_comments(text)
+        self.constants = {k: int(v) for k, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(EW_\w+)[ \t]+\(?[ \t]*(-?\d+)[ \t]*\)?[ \t]*$", text, flags=re.M)}
+        for body in re.findall(r"\benum\s*\{([^}]*)\}", text):
+            for member in filter(None, (s.strip() for s in body.split(","))):
+                m = re.fullmatch(r"(\w+)\s*=\s*(-?\d+)", member)
+                if not m:
+                    raise EvoWorldHipError(f"evoworld_hip.h: enum member '{member}' has no explicit integer value")
+                self.constants[m.group(1)] = int(m.group(2))
+        text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+        self.struct_fields, self.structs = {}, {}
+        for name, body, alias in re.findall(r"\btypedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;", text, flags=re.S):
+            if alias != name:
+                raise EvoWorldHipError(f"evoworld_hip.h: struct {name} is typedef'd to another name ({alias})")
+            fields = []
+            for decl in filter(None, (s.strip() for s in body.split(";"))):
+                first, *more = decl.split(",")
+                ctype, field = _typed_name(first)
+                if more and "*" in ctype or not all(re.fullmatch(r"\s*\w+\s*", s) for s in more):
+                    raise EvoWorldHipError(f"evoworld_hip.h: cannot read the declarators of '{decl}' in struct {name}")
+                fields += [(ctype, f.strip()) for f in (field, *more)]
+            self.struct_fields[name] = fields
+            self.structs[name] = type("".join(p.title() for p in name.split("_")[1:]), (ctypes.Structure,),
+                                      {"_fields_": [(f, self.ctype(t)) for t, f in fields], "__doc__": f"struct {name} (include/evoworld_hip.h)."})
+        self.functions, self.signatures = {}, {}
+        for ret, name, params in re.findall(r"(?:\A|(?<=[;{}]))\s*([\w\s*]+?)\s*\b(ew_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+            ret = re.sub(r"\s*\*\s*", "*", " ".join(ret.split()))
+            types = [] if params.strip() == "void" else [_typed_name(p)[0] for p in params.split(",")]
+            self.functions[name] = (ret, types)
+            self.signatures[name] = (self.ctype(ret, ret=True), [self.ctype(t) for t in types])
+        unread = set(re.findall(r"\b(ew_[a-z0-9_]+)\s*\(", text)) - set(self.functions)
+        if unread:
+            raise EvoWorldHipError(f"evoworld_hip.h: cannot read the prototype of {sorted(unread)}")
+
+    def ctype(self, t, ret=False):
+        """C type text -> ctypes type"""
+        if t.endswith("*"):
+            base = t[:-1].replace("const ", "").strip()
+            if ret and base == "char":
+                return ctypes.c_char_p
+            return ctypes.POINTER(self.structs[base]) if base in self.structs else ctypes.c_void_p
+        if ret and t == "void":
+            return None
+        if t not in _SCALARS:
+            raise EvoWorldHipError(f"evoworld_hip.h: no ctypes mapping for the type '{t}'")
+        return _SCALARS[t]
+
+
+with open(HEADER_PATH) as _f:
+    HEADER = Header(_f.read())
+globals().update(HEADER.constants)                      # EW_OK, EW_ERR_*, EW_A_*, EW_ACT_*, EW_IM2COL_*, EW_ABI_VERSION
+ABI_VERSION = HEADER.constants["EW_ABI_VERSION"]
+GemmArgs, FfArgs = HEADER.structs["ew_gemm_args"], HEADER.structs["ew_ff_args"]
+
+_lib = None
+
+
+def bind(cdll):
+    """Set restype / argtypes of every function the header declares on `cdll` (any build of the library); returns it."""
+    for name, (restype, argtypes) in HEADER.signatures.items():
+        try:
+            fn = getattr(cdll, name)
+        except AttributeError:
+            raise EvoWorldHipError(f"{cdll._name} does not export {name}") from None
+        fn.restype, fn.argtypes = restype, argtypes
+    return cdll
 
 
 def load():
@@ -73,88 +122,25 @@ def load():
         raise EvoWorldHipError(
             f"{LIB_PATH} not found: build it with `make -C evoworld_amd/csrc` (hipcc --offload-arch=gfx950). "
             "evoworld_amd has no CPU fallback.")
-    lib = ctypes.CDLL(LIB_PATH)
-    for s in SYMBOLS:       # (EW_LIB_PATH: another BUILD of the same ABI -- A/B of two compilations in one gpurun call; older ABIs are refused)
-        if not hasattr(lib, s):
-            raise EvoWorldHipError(f"{LIB_PATH} does not export {s}")
-    lib.ew_last_error.restype = c_char_p
-    lib.ew_gemm_last_kernel.restype = c_char_p
-    lib.ew_abi_version.restype = c_int
+    lib = bind(ctypes.CDLL(LIB_PATH))       # (EW_LIB_PATH: another BUILD of the same ABI -- A/B of two compilations in one process; older ABIs are refused)
     if lib.ew_abi_version() != ABI_VERSION:
         raise EvoWorldHipError(f"ABI mismatch: library {lib.ew_abi_version()} != binding {ABI_VERSION}")
-    P, I, F, LL = c_void_p, c_int, c_float, c_longlong
-    sig = {
-        "ew_gemm_f16": [ctypes.POINTER(GemmArgs), P],
-        "ew_groupnorm_stats_f16": [P, P, P, I, I, I, I, I, I, P],
-        "ew_groupnorm_finalize": [P, I, I, I, I, P],
-        "ew_groupnorm_apply_f16": [P, P, P, P, P, P, I, I, I, I, I, I, F, I, P],
-        "ew_groupnorm_apply_split_f16": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, I, P],
-        "ew_gemm_streamk_init": [P],
-        "ew_ff_geglu320_f16": [ctypes.POINTER(FfArgs), P],
-        "ew_layernorm_f16": [P, P, P, I, P, P, P, P, P, I, I, F, P],
-        "ew_attn_spatial_f16": [P, P, P, P, I, I, I, I, LL, I, F, P],
-        "ew_attn_spatial_log2_f16": [P, P, P, P, I, I, I, I, LL, I, P],
-        "ew_attn_temporal_f16": [P, P, P, P, I, I, I, I, I, I, F, P],
-        "ew_nchw_f32_to_nhwc_f16": [P, P, I, I, I, I, I, I, F, P],
-        "ew_nhwc_f16_to_nchw_f32": [P, P, I, I, I, I, I, P],
-        "ew_euler_cfg_step": [P, I, P, P, F, F, P, I, I, I, I, P],
-        "ew_nchw_f32_to_nhwc_split_f16": [P, P, I, I, I, I, I, I, I, I, F, P],
-        "ew_euler_cfg_step_split": [P, I, P, P, F, F, P, I, I, I, I, I, I, P],
-        "ew_sinusoid_embed_f16": [P, I, I, I, P, P],
-        "ew_softmax_rows_f16": [P, P, P, LL, I, LL, P],
-        "ew_time_conv3_f32": [P, P, P, P, I, I, I, I, P],
-        "ew_plucker_embed": [P, P, P, I, I, I, P],
-        "ew_cube2equi_gather": [P, I, P, P, I, I, I, I, P],
-        "ew_select_kth_f32": [P, c_size_t, c_size_t, P, P, P],
-        "ew_filter_compact": [P, c_size_t, F, P, P, I, ctypes.c_uint, P, P, P, P, P],
-        "ew_depth_unproject": [P, P, P, P, I, I, I, P],
-        "ew_splat_cubemap": [P, c_size_t, P, P, I, I, F, F, F, F, F, P],
-        "ew_splat_resolve": [P, P, I, P, I, I, I, P],
-        "ew_equi2pers": [P, P, P, I, I, I, I, I, F, P],
-        "ew_resize_aa_u8": [P, P, P, P, P, I, P, P, I, I, I, I, I, I, P],
-        "ew_u8_hwc_to_f32_chw": [P, P, I, I, I, P],
-        "ew_f32_chw_to_u8_hwc": [P, P, I, I, I, P],
-        "ew_pano_yaw_rotate": [P, I, P, P, I, I, I, P],
-        "ew_video_metrics": [P, P, I, I, I, I, I, I, P, P, P, P],
-        "ew_gt_dump_map_u8": [P, P, c_size_t, P],
-        "ew_equi2cube_u8": [P, P, I, I, I, I, P],
-        "ew_im2col_f16": [P, I, P, I, I, I, I, I, I, I, I, I, I, I, I, ctypes.POINTER(c_float), P],
-        "ew_maxpool3s2_relu_f16": [P, P, I, I, I, I, I, I, P],
-        "ew_lpips_head": [P, P, P, P, P, I, I, I, I, ctypes.c_double, P, P, P],
-        "ew_quant_rows_fp8": [P, P, P, I, I, P],
-        "ew_gemm_fp8": [P, P, P, P, P, I, I, I, LL, F, P],
-        "ew_blur_axis_f32": [P, P, I, P, LL, I, I, I, P],
-        "ew_bicubic_resize_f32": [P, P, I, I, I, I, I, I, P, P, P],
-        "ew_vit_patchify_f16": [P, P, I, I, I, I, P],
-        "ew_attn_small_f16": [P, P, P, P, I, I, I, I, I, I, F, P],
-    }
-    lib.ew_groupnorm_workspace_floats.argtypes = [c_int, c_int, c_int, c_int]
-    lib.ew_groupnorm_workspace_floats.restype = c_size_t
-    lib.ew_select_workspace_bytes.argtypes = []
-    lib.ew_select_workspace_bytes.restype = c_size_t
-    lib.ew_filter_compact_workspace_bytes.argtypes = [c_size_t]
-    lib.ew_filter_compact_workspace_bytes.restype = c_size_t
-    lib.ew_video_metrics_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
-    lib.ew_video_metrics_workspace_bytes.restype = c_size_t
-    lib.ew_lpips_head_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
-    lib.ew_lpips_head_workspace_bytes.restype = c_size_t
-    lib.ew_set_gemm_generation.argtypes = [c_int]
-    lib.ew_set_gemm_generation.restype = None
-    lib.ew_get_gemm_generation.restype = c_int
-    lib.ew_gemm_streamk_status.argtypes = []
-    lib.ew_gemm_streamk_status.restype = c_int
-    lib.ew_set_gemm_debug.argtypes = [c_int]
-    lib.ew_set_gemm_debug.restype = None
-    lib.ew_set_cu_budget.argtypes, lib.ew_set_cu_budget.restype = [c_int], c_int
-    lib.ew_get_cu_budget.argtypes, lib.ew_get_cu_budget.restype = [], c_int
-    lib.ew_stream_create_cu_mask.argtypes, lib.ew_stream_create_cu_mask.restype = [c_int, c_int], c_void_p
-    lib.ew_stream_destroy.argtypes, lib.ew_stream_destroy.restype = [c_void_p], c_int
-    for name, argtypes in sig.items():
-        fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = c_int
     _lib = lib
     return lib
+
+
+@contextlib.contextmanager
+def using(lib):
+    """Inside the block load() returns `lib` -- another build of the same ABI, already bound (`bind`) -- so that every ops.* call
+    goes to it; the previous library is back on exit, also after an exception."""
+    global _lib
+    if lib.ew_abi_version() != ABI_VERSION:
+        raise EvoWorldHipError(f"ABI mismatch: library {lib.ew_abi_version()} != binding {ABI_VERSION}")
+    keep, _lib = _lib, lib
+    try:
+        yield lib
+    finally:
+        _lib = keep
 
 
 def check(status, what):

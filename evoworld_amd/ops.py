@@ -1,5 +1,7 @@
 """Thin tensor->pointer wrappers over the C ABI (include/evoworld_hip.h).  torch is used only for device
-memory and the current HIP stream; every op below is one hand-written HIP kernel launch.  No fallback."""
+memory and the current HIP stream; every op below is one hand-written HIP kernel launch.  No fallback.
+Signatures, argument structs and enum values come from the header through _lib's parse of it; every launch goes through
+`_call`, which passes the arguments positionally in the prototype's order with the current stream last."""
 import ctypes
 
 import torch
@@ -7,8 +9,8 @@ import torch
 from . import _lib
 from ._lib import GemmArgs
 
-A_DENSE, A_CONV3X3, A_CONVT3 = 0, 1, 2
-ACT_NONE, ACT_SILU, ACT_GEGLU, ACT_GELU = 0, 1, 2, 3
+A_DENSE, A_CONV3X3, A_CONVT3 = _lib.EW_A_DENSE, _lib.EW_A_CONV3X3, _lib.EW_A_CONVT3
+ACT_NONE, ACT_SILU, ACT_GEGLU, ACT_GELU = _lib.EW_ACT_NONE, _lib.EW_ACT_SILU, _lib.EW_ACT_GEGLU, _lib.EW_ACT_GELU
 
 _zero_pages = {}
 
@@ -19,6 +21,13 @@ def _stream():
 
 def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _call(name, *args):
+    """The one path into the library for the ew_status entry points: name(*args, current stream), raising on a status != 0.
+    The function is looked up on the library object at every call, so that a wrapper set on it (bench.py's per-kernel timers)
+    or another build (_lib.using) takes effect."""
+    _lib.check(getattr(_lib.load(), name)(*args, _stream()), name)
 
 
 def _aligned(t, n=16):
@@ -91,7 +100,6 @@ def gemm(a, w, out, *, M, N, c1, lda, a2=None, c2=0, lda2=0, bias=None, rowbias=
     """out = c_acc*act(A@W^T + bias + rowbias) + c_r1*r1 + c_r2*r2  (see ew_gemm_f16).
     conv = (n_img, h_in, w_in, h_out, w_out, stride, upsample); tconv = (B, T, P); conv_shift=1: padding (0,1) taps.
     r1 / r2 / out may be `Res` (split-fp16 residual stream): the lo halves ride along (ew_gemm_args.r1_lo ...)."""
-    lib = _lib.load()
     g = GemmArgs()
     r1h, r1l = _hl(r1)
     r2h, r2l = _hl(r2)
@@ -111,7 +119,7 @@ def gemm(a, w, out, *, M, N, c1, lda, a2=None, c2=0, lda2=0, bias=None, rowbias=
     g.rows_per_group, g.act = rows_per_group, act
     g.c_acc, g.c_r1, g.c_r2 = c_acc, c_r1, c_r2
     g.conv_shift = conv_shift
-    _lib.check(lib.ew_gemm_f16(ctypes.byref(g), _stream()), "ew_gemm_f16")
+    _call("ew_gemm_f16", ctypes.byref(g))
     return out
 
 
@@ -180,9 +188,6 @@ class WorkspacePool:
         return v
 
 
-SumsPool = WorkspacePool   # former name
-
-
 def groupnorm(xs, gamma, beta, n_slabs, rows, eps, silu, groups=32, out=None, pool=None, stats_hi_only=False, split_out=False):
     """GroupNorm(+SiLU) over the channel concat of `xs` (list of [n_slabs*rows, C_i] fp16 tensors or `Res`) ->
     [n_slabs*rows, sum C_i] fp16.  Deterministic shifted statistics: stats per source, one finalize, apply per source.
@@ -195,47 +200,39 @@ def groupnorm(xs, gamma, beta, n_slabs, rows, eps, silu, groups=32, out=None, po
     ws = pool.take(nws) if pool is not None else torch.empty(nws, dtype=torch.float32, device=dev)
     if out is None:
         out = torch.empty(n_slabs * rows, 2 * C_tot if split_out else C_tot, dtype=torch.float16, device=dev)
-    st = _stream()
     off = 0
     for h, l in srcs:
         # stats_hi_only (off): statistics from the hi half alone would save the lo read of this pass (2.3 ms per forward), but
         # the rounding remainders add ulp^2/12 to the variance -- 0.5 % when a channel's std is ~4 fp16 ulps of its mean
         # (mean/std = 300), i.e. exactly the cancellation-prone inputs the shifted statistics exist for
-        _lib.check(lib.ew_groupnorm_stats_f16(_ptr(h), None if stats_hi_only else _ptr(l), _ptr(ws), n_slabs, rows, h.shape[-1],
-                                              off, C_tot, groups, st), "ew_groupnorm_stats_f16")
+        _call("ew_groupnorm_stats_f16", _ptr(h), None if stats_hi_only else _ptr(l), _ptr(ws), n_slabs, rows, h.shape[-1], off, C_tot, groups)
         off += h.shape[-1]
-    _lib.check(lib.ew_groupnorm_finalize(_ptr(ws), n_slabs, rows, C_tot, groups, st), "ew_groupnorm_finalize")
+    _call("ew_groupnorm_finalize", _ptr(ws), n_slabs, rows, C_tot, groups)
     off = 0
     for h, l in srcs:
         if split_out:
-            _lib.check(lib.ew_groupnorm_apply_split_f16(_ptr(h), _ptr(l), _ptr(ws), _ptr(gamma), _ptr(beta), _ptr(out), _ptr(out[:, C_tot:]),
-                                                        2 * C_tot, n_slabs, rows, h.shape[-1], off, C_tot, groups, eps, 1 if silu else 0, st),
-                       "ew_groupnorm_apply_split_f16")
+            _call("ew_groupnorm_apply_split_f16", _ptr(h), _ptr(l), _ptr(ws), _ptr(gamma), _ptr(beta), _ptr(out), _ptr(out[:, C_tot:]),
+                  2 * C_tot, n_slabs, rows, h.shape[-1], off, C_tot, groups, eps, 1 if silu else 0)
         else:
-            _lib.check(lib.ew_groupnorm_apply_f16(_ptr(h), _ptr(l), _ptr(ws), _ptr(gamma), _ptr(beta), _ptr(out), n_slabs, rows,
-                                                  h.shape[-1], off, C_tot, groups, eps, 1 if silu else 0, st),
-                       "ew_groupnorm_apply_f16")
+            _call("ew_groupnorm_apply_f16", _ptr(h), _ptr(l), _ptr(ws), _ptr(gamma), _ptr(beta), _ptr(out), n_slabs, rows,
+                  h.shape[-1], off, C_tot, groups, eps, 1 if silu else 0)
         off += h.shape[-1]
     return out
 
 
 def layernorm(x, gamma, beta, eps=1e-5, addvec=None, rows_per_group=1, x_out=None, out=None):
     """x, x_out: fp16 tensors or `Res` (split-fp16 residual stream)."""
-    lib = _lib.load()
     xh, xl = _hl(x)
     oh, ol = _hl(x_out)
     rows, C = xh.shape
     if out is None:
         out = torch.empty_like(xh)
-    _lib.check(lib.ew_layernorm_f16(_ptr(xh), _ptr(xl), _ptr(addvec), rows_per_group, _ptr(oh), _ptr(ol), _ptr(gamma),
-                                    _ptr(beta), _ptr(out), rows, C, eps, _stream()), "ew_layernorm_f16")
+    _call("ew_layernorm_f16", _ptr(xh), _ptr(xl), _ptr(addvec), rows_per_group, _ptr(oh), _ptr(ol), _ptr(gamma), _ptr(beta), _ptr(out), rows, C, eps)
     return out
 
 
 def attn_spatial(q, k, vt, o, n_seq, S, heads, ld_qk, ld_vt, ld_o, scale=0.125):
-    lib = _lib.load()
-    _lib.check(lib.ew_attn_spatial_f16(_ptr(q), _ptr(k), _ptr(vt), _ptr(o), n_seq, S, heads, ld_qk, ld_vt, ld_o, scale,
-                                       _stream()), "ew_attn_spatial_f16")
+    _call("ew_attn_spatial_f16", _ptr(q), _ptr(k), _ptr(vt), _ptr(o), n_seq, S, heads, ld_qk, ld_vt, ld_o, scale)
     return o
 
 
@@ -244,23 +241,20 @@ QK_LOG2_PRESCALE = (0.125 * 1.4426950408889634) ** 0.5    # sqrt(head_dim^-0.5 *
 
 def attn_spatial_log2(q, k, vt, o, n_seq, S, heads, ld_qk, ld_vt, ld_o):
     """q, k pre-scaled by QK_LOG2_PRESCALE each (projection epilogue): the kernel's MFMA subtracts the running max itself."""
-    lib = _lib.load()
-    _lib.check(lib.ew_attn_spatial_log2_f16(_ptr(q), _ptr(k), _ptr(vt), _ptr(o), n_seq, S, heads, ld_qk, ld_vt, ld_o, _stream()),
-               "ew_attn_spatial_log2_f16")
+    _call("ew_attn_spatial_log2_f16", _ptr(q), _ptr(k), _ptr(vt), _ptr(o), n_seq, S, heads, ld_qk, ld_vt, ld_o)
     return o
 
 
 def quant_rows_fp8(x):
     """x fp16 [rows, K] -> (q uint8 [rows, K] holding OCP e4m3 bytes, scale fp32 [rows]): scale = amax(row) / 448 (1 for an all-zero
     row), q = e4m3(x / scale) (ew_quant_rows_fp8).  K % 8 == 0, K <= 2048."""
-    lib = _lib.load()
     _req(x, torch.float16, "x")
     if x.ndim != 2:
         raise ValueError(f"x: expected fp16 [rows, K], got {tuple(x.shape)}")
     rows, K = x.shape
     q = torch.empty(rows, K, dtype=torch.uint8, device=x.device)
     scale = torch.empty(rows, dtype=torch.float32, device=x.device)
-    _lib.check(lib.ew_quant_rows_fp8(_ptr(x), _ptr(q), _ptr(scale), rows, K, _stream()), "ew_quant_rows_fp8")
+    _call("ew_quant_rows_fp8", _ptr(x), _ptr(q), _ptr(scale), rows, K)
     return q, scale
 
 
@@ -268,7 +262,6 @@ def gemm_fp8(aq, a_scale, wq, w_scale, out=None, c_acc=1.0):
     """aq [M, K], wq [N, K] e4m3 bytes (uint8), a_scale [M], w_scale [N] fp32 -> fp16 [M, N] = (aq wq^T) * a_scale[m] * w_scale[n] * c_acc
     (ew_gemm_fp8).  `out`: an fp16 [M, N] tensor or view with unit column stride to write into (its row stride is ld_out).
     Swapping the (bytes, scale) pairs gives the transposed product.  K % 64 == 0, N % 4 == 0."""
-    lib = _lib.load()
     _req(aq, torch.uint8, "aq"); _req(wq, torch.uint8, "wq"); _req(a_scale, torch.float32, "a_scale"); _req(w_scale, torch.float32, "w_scale")
     if aq.ndim != 2 or wq.ndim != 2 or aq.shape[1] != wq.shape[1]:
         raise ValueError(f"aq {tuple(aq.shape)} / wq {tuple(wq.shape)}: expected [M, K] and [N, K]")
@@ -280,99 +273,85 @@ def gemm_fp8(aq, a_scale, wq, w_scale, out=None, c_acc=1.0):
         out = torch.empty(M, N, dtype=torch.float16, device=aq.device)
     if out.dtype != torch.float16 or out.device != aq.device or tuple(out.shape) != (M, N) or out.stride(1) != 1:
         raise ValueError(f"out: expected an fp16 [{M}, {N}] device tensor with unit column stride, got {out.dtype} {tuple(out.shape)} strides {out.stride()}")
-    _lib.check(lib.ew_gemm_fp8(_ptr(aq), _ptr(a_scale), _ptr(wq), _ptr(w_scale), _ptr(out), M, N, K, out.stride(0), float(c_acc), _stream()),
-               "ew_gemm_fp8")
+    _call("ew_gemm_fp8", _ptr(aq), _ptr(a_scale), _ptr(wq), _ptr(w_scale), _ptr(out), M, N, K, out.stride(0), float(c_acc))
     return out
 
 
 def attn_temporal(q, k, v, o, B, T, S, heads, ld, ld_o, scale=0.125):
-    lib = _lib.load()
-    _lib.check(lib.ew_attn_temporal_f16(_ptr(q), _ptr(k), _ptr(v), _ptr(o), B, T, S, heads, ld, ld_o, scale, _stream()),
-               "ew_attn_temporal_f16")
+    _call("ew_attn_temporal_f16", _ptr(q), _ptr(k), _ptr(v), _ptr(o), B, T, S, heads, ld, ld_o, scale)
     return o
 
 
 def softmax_rows(scores, out=None):
     """scores: fp16 [R, C] tensor or `Res` (hi + lo) -> fp16 softmax over the last dim (fp32 math)."""
-    lib = _lib.load()
     h, l = _hl(scores)
     R, C = h.shape
     if out is None:
         out = torch.empty_like(h)
-    _lib.check(lib.ew_softmax_rows_f16(_ptr(h), _ptr(l), _ptr(out), R, C, C, _stream()), "ew_softmax_rows_f16")
+    _call("ew_softmax_rows_f16", _ptr(h), _ptr(l), _ptr(out), R, C, C)
     return out
 
 
 def time_conv3(x, w, bias):
     """x fp32 [B,T,C,H,W], w fp32 [C,C,3], bias fp32 [C] -> fp32 [B,T,C,H,W] (Conv3d (3,1,1), zero padding in T)."""
-    lib = _lib.load()
     _req(x, torch.float32, "x"); _req(w, torch.float32, "w"); _req(bias, torch.float32, "bias")
     B, T, C, H, W = x.shape
     y = torch.empty_like(x)
-    _lib.check(lib.ew_time_conv3_f32(_ptr(x), _ptr(w), _ptr(bias), _ptr(y), B, T, C, H * W, _stream()), "ew_time_conv3_f32")
+    _call("ew_time_conv3_f32", _ptr(x), _ptr(w), _ptr(bias), _ptr(y), B, T, C, H * W)
     return y
 
 
 def sinusoid_embed(vals, n_rows, dim):
     """vals fp32 device [n] -> fp16 [n_rows, dim] = [cos | sin] sinusoidal embedding of vals[row % n] (ew_sinusoid_embed_f16)."""
-    lib = _lib.load()
     _req(vals, torch.float32, "vals")
     out = torch.empty(n_rows, dim, dtype=torch.float16, device=vals.device)
-    _lib.check(lib.ew_sinusoid_embed_f16(_ptr(vals), vals.numel(), n_rows, dim, _ptr(out), _stream()), "ew_sinusoid_embed_f16")
+    _call("ew_sinusoid_embed_f16", _ptr(vals), vals.numel(), n_rows, dim, _ptr(out))
     return out
 
 
 def nchw_f32_to_nhwc_f16(x, y, ldc, c_off=0, scale=1.0, split=None):
     """split = (lo_off, dup_off): the row also receives fp16(v - hi) at lo_off + c_off + c and hi again at dup_off + c_off + c
     (ew_nchw_f32_to_nhwc_split_f16: the [x_hi | x_lo | x_hi] A operand of a conv_in packed [W_hi | W_hi | W_lo])."""
-    lib = _lib.load()
     _req(x, torch.float32, "x"); _req(y, torch.float16, "y")
     N, C, H, W = x.shape
     if split:
-        _lib.check(lib.ew_nchw_f32_to_nhwc_split_f16(_ptr(x), _ptr(y), N, C, H, W, ldc, c_off, split[0], split[1], scale, _stream()),
-                   "ew_nchw_f32_to_nhwc_split_f16")
+        _call("ew_nchw_f32_to_nhwc_split_f16", _ptr(x), _ptr(y), N, C, H, W, ldc, c_off, split[0], split[1], scale)
         return y
-    _lib.check(lib.ew_nchw_f32_to_nhwc_f16(_ptr(x), _ptr(y), N, C, H, W, ldc, c_off, scale, _stream()),
-               "ew_nchw_f32_to_nhwc_f16")
+    _call("ew_nchw_f32_to_nhwc_f16", _ptr(x), _ptr(y), N, C, H, W, ldc, c_off, scale)
     return y
 
 
 def nhwc_f16_to_nchw_f32(x, N, C, H, W, ldc):
-    lib = _lib.load()
     _req(x, torch.float16, "x")
     y = torch.empty(N, C, H, W, dtype=torch.float32, device=x.device)
-    _lib.check(lib.ew_nhwc_f16_to_nchw_f32(_ptr(x), _ptr(y), N, C, H, W, ldc, _stream()), "ew_nhwc_f16_to_nchw_f32")
+    _call("ew_nhwc_f16_to_nchw_f32", _ptr(x), _ptr(y), N, C, H, W, ldc)
     return y
 
 
 def euler_cfg_step(eps, ld_eps, latents, guidance, sigma, sigma_next, next_in, cpad, T, h, w, split=None):
-    lib = _lib.load()
     _req(latents, torch.float32, "latents"); _req(guidance, torch.float32, "guidance")
     if split:
-        _lib.check(lib.ew_euler_cfg_step_split(_ptr(eps), ld_eps, _ptr(latents), _ptr(guidance), float(sigma), float(sigma_next),
-                                               _ptr(next_in), cpad, split[0], split[1], T, h, w, _stream()), "ew_euler_cfg_step_split")
+        _call("ew_euler_cfg_step_split", _ptr(eps), ld_eps, _ptr(latents), _ptr(guidance), float(sigma), float(sigma_next),
+              _ptr(next_in), cpad, split[0], split[1], T, h, w)
         return
-    _lib.check(lib.ew_euler_cfg_step(_ptr(eps), ld_eps, _ptr(latents), _ptr(guidance), float(sigma), float(sigma_next),
-                                     _ptr(next_in), cpad, T, h, w, _stream()), "ew_euler_cfg_step")
+    _call("ew_euler_cfg_step", _ptr(eps), ld_eps, _ptr(latents), _ptr(guidance), float(sigma), float(sigma_next), _ptr(next_in), cpad, T, h, w)
 
 
 def plucker_embed(rays, c2w):
-    lib = _lib.load()
     _req(rays, torch.float32, "rays"); _req(c2w, torch.float32, "c2w")
     H, W, _ = rays.shape
     N = c2w.shape[0]
     out = torch.empty(N, 6, H, W, dtype=torch.float32, device=rays.device)
-    _lib.check(lib.ew_plucker_embed(_ptr(rays), _ptr(c2w), _ptr(out), N, H, W, _stream()), "ew_plucker_embed")
+    _call("ew_plucker_embed", _ptr(rays), _ptr(c2w), _ptr(out), N, H, W)
     return out
 
 
 def cube2equi_gather(faces, lut, H, W):
     """faces uint8 [V,6,res,res,3|4] (order right,left,bottom,top,front,back), lut int16 [H,W,3] -> uint8 [V,H,W,3]."""
-    lib = _lib.load()
     _req(faces, torch.uint8, "faces"); _req(lut, torch.int16, "lut")
     V, res, ch = faces.shape[0], faces.shape[2], faces.shape[-1]
     pano = torch.empty(V, H, W, 3, dtype=torch.uint8, device=faces.device)
-    _lib.check(lib.ew_cube2equi_gather(_ptr(faces), ch, _ptr(lut), _ptr(pano), V, H, W, res, _stream()), "ew_cube2equi_gather")
+    _call("ew_cube2equi_gather", _ptr(faces), ch, _ptr(lut), _ptr(pano), V, H, W, res)
     return pano
 
 
@@ -380,7 +359,6 @@ def equi2cube(panos, interpolation=True, out=None):
     """Equirectangular panoramas uint8 [V,H,W,3] (W == 2H, W % 4 == 0) -> the reference's cube cross uint8 [V,3W/4,W,3]
     (Navigator.convert_panorama_to_cubemap's transform, navigator_evoworld.py:537-659): bilinear with truncation, or nearest
     with interpolation=False.  One launch for all V.  `out`: a contiguous uint8 [V,3W/4,W,3] tensor to write into."""
-    lib = _lib.load()
     _req(panos, torch.uint8, "panos")
     if panos.ndim != 4 or panos.shape[3] != 3:
         raise ValueError(f"panos: expected uint8 [V,H,W,3], got {tuple(panos.shape)}")
@@ -390,7 +368,7 @@ def equi2cube(panos, interpolation=True, out=None):
     _req(out, torch.uint8, "out")
     if tuple(out.shape) != (V, 3 * (W // 4), W, 3):
         raise ValueError(f"out: expected {(V, 3 * (W // 4), W, 3)}, got {tuple(out.shape)}")
-    _lib.check(lib.ew_equi2cube_u8(_ptr(panos), _ptr(out), V, H, W, int(bool(interpolation)), _stream()), "ew_equi2cube_u8")
+    _call("ew_equi2cube_u8", _ptr(panos), _ptr(out), V, H, W, int(bool(interpolation)))
     return out
 
 
@@ -420,7 +398,7 @@ def select_kth(x, k):
     _req(x, torch.float32, "x")
     ws = torch.empty(lib.ew_select_workspace_bytes() // 4 + 4, dtype=torch.int32, device=x.device)
     out = torch.empty(2, dtype=torch.float32, device=x.device)
-    _lib.check(lib.ew_select_kth_f32(_ptr(x), x.numel(), int(k), _ptr(ws), _ptr(out), _stream()), "ew_select_kth_f32")
+    _call("ew_select_kth_f32", _ptr(x), x.numel(), int(k), _ptr(ws), _ptr(out))
     return out
 
 
@@ -436,27 +414,23 @@ def filter_compact(conf, thr, xyz, img, img_nchw_hw=0):
     out_rgbx = torch.empty(n, 4, dtype=torch.uint8, device=dev)
     ws = torch.empty(lib.ew_filter_compact_workspace_bytes(n) // 4 + 1, dtype=torch.int32, device=dev)
     total = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(lib.ew_filter_compact(_ptr(conf), n, float(thr), _ptr(xyz), _ptr(img), 1 if img_nchw_hw else 0,
-                                     int(img_nchw_hw), _ptr(out_xyz), _ptr(out_rgbx), _ptr(ws), _ptr(total), _stream()),
-               "ew_filter_compact")
+    _call("ew_filter_compact", _ptr(conf), n, float(thr), _ptr(xyz), _ptr(img), 1 if img_nchw_hw else 0, int(img_nchw_hw),
+          _ptr(out_xyz), _ptr(out_rgbx), _ptr(ws), _ptr(total))
     m = int(total.item())
     return out_xyz[:m], out_rgbx[:m]
 
 
 def depth_unproject(depth, extr, intr):
-    lib = _lib.load()
     _req(depth, torch.float32, "depth"); _req(extr, torch.float32, "extr"); _req(intr, torch.float32, "intr")
     S, H, W = depth.shape
     xyz = torch.empty(S, H, W, 3, dtype=torch.float32, device=depth.device)
-    _lib.check(lib.ew_depth_unproject(_ptr(depth), _ptr(extr), _ptr(intr), _ptr(xyz), S, H, W, _stream()),
-               "ew_depth_unproject")
+    _call("ew_depth_unproject", _ptr(depth), _ptr(extr), _ptr(intr), _ptr(xyz), S, H, W)
     return xyz
 
 
 def splat_cubemap(xyz, rgb, w2c, res, fx, fy, cx, cy, z_near, face_channels=3):
     """xyz [N,3] f32, rgb u8 [N,3] (packed) or [N,4] (RGBX words, possibly a [:, :3] view of one), w2c [V,6,3,4] f32 ->
     faces u8 [V,6,res,res,face_channels], zbuf u64-as-int64 [V,6,res,res]."""
-    lib = _lib.load()
     xyz = _aligned(xyz)
     _req(xyz, torch.float32, "xyz"); _req(w2c, torch.float32, "w2c")
     if rgb.dtype != torch.uint8 or rgb.device.type != "cuda":
@@ -467,52 +441,45 @@ def splat_cubemap(xyz, rgb, w2c, res, fx, fy, cx, cy, z_near, face_channels=3):
         rgb, stride = rgb.contiguous(), 3
     V = w2c.shape[0]
     zbuf = torch.empty((V, 6, res, res), dtype=torch.int64, device=xyz.device)     # initialised by ew_splat_cubemap itself (0xFFFF... = no fragment)
-    _lib.check(lib.ew_splat_cubemap(_ptr(xyz), xyz.shape[0], _ptr(w2c), _ptr(zbuf), V, res, fx, fy, cx, cy, z_near,
-                                    _stream()), "ew_splat_cubemap")
+    _call("ew_splat_cubemap", _ptr(xyz), xyz.shape[0], _ptr(w2c), _ptr(zbuf), V, res, fx, fy, cx, cy, z_near)
     faces = torch.empty(V, 6, res, res, face_channels, dtype=torch.uint8, device=xyz.device)
-    _lib.check(lib.ew_splat_resolve(_ptr(zbuf), _ptr(rgb), stride, _ptr(faces), face_channels, V, res, _stream()),
-               "ew_splat_resolve")
+    _call("ew_splat_resolve", _ptr(zbuf), _ptr(rgb), stride, _ptr(faces), face_channels, V, res)
     return faces, zbuf
 
 
 def equi2pers(equi, rot, Hp, Wp, fov_x):
-    lib = _lib.load()
     _req(equi, torch.uint8, "equi"); _req(rot, torch.float32, "rot")
     F_, He, We, _ = equi.shape
     out = torch.empty(F_, Hp, Wp, 3, dtype=torch.uint8, device=equi.device)
-    _lib.check(lib.ew_equi2pers(_ptr(equi), _ptr(rot), _ptr(out), F_, He, We, Hp, Wp, float(fov_x), _stream()), "ew_equi2pers")
+    _call("ew_equi2pers", _ptr(equi), _ptr(rot), _ptr(out), F_, He, We, Hp, Wp, float(fov_x))
     return out
 
 
 def resize_aa_u8(src, coeffs_h, coeffs_v, Ho, Wo):
     """src uint8 [V,Hi,Wi,3]; coeffs_* = (kk int32 [n_out,ksize], bounds int32 [n_out,2]) device tensors -> uint8 [V,Ho,Wo,3]."""
-    lib = _lib.load()
     _req(src, torch.uint8, "src")
     V, Hi, Wi, _ = src.shape
     tmp = torch.empty(V, Hi, Wo, 3, dtype=torch.uint8, device=src.device)
     dst = torch.empty(V, Ho, Wo, 3, dtype=torch.uint8, device=src.device)
     (kh, bh), (kv, bv) = coeffs_h, coeffs_v
-    _lib.check(lib.ew_resize_aa_u8(_ptr(src), _ptr(tmp), _ptr(dst), _ptr(kh), _ptr(bh), kh.shape[1], _ptr(kv), _ptr(bv),
-                                   kv.shape[1], V, Hi, Wi, Ho, Wo, _stream()), "ew_resize_aa_u8")
+    _call("ew_resize_aa_u8", _ptr(src), _ptr(tmp), _ptr(dst), _ptr(kh), _ptr(bh), kh.shape[1], _ptr(kv), _ptr(bv), kv.shape[1], V, Hi, Wi, Ho, Wo)
     return dst
 
 
 def u8_hwc_to_f32_chw(src):
-    lib = _lib.load()
     _req(src, torch.uint8, "src")
     V, H, W, _ = src.shape
     dst = torch.empty(V, 3, H, W, dtype=torch.float32, device=src.device)
-    _lib.check(lib.ew_u8_hwc_to_f32_chw(_ptr(src), _ptr(dst), V, H, W, _stream()), "ew_u8_hwc_to_f32_chw")
+    _call("ew_u8_hwc_to_f32_chw", _ptr(src), _ptr(dst), V, H, W)
     return dst
 
 
 def f32_chw_to_u8_hwc(src):
     """fp32 [V,3,H,W] in [-1,1] -> uint8 [V,H,W,3] (round-half-even of clamp(x/2+0.5,0,1)*255: the pipeline's PIL frames)."""
-    lib = _lib.load()
     _req(src, torch.float32, "src")
     V, _, H, W = src.shape
     dst = torch.empty(V, H, W, 3, dtype=torch.uint8, device=src.device)
-    _lib.check(lib.ew_f32_chw_to_u8_hwc(_ptr(src), _ptr(dst), V, H, W, _stream()), "ew_f32_chw_to_u8_hwc")
+    _call("ew_f32_chw_to_u8_hwc", _ptr(src), _ptr(dst), V, H, W)
     return dst
 
 
@@ -520,7 +487,6 @@ def pano_yaw_rotate(src, yaw_deg):
     """Yaw rotation of equirectangular panoramas (Navigator.rotate_panorama, navigator_evoworld.py:466-512), bit-exact:
     src fp32 [V,3,H,W] or uint8 [V,H,W,3] (the 8-bit frames; mapped x/255*2-1 in the same pass), yaw_deg [V] degrees (a float32
     tensor on any device, or numbers rounded to float32 as torch.tensor(..., dtype=float32) does) -> fp32 [V,3,H,W]."""
-    lib = _lib.load()
     if src.dtype == torch.uint8:
         _req(src, torch.uint8, "src")
         if src.ndim != 4 or src.shape[3] != 3:
@@ -537,8 +503,7 @@ def pano_yaw_rotate(src, yaw_deg):
     if yaw.numel() != V:
         raise ValueError(f"yaw_deg: expected {V} yaws (one per panorama), got {yaw.numel()}")
     dst = torch.empty(V, 3, H, W, dtype=torch.float32, device=src.device)
-    _lib.check(lib.ew_pano_yaw_rotate(_ptr(src), int(src.dtype == torch.uint8), _ptr(yaw), _ptr(dst), V, H, W, _stream()),
-               "ew_pano_yaw_rotate")
+    _call("ew_pano_yaw_rotate", _ptr(src), int(src.dtype == torch.uint8), _ptr(yaw), _ptr(dst), V, H, W)
     return dst
 
 
@@ -578,18 +543,16 @@ def video_metrics(a, b, what=METRIC_SSE | METRIC_SSIM, sse=None, ssim=None):
                 raise ValueError(f"{name}: expected {F_} values, got {t.numel()}")
         out.append(t if what & flag else None)
     ws = torch.empty(max(1, lib.ew_video_metrics_workspace_bytes(F_, C, H, W)), dtype=torch.uint8, device=a.device)
-    _lib.check(lib.ew_video_metrics(_ptr(a), _ptr(b), layout, F_, C, H, W, int(what), _ptr(out[0]), _ptr(out[1]), _ptr(ws), _stream()),
-               "ew_video_metrics")
+    _call("ew_video_metrics", _ptr(a), _ptr(b), layout, F_, C, H, W, int(what), _ptr(out[0]), _ptr(out[1]), _ptr(ws))
     return out[0], out[1]
 
 
 def gt_dump_map_u8(src):
     """The 8-bit ground-truth frame the reference's episode mode dumps (ew_gt_dump_map_u8: k/255 -> x*2-1 -> tensor_to_pil's
     truncating (x*0.5+0.5)*255, a fixed 256-entry map): uint8 tensor of any shape (device) -> a new one of the same shape."""
-    lib = _lib.load()
     _req(src, torch.uint8, "src")
     dst = torch.empty_like(src)
-    _lib.check(lib.ew_gt_dump_map_u8(_ptr(src), _ptr(dst), src.numel(), _stream()), "ew_gt_dump_map_u8")
+    _call("ew_gt_dump_map_u8", _ptr(src), _ptr(dst), src.numel())
     return dst
 
 
@@ -602,7 +565,6 @@ def im2col(src, k, stride, pad, ldk, relu=False, first=None):
     relu: read max(x, 0)) -> fp16 [n*h_out*w_out, ldk], column (ky*k + kx)*C + c, zero beyond k*k*C.  first = (shift[3], scale[3],
     swap_rb): src is a batch of frames in [0,1], uint8 [n,h,w,3] or fp32 [n,3,h,w], mapped 2v - 1 -> (x - shift) / scale on the way
     (network channel c reads frame channel 2 - c when swap_rb).  Returns (rows, h_out, w_out)."""
-    lib = _lib.load()
     affine, swap = None, 0
     if first is None:
         _req(src, torch.float16, "src")
@@ -627,21 +589,19 @@ def im2col(src, k, stride, pad, ldk, relu=False, first=None):
     if ho < 1 or wo < 1:
         raise ValueError(f"im2col: a {k}x{k} window (pad {pad}) does not fit {h}x{w}")
     out = torch.empty(n * ho * wo, ldk, dtype=torch.float16, device=src.device)
-    _lib.check(lib.ew_im2col_f16(_ptr(src), kind, _ptr(out), n, h, w, C, k, stride, pad, ho, wo, ldk, int(bool(relu)), int(bool(swap)),
-                                 affine, _stream()), "ew_im2col_f16")
+    _call("ew_im2col_f16", _ptr(src), kind, _ptr(out), n, h, w, C, k, stride, pad, ho, wo, ldk, int(bool(relu)), int(bool(swap)), affine)
     return out, ho, wo
 
 
 def maxpool3s2_relu(x):
     """MaxPool2d(3, 2) of max(x, 0) (ew_maxpool3s2_relu_f16): fp16 NHWC [n,h,w,C], C % 8 == 0 -> [n, (h-3)//2+1, (w-3)//2+1, C]."""
-    lib = _lib.load()
     _req(x, torch.float16, "x")
     if x.ndim != 4 or x.shape[1] < 3 or x.shape[2] < 3:
         raise ValueError(f"x: expected fp16 [n,h,w,C] with h, w >= 3, got {tuple(x.shape)}")
     n, h, w, C = x.shape
     ho, wo = (h - 3) // 2 + 1, (w - 3) // 2 + 1
     out = torch.empty(n, ho, wo, C, dtype=torch.float16, device=x.device)
-    _lib.check(lib.ew_maxpool3s2_relu_f16(_ptr(x), _ptr(out), n, h, w, C, ho, wo, _stream()), "ew_maxpool3s2_relu_f16")
+    _call("ew_maxpool3s2_relu_f16", _ptr(x), _ptr(out), n, h, w, C, ho, wo)
     return out
 
 
@@ -658,46 +618,38 @@ def lpips_head(fa, fb, lin, wy, wx, n_out, acc):
         raise ValueError(f"lpips_head: lin / wy / wx / acc hold {lin.numel()}, {wy.numel()}, {wx.numel()}, {acc.numel()} values for "
                          f"C, h, w, F = {C}, {h}, {w}, {F_}")
     ws = torch.empty(max(1, lib.ew_lpips_head_workspace_bytes(F_, h, w, C)), dtype=torch.uint8, device=fa.device)
-    _lib.check(lib.ew_lpips_head(_ptr(fa), _ptr(fb), _ptr(lin), _ptr(wy), _ptr(wx), F_, h, w, C, float(n_out), _ptr(acc), _ptr(ws), _stream()),
-               "ew_lpips_head")
+    _call("ew_lpips_head", _ptr(fa), _ptr(fb), _ptr(lin), _ptr(wy), _ptr(wx), F_, h, w, C, float(n_out), _ptr(acc), _ptr(ws))
     return acc
 
 
 def blur_axis(x, kern, axis):
     """x fp32 [..., H, W], kern fp32 [k] -> correlation along H (axis 0) or W (axis 1), reflect padding."""
-    lib = _lib.load()
     _req(x, torch.float32, "x"); _req(kern, torch.float32, "kern")
     H, W = x.shape[-2:]
     out = torch.empty_like(x)
-    _lib.check(lib.ew_blur_axis_f32(_ptr(x), _ptr(kern), kern.numel(), _ptr(out), x.numel() // (H * W), H, W, axis, _stream()),
-               "ew_blur_axis_f32")
+    _call("ew_blur_axis_f32", _ptr(x), _ptr(kern), kern.numel(), _ptr(out), x.numel() // (H * W), H, W, axis)
     return out
 
 
 def bicubic_resize(x, Ho, Wo, scale=None, shift=None):
     """x fp32 [N,C,H,W] -> [N,C,Ho,Wo], bicubic align_corners=True; optional per-channel out = v*scale[c] + shift[c]."""
-    lib = _lib.load()
     _req(x, torch.float32, "x")
     N, C, H, W = x.shape
     out = torch.empty(N, C, Ho, Wo, dtype=torch.float32, device=x.device)
-    _lib.check(lib.ew_bicubic_resize_f32(_ptr(x), _ptr(out), N, C, H, W, Ho, Wo, _ptr(scale), _ptr(shift), _stream()),
-               "ew_bicubic_resize_f32")
+    _call("ew_bicubic_resize_f32", _ptr(x), _ptr(out), N, C, H, W, Ho, Wo, _ptr(scale), _ptr(shift))
     return out
 
 
 def vit_patchify(x, P, ldk):
-    lib = _lib.load()
     _req(x, torch.float32, "x")
     N, _, S, _ = x.shape
     out = torch.empty(N * (S // P) ** 2, ldk, dtype=torch.float16, device=x.device)
-    _lib.check(lib.ew_vit_patchify_f16(_ptr(x), _ptr(out), N, S, P, ldk, _stream()), "ew_vit_patchify_f16")
+    _call("ew_vit_patchify_f16", _ptr(x), _ptr(out), N, S, P, ldk)
     return out
 
 
 def attn_small(q, k, v, o, n_seq, S, heads, D, ld, ld_o, scale):
-    lib = _lib.load()
-    _lib.check(lib.ew_attn_small_f16(_ptr(q), _ptr(k), _ptr(v), _ptr(o), n_seq, S, heads, D, ld, ld_o, float(scale), _stream()),
-               "ew_attn_small_f16")
+    _call("ew_attn_small_f16", _ptr(q), _ptr(k), _ptr(v), _ptr(o), n_seq, S, heads, D, ld, ld_o, float(scale))
     return o
 
 
@@ -734,7 +686,6 @@ def ff_pack(w1, b1, w2):
 def ff_geglu320(x, pack, b2, out, *, rowbias=None, rows_per_group=1, ld_rowbias=None, r1=None, r2=None, c_acc=1.0, c_r1=1.0, c_r2=1.0):
     """out = c_acc * (GEGLU(x W1^T + b1) W2^T + b2 + rowbias) + c_r1 * r1 + c_r2 * r2 for 320-channel tokens, one kernel
     (ew_ff_geglu320_f16): x fp16 [M, 320] (the LayerNorm output), pack = ff_pack(...); r1 / r2 / out tensors or `Res`."""
-    lib = _lib.load()
     _req(x, torch.float16, "x")
     a = _lib.FfArgs()
     r1h, r1l = _hl(r1)
@@ -748,7 +699,7 @@ def ff_geglu320(x, pack, b2, out, *, rowbias=None, rows_per_group=1, ld_rowbias=
     a.rows_per_group = rows_per_group
     a.ld_rowbias = ld_rowbias if ld_rowbias is not None else x.shape[1]
     a.c_acc, a.c_r1, a.c_r2 = c_acc, c_r1, c_r2
-    _lib.check(lib.ew_ff_geglu320_f16(ctypes.byref(a), _stream()), "ew_ff_geglu320_f16")
+    _call("ew_ff_geglu320_f16", ctypes.byref(a))
     return out
 
 

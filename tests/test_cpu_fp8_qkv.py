@@ -71,7 +71,10 @@ def test_abi_version_at_least_15():
     from evoworld_amd import _lib
     version = int(re.search(r"#define EW_ABI_VERSION (\d+)", _header()).group(1))
     assert version >= 15 and version == _lib.ABI_VERSION
-    assert "ew_quant_rows_fp8" in _lib.SYMBOLS and "ew_gemm_fp8" in _lib.SYMBOLS
+    lib = _lib.load()
+    for s in ("ew_quant_rows_fp8", "ew_gemm_fp8"):
+        assert s in _lib.HEADER.functions, s
+        assert (getattr(lib, s).restype, list(getattr(lib, s).argtypes)) == _lib.HEADER.signatures[s], s
 
 
 def test_cli_flag_defaults_off():

@@ -1,6 +1,10 @@
-"""-m 'not gpu': host logic + the C-ABI library loads and exports every symbol include/evoworld_hip.h declares."""
+"""-m 'not gpu': host logic + the binding derived from include/evoworld_hip.h: the parse against the C compiler, the struct layouts,
+and the library exports and binds every function the header declares."""
+import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -9,31 +13,113 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_library_exports_every_declared_symbol():
+def _clang():
+    """the C compiler of the ROCm toolchain the Makefile builds with (next to hipcc)"""
+    hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    clang = os.path.join(os.path.dirname(hipcc), "amdclang")
+    if not os.path.exists(clang):
+        pytest.fail(f"{clang} not found: the ROCm toolchain that builds the library is needed")
+    return clang
+
+
+def _compile(tmp_path, source, *flags):
+    src = tmp_path / "abi_check.c"
+    src.write_text(source)
+    r = subprocess.run([_clang(), "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), *flags, str(src)],
+                       capture_output=True, text=True, cwd=tmp_path)
+    assert r.returncode == 0, r.stderr
+
+
+def test_parsed_prototypes_compile_against_the_header(tmp_path):
+    """The compiler checks the parser: one function-pointer typedef per function, rendered from the PARSED return and parameter
+    types and initialised with the declared function -- a misread type is an incompatible-pointer error."""
     from evoworld_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "evoworld_hip.h")).read()
-    declared = set(re.findall(r"\b(ew_[a-z0-9_]+)\s*\(", hdr)) - {"ew_gemm_args"}
-    assert declared == set(_lib.SYMBOLS), declared ^ set(_lib.SYMBOLS)
+    lines = ['#include "evoworld_hip.h"']
+    for name, (ret, params) in _lib.HEADER.functions.items():
+        lines.append(f"typedef {ret} (*fp_{name})({', '.join(params) or 'void'});")
+        lines.append(f"fp_{name} p_{name} = &{name};")
+    _compile(tmp_path, "\n".join(lines) + "\n", "-fsyntax-only")
+
+
+def test_struct_layout_matches_the_compiler(tmp_path):
+    """sizeof / offsetof of both argument structs (and the size of every mapped scalar type) as a compiled host program prints
+    them, against the generated ctypes classes."""
+    from evoworld_amd import _lib
+    H = _lib.HEADER
+    assert set(H.structs) == {"ew_gemm_args", "ew_ff_args"} and _lib.GemmArgs is H.structs["ew_gemm_args"] and _lib.FfArgs is H.structs["ew_ff_args"]
+    out = ['#include <stdio.h>', '#include "evoworld_hip.h"', "int main(void) {"]
+    for s, fields in H.struct_fields.items():
+        out.append(f'    printf("{s} %zu\\n", sizeof({s}));')
+        out += [f'    printf("{s}.{f} %zu\\n", offsetof({s}, {f}));' for _, f in fields]
+    out += [f'    printf("scalar:{t} %zu\\n", sizeof({t}));' for t in _lib._SCALARS]
+    _compile(tmp_path, "\n".join(out + ["    return 0;", "}"]) + "\n", "-o", "abi_check")
+    r = subprocess.run([str(tmp_path / "abi_check")], capture_output=True, text=True, check=True)
+    got = {k: int(v) for k, v in (line.rsplit(" ", 1) for line in r.stdout.splitlines())}
+    want = {f"scalar:{t}": ctypes.sizeof(c) for t, c in _lib._SCALARS.items()}
+    for s, cls in H.structs.items():
+        assert [f for f, _ in cls._fields_] == [f for _, f in H.struct_fields[s]]
+        want[s] = ctypes.sizeof(cls)
+        want.update({f"{s}.{f}": getattr(cls, f).offset for f, _ in cls._fields_})
+    assert got == want
+    assert len(H.struct_fields["ew_gemm_args"]) == 39 and len(H.struct_fields["ew_ff_args"]) == 21     # multi-declarator lines included
+
+
+def test_every_prototype_in_the_header_is_parsed():
+    from evoworld_amd import _lib
+    hdr = _lib.strip_comments(open(_lib.HEADER_PATH).read())
+    assert os.path.samefile(_lib.HEADER_PATH, os.path.join(ROOT, "include", "evoworld_hip.h"))
+    assert len(_lib.HEADER.functions) == len(set(re.findall(r"ew_[a-z0-9_]+\s*\(", hdr)))
+
+
+def test_library_exports_and_binds_every_declared_function():
+    from evoworld_amd import _lib
+    H = _lib.HEADER
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    for name in H.functions:
+        assert hasattr(raw, name), name
     lib = _lib.load()
-    for s in declared:
-        assert hasattr(lib, s), s
-    assert lib.ew_abi_version() == _lib.ABI_VERSION
+    assert lib.ew_abi_version() == H.constants["EW_ABI_VERSION"] == _lib.ABI_VERSION
+    assert (_lib.EW_OK, _lib.EW_ERR_INVALID_ARG, _lib.EW_ERR_UNSUPPORTED, _lib.EW_ERR_HIP) == (0, -1, -2, -3)
+    for name, (restype, argtypes) in H.signatures.items():
+        fn = getattr(lib, name)
+        assert fn.restype == restype and list(fn.argtypes) == argtypes, name
+    # a few by hand: 64-bit strides and sizes, the struct pointers, the non-status returns
+    LL, I, P, F = ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_float
+    assert list(lib.ew_softmax_rows_f16.argtypes) == [P, P, P, LL, I, LL, P]
+    assert list(lib.ew_gemm_fp8.argtypes) == [P, P, P, P, P, I, I, I, LL, F, P]
+    assert lib.ew_splat_cubemap.argtypes[1] is ctypes.c_size_t and lib.ew_filter_compact.argtypes[6] is ctypes.c_uint
+    assert lib.ew_lpips_head.argtypes[9] is ctypes.c_double
+    assert list(lib.ew_gemm_f16.argtypes) == [ctypes.POINTER(_lib.GemmArgs), P] and lib.ew_gemm_f16.restype is I
+    assert lib.ew_last_error.restype is ctypes.c_char_p and lib.ew_set_gemm_debug.restype is None
+    assert lib.ew_select_workspace_bytes.restype is ctypes.c_size_t and lib.ew_stream_create_cu_mask.restype is P
+    with pytest.raises(_lib.EvoWorldHipError, match="does not export ew_abi_version"):
+        _lib.bind(ctypes.CDLL(None))
 
 
-def test_gemm_args_struct_matches_header():
-    from evoworld_amd._lib import GemmArgs
-    hdr = open(os.path.join(ROOT, "include", "evoworld_hip.h")).read()
-    body = hdr[hdr.index("typedef struct ew_gemm_args {"):hdr.index("} ew_gemm_args;")]
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split("{", 1)[1].split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        parts = decl.replace("*", " ").split(",")
-        names.append(parts[0].split()[-1])
-        names += [p.strip() for p in parts[1:]]
-    assert names == [f[0] for f in GemmArgs._fields_]
+@pytest.mark.parametrize("text", ["short ew_f(int a);", "ew_status ew_f(short a, void* stream);", "ew_status ew_f(unsigned long n);",
+                                  "typedef struct ew_s { int a; short b; } ew_s;", "int ew_f(void), ew_g(void);"])
+def test_parser_raises_on_what_it_cannot_map(text):
+    from evoworld_amd import _lib
+    with pytest.raises(_lib.EvoWorldHipError):
+        _lib.Header(text)
+
+
+def test_using_restores_the_previous_library():
+    from evoworld_amd import _lib
+    lib = _lib.load()
+    other = _lib.bind(ctypes.CDLL(_lib.LIB_PATH))              # a second object over the same build
+    assert other is not lib
+    with _lib.using(other) as got:
+        assert got is other and _lib.load() is other
+        with _lib.using(lib):
+            assert _lib.load() is lib
+        assert _lib.load() is other
+    assert _lib.load() is lib
+    with pytest.raises(KeyError):
+        with _lib.using(other):
+            assert _lib.load() is other
+            raise KeyError("inside")
+    assert _lib.load() is lib
 
 
 def test_ops_refuse_cpu_tensors():

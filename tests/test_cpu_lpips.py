@@ -160,11 +160,13 @@ def test_abi_declares_the_lpips_entries():
     hdr = open(os.path.join(ROOT, "include", "evoworld_hip.h")).read()
     for s in ("ew_im2col_f16", "ew_maxpool3s2_relu_f16", "ew_lpips_head", "ew_lpips_head_workspace_bytes"):
         assert re.search(r"\b%s\s*\(" % s, hdr), s
-        assert s in _lib.SYMBOLS, s
+        assert s in _lib.HEADER.functions, s
     version = int(re.search(r"#define EW_ABI_VERSION (\d+)", hdr).group(1))
     assert version == _lib.ABI_VERSION and version >= 14
     lib = _lib.load()
     assert lib.ew_abi_version() == version
+    for s in ("ew_im2col_f16", "ew_maxpool3s2_relu_f16", "ew_lpips_head", "ew_lpips_head_workspace_bytes"):
+        assert (getattr(lib, s).restype, list(getattr(lib, s).argtypes)) == _lib.HEADER.signatures[s], s
     # the workspace of the head: 8 bytes per (frame, block), a block count that depends on the tap alone
     one = lib.ew_lpips_head_workspace_bytes(1, 143, 255, 64)
     assert one > 0 and one % 8 == 0 and lib.ew_lpips_head_workspace_bytes(7, 143, 255, 64) == 7 * one

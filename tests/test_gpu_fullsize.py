@@ -4,8 +4,6 @@ U-Net; reprojection with ~5 M points into 24 x 6 x 512^2 faces), where the fp32 
   * batch independence: the CFG halves do not see each other (B=2 forward == two B=1 forwards);
   * the splat is deterministic and order-independent (64-bit atomicMin on depth|index), and idempotent under duplicated points.
 Tolerances for the U-Net: 5e-3 rel-L2 = two realisations of the fp16 rounding-noise floor."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -33,7 +31,6 @@ def test_unet_full_size_two_kernel_families_agree(full):
     from evoworld_amd import _lib
     unet, x, ehs, ids, (B, T, h, w) = full
     lib = _lib.load()
-    lib.ew_set_gemm_generation.argtypes = [ctypes.c_int]
     try:
         lib.ew_set_gemm_generation(3)
         a = unet.forward_nhwc(x, 1.234, ehs, ids, B, T, h, w).float().cpu()

@@ -30,7 +30,6 @@ def ops():
 def lib():
     from evoworld_amd import _lib
     L = _lib.load()
-    L.ew_set_gemm_generation.argtypes = [ctypes.c_int]
     yield L
     L.ew_set_gemm_generation(3)
 
@@ -277,13 +276,7 @@ def test_reslds_epilogue_matches_register_operand_build(ops, lib, case, streamk)
     alt_path = os.path.join(os.path.dirname(_lib.LIB_PATH), "libevoworld_hip_reslds0.so")
     if not os.path.exists(alt_path):
         pytest.fail(f"{alt_path} missing: run `make -C evoworld_amd/csrc reslds0` (or __graft_entry__.build())")
-    alt = ctypes.CDLL(alt_path)
-    alt.ew_gemm_f16.argtypes, alt.ew_gemm_f16.restype = [ctypes.POINTER(_lib.GemmArgs), ctypes.c_void_p], ctypes.c_int
-    alt.ew_last_error.restype = ctypes.c_char_p
-    alt.ew_gemm_last_kernel.restype = ctypes.c_char_p
-    alt.ew_set_gemm_debug.argtypes = [ctypes.c_int]
-    alt.ew_gemm_streamk_init.argtypes, alt.ew_gemm_streamk_init.restype = [ctypes.c_void_p], ctypes.c_int
-    alt.ew_gemm_streamk_status.restype = ctypes.c_int
+    alt = _lib.bind(ctypes.CDLL(alt_path))
     g = torch.Generator().manual_seed(17)
     r = lambda *sh: (torch.rand(*sh, generator=g) * 2 - 1)
     kw = {}
@@ -318,17 +311,14 @@ def test_reslds_epilogue_matches_register_operand_build(ops, lib, case, streamk)
         out = ops.Res.empty(M, N, DEV, True)
         out.hi.fill_(5.0); out.lo.fill_(1)
         L.ew_set_gemm_debug(0 if streamk else 4)
-        keep = _lib._lib
-        _lib._lib = L                                    # ops.gemm fills the ew_gemm_args struct; the call goes to library L
         try:
-            ops.gemm(a, w, out, bias=bias, r1=r1, ld_r1=N, **kw)
-            name = L.ew_gemm_last_kernel().decode()
+            with _lib.using(L):                          # ops.gemm fills the ew_gemm_args struct; the call goes to library L
+                ops.gemm(a, w, out, bias=bias, r1=r1, ld_r1=N, **kw)
+                name = L.ew_gemm_last_kernel().decode()
         finally:
-            _lib._lib = keep
             L.ew_set_gemm_debug(0)
         torch.cuda.synchronize()
         return out, name
-    lib.ew_set_gemm_debug.argtypes = [ctypes.c_int]
     o1, n1 = run(lib)
     o0, n0 = run(alt)
     assert n1 == n0 == "gemm3_kernel" + want, (n1, n0)

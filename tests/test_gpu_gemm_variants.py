@@ -14,7 +14,6 @@ from kernel_checks import report
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-EW_ERR_UNSUPPORTED = -2                 # include/evoworld_hip.h
 MODES = ("dense", "conv3x3", "temporal")
 # generation N against generation 1: the bounds test_gpu_gemm_gen3.py puts on the same comparison (fp16 outputs / split hi + lo8 outputs)
 BOUND, BOUND_SPLIT = 1e-3, 2e-5
@@ -82,7 +81,7 @@ def test_every_operand_set_has_its_kernel(gen, mode):
                 with pytest.raises(_lib.EvoWorldHipError) as e:
                     run(gen, N, rb, r1, r2, split, geglu)
                 status = re.search(r"failed \((-?\d+)\)", str(e.value))
-                assert status and int(status.group(1)) == EW_ERR_UNSUPPORTED, (case, str(e.value))
+                assert status and int(status.group(1)) == _lib.EW_ERR_UNSUPPORTED == -2, (case, str(e.value))
                 assert lib.ew_last_error(), case
                 continue
             got, name = run(gen, N, rb, r1, r2, split, geglu)
