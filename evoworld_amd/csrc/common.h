@@ -43,6 +43,28 @@ static inline ew_status ew_ensure_dynamic_lds(const void* fn, int bytes, std::at
     return EW_OK;
 }
 
+// ---------------- wait / fence / barrier (every kernel file's one copy) ----------------
+// gfx9 s_waitcnt simm16: vmcnt[3:0]=bits3:0, expcnt=bits6:4, lgkmcnt=bits11:8, vmcnt[5:4]=bits15:14.  The BUILTIN form is
+// used for lgkmcnt so that hipcc's own waitcnt model knows the LDS queue is empty (an inline-asm wait is opaque to it).
+__device__ __forceinline__ void ew_wait_lgkm0() { __builtin_amdgcn_s_waitcnt(0xC07F); }
+// counted vmcnt keeps the inline-asm form: the counts are the kernels' own (instructions issued since the DMA / stores waited for)
+template <int N>
+__device__ __forceinline__ void ew_wait_vmcnt() {
+    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+// A full drain -- vmcnt(0) (expcnt = 7, lgkmcnt = 15 untouched), and vmcnt(0) + lgkmcnt(0) -- through the builtin, not inline asm: hipcc's
+// waitcnt pass then KNOWS the queue is empty.  With an opaque asm wait ff320_kernel kept a vmcnt(0) in front of the first use of the x
+// fragments in EVERY chunk (their loads are issued at the end of the previous tile), which drained the weight DMA right after it was
+// requested: 3.4x slower.
+__device__ __forceinline__ void ew_wait_vm0() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+__device__ __forceinline__ void ew_wait_vm0_lgkm0() { __builtin_amdgcn_s_waitcnt(0x0070); }
+__device__ __forceinline__ void ew_fence() { asm volatile("" ::: "memory"); }                  // compiler-only
+__device__ __forceinline__ void ew_block_barrier() { ew_fence(); __builtin_amdgcn_s_barrier(); ew_fence(); }
+__device__ __forceinline__ void ew_pin() { __builtin_amdgcn_sched_barrier(0); }                // nothing is scheduled across
+// wave-private LDS hand-over: this wave's LDS queue is empty and no lane's LDS access is moved across
+__device__ __forceinline__ void ew_wave_lds_sync() { ew_wait_lgkm0(); __builtin_amdgcn_wave_barrier(); }
+
 __device__ __forceinline__ float ew_silu(float x) { return x / (1.0f + __expf(-x)); }
 // erf GELU (torch.nn.functional.gelu default, diffusers GEGLU).  erf via Abramowitz-Stegun 7.1.26 (|abs err| <= 1.5e-7,
 // i.e. below fp32 erff's own error after the fp16 output rounding): 2 transcendentals + ~10 VALU instead of libm's

@@ -77,14 +77,7 @@ struct FfP {
     float c_acc, c_r1, c_r2;
 };
 
-#define FF_FENCE() asm volatile("" ::: "memory")
-// vmcnt(0) through the builtin (simm16: vmcnt = 0, expcnt = 7, lgkmcnt = 15), not inline asm: hipcc's waitcnt pass then KNOWS the
-// queue is empty.  With an opaque asm wait it kept a vmcnt(0) in front of the first use of the x fragments in EVERY chunk (their
-// loads are issued at the end of the previous tile), which drained the weight DMA right after it was requested: 3.4x slower.
-#define FF_WAIT_VM0() __builtin_amdgcn_s_waitcnt(0x0F70)
-#define FF_PIN() __builtin_amdgcn_sched_barrier(0)
-#define FF_WAIT_VM0_LGKM0() __builtin_amdgcn_s_waitcnt(0x0070)
-
+// (waits, fences and scheduling pins: common.h's ew_wait_vm0 / ew_wait_vm0_lgkm0 / ew_fence / ew_pin -- the waits are the builtin forms, see there)
 template <bool LO, bool R2>
 __global__ __launch_bounds__(64 * NWV, NWV / 4) void ff320_kernel(const FfP p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -128,7 +121,7 @@ __global__ __launch_bounds__(64 * NWV, NWV / 4) void ff320_kernel(const FfP p) {
     };
     issue_w1(0, 0);
     int cc = 0;                                 // global chunk index
-    FF_WAIT_VM0_LGKM0();                        // every wave drains ITS OWN DMA pieces of W1(0) (vmcnt) and its LDS writes before the
+    ew_wait_vm0_lgkm0();                        // every wave drains ITS OWN DMA pieces of W1(0) (vmcnt) and its LDS writes before the
     __syncthreads();                            // barrier: the fragment reads below cover pieces other waves loaded (b1 staged too)
     if (CC_total > 1) issue_w1(1, 1);
 
@@ -167,7 +160,7 @@ __global__ __launch_bounds__(64 * NWV, NWV / 4) void ff320_kernel(const FfP p) {
         }
     };
     load_x((int)blockIdx.x);
-    FF_WAIT_VM0();
+    ew_wait_vm0();
 
     for (int ti = 0; ti < n_my; ++ti) {
         const int tile = (int)blockIdx.x + ti * G;
@@ -222,7 +215,7 @@ __global__ __launch_bounds__(64 * NWV, NWV / 4) void ff320_kernel(const FfP p) {
 #pragma unroll
                     for (int j = 0; j < 2; ++j) wf[(ks + 2) % 3][j] = FF_W1F(w1b, ks + 2, j);
                 }
-                FF_PIN();
+                ew_pin();
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -235,14 +228,14 @@ __global__ __launch_bounds__(64 * NWV, NWV / 4) void ff320_kernel(const FfP p) {
                 } else {
                     if (ks == 1 || ks == 3 || ks == 5 || ks == 7) geglu_rf(acc1p[(ks - 1) / 2], bbp, hxp + ((ks - 1) / 2) * 1024);
                 }
-                FF_PIN();
+                ew_pin();
             }
 #pragma unroll
             for (int rf = 0; rf < RF; ++rf) { acc1p[rf][0] = acc1[rf][0]; acc1p[rf][1] = acc1[rf][1]; }
-            FF_WAIT_VM0_LGKM0();
-            FF_FENCE();
+            ew_wait_vm0_lgkm0();
+            ew_fence();
             __builtin_amdgcn_s_barrier();
-            FF_FENCE();
+            ew_fence();
             // ---- phase 2 (no branches: on the first chunk of a tile the exchange buffer holds zeros -- see the flush -- and past the
             // end of the block's work the W1 request / fragment reads touch buffers nobody reads again)
             if (c > 0) {
@@ -259,20 +252,20 @@ __global__ __launch_bounds__(64 * NWV, NWV / 4) void ff320_kernel(const FfP p) {
             char* d1 = smem + LDS_W1 + (cc & 1) * W1_TILE + wave * (P1 * 1024);
             const __amdgpu_buffer_rsrc_t r2d = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.w2p + (size_t)c * W2_TILE), 0, W2_TILE, 0x00020000);
             char* d2 = smem + LDS_W2 + (cc & 1) * W2_TILE + wave * 1024;
-            FF_PIN();
+            ew_pin();
             // ---- down-projection of chunk c-1: one k-step x this wave's 10 output fragments x 2 row fragments
 #pragma unroll
             for (int g2 = 0; g2 < 2; ++g2) {
                 f16x8 w2f[5];
 #pragma unroll
                 for (int u = 0; u < 5; ++u) w2f[u] = *(const f16x8*)(w2b + (g2 * 5 + u) * 1024 + rd2);
-                FF_PIN();
+                ew_pin();
 #pragma unroll
                 for (int u = 0; u < 5; ++u)
 #pragma unroll
                     for (int rf = 0; rf < RF; ++rf)
                         acc2[rf][g2 * 5 + u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w2f[u], hf_old[rf], acc2[rf][g2 * 5 + u], 0, 0, 0);
-                FF_PIN();
+                ew_pin();
                 // DMA pieces of this wave, half per group
                 constexpr int PER = (P1 + P2MAX + 1) / 2;
 #pragma unroll
@@ -281,7 +274,7 @@ __global__ __launch_bounds__(64 * NWV, NWV / 4) void ff320_kernel(const FfP p) {
                     else if (wave + NWV * (k - P1) < W2_TILE / 1024)
                         __builtin_amdgcn_raw_ptr_buffer_load_lds(r2d, (lptr_t)(d2 + (k - P1) * NWV * 1024), 16, (int)lane16, wave * 1024 + (k - P1) * NWV * 1024, 0, 0);
                 }
-                FF_PIN();
+                ew_pin();
             }
         }
         // ---- flush: down-projection of the tile's last chunk (its W2 image was requested in the last phase 2, its exchange halves
@@ -296,10 +289,10 @@ __global__ __launch_bounds__(64 * NWV, NWV / 4) void ff320_kernel(const FfP p) {
                     acc1p[rf][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
                 }
             }
-            FF_WAIT_VM0_LGKM0();
-            FF_FENCE();
+            ew_wait_vm0_lgkm0();
+            ew_fence();
             __builtin_amdgcn_s_barrier();
-            FF_FENCE();
+            ew_fence();
             const char* w2b = smem + LDS_W2 + ((cc + 1) & 1) * W2_TILE;       // W2(cc - 1): cc already points past the tile
 #pragma unroll
             for (int rf = 0; rf < RF; ++rf) hf_old[rf] = *(const f16x8*)(smem + LDS_HX + ((cc + 1) & 1) * HX_TILE + hx_off + rf * 1024);
@@ -376,9 +369,9 @@ __global__ __launch_bounds__(64 * NWV, NWV / 4) void ff320_kernel(const FfP p) {
                 }
             }
         }
-        FF_WAIT_VM0();      // next tile's x fragments (and this tile's stores) are complete before the chunk loop starts
+        ew_wait_vm0();      // next tile's x fragments (and this tile's stores) are complete before the chunk loop starts
     }
-    FF_WAIT_VM0();          // the last hand-overs requested images nobody reads: let them land
+    ew_wait_vm0();          // the last hand-overs requested images nobody reads: let them land
 }
 
 }  // namespace

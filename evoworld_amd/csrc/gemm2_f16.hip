@@ -240,9 +240,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void gemm2_kernel(const 
                 for (int q = 0; q < NQ; ++q)
                     if (idx == ((q + 1) * NM) / (NQ + 1) - 1) {
                         if (on) {
-                            __builtin_amdgcn_sched_barrier(0);
+                            ew_pin();
                             stage_piece(LO + q);
-                            __builtin_amdgcn_sched_barrier(0);
+                            ew_pin();
                         }
                     }
             }
@@ -274,7 +274,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void gemm2_kernel(const 
         ew_wait_lgkm0();   // af0/bf0 (read one half-step ago) have landed: free, and it lets the MFMAs below start
                            // without waiting for the reads issued next (hipcc otherwise emits lgkmcnt(0) after them)
         read_frags(cur, so1, af1, bf1);
-        __builtin_amdgcn_sched_barrier(0);   // keep the reads AHEAD of the MFMAs (hipcc otherwise sinks them to the end)
+        ew_pin();   // keep the reads AHEAD of the MFMAs (hipcc otherwise sinks them to the end)
         mma_il(af0, bf0, pend, std::integral_constant<int, P0>{}, std::integral_constant<int, NP>{});
         pend = false;
         // ---- publish K-tile v+1.  Unconditional (also on the last position, where the fragments read from the ring are
@@ -291,7 +291,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void gemm2_kernel(const 
             stage_begin(smem + s_cur * STAGE);
             pend = true;
         }
-        __builtin_amdgcn_sched_barrier(0);
+        ew_pin();
         // ---- half-step 1
         mma_il(af1, bf1, st_now, std::integral_constant<int, 0>{}, std::integral_constant<int, P0>{});
         const int s_prev = s_cur;

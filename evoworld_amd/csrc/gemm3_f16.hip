@@ -543,11 +543,11 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm3_kernel(const GemmP p, const 
                                     if constexpr (R2) x += p.c_r2 * (float)q2v[e];
                                     o[e] = (f16)x;
                                 }
-                                __builtin_amdgcn_sched_barrier(0);
+                                ew_pin();
                                 if (it + 1 < ITERS) fetch(i, h, it + 1);
                                 else if (h + 1 < NH) fetch(i, h + 1, 0);
                                 else if (i + 1 < FM) fetch(i + 1, 0, 0);
-                                __builtin_amdgcn_sched_barrier(0);
+                                ew_pin();
                                 if (is_live(it) && (FULL || m < p.M)) *(f16x8*)((char*)p.out + (unsigned)(m * p.ld_out + n) * 2u) = o;
                             }
                             __builtin_amdgcn_wave_barrier();
@@ -629,9 +629,9 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm3_kernel(const GemmP p, const 
                                 if constexpr (LO) s8[e] = ew_split_enc(x, o[e]);
                             }
                             if constexpr (LO) { ol[0] = ew_pack4(s8[0], s8[1], s8[2], s8[3]); ol[1] = ew_pack4(s8[4], s8[5], s8[6], s8[7]); }
-                            __builtin_amdgcn_sched_barrier(0);
+                            ew_pin();
                             if (k + ED < FM * NQ) fetch(k + ED);
-                            __builtin_amdgcn_sched_barrier(0);
+                            ew_pin();
                             if ((FULL || m < p.M)) {
                                 *(f16x8*)((char*)p.out + (unsigned)(m * p.ld_out + n) * 2u) = o;
                                 if constexpr (LO) {
@@ -732,7 +732,7 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm3_kernel(const GemmP p, const 
 #pragma unroll
                     for (int j = 0; j < FN; ++j) {
                         wsp[(i * FN + j) * (64 * NW)] = acc[i][j];
-                        __builtin_amdgcn_sched_barrier(0);
+                        ew_pin();
                     }
                 ew_wait_vmcnt<0>();
                 ew_block_barrier();

@@ -1,24 +1,10 @@
-// gemm_gen23.h -- what generations 2 and 3 (gemm2_f16.hip, gemm3_f16.hip) share: wait / fence / barrier primitives, the tap walk of the
-// implicit-GEMM loaders and the table of compiled (MODE, EPI) variants.  (The A-row geometry, the epilogue operand preamble and the
+// gemm_gen23.h -- what generations 2 and 3 (gemm2_f16.hip, gemm3_f16.hip) share: the tap walk of the implicit-GEMM loaders and the table
+// of compiled (MODE, EPI) variants; the wait / fence / barrier primitives they use are common.h's.  (The A-row geometry, the epilogue operand preamble and the
 // residual add are still one copy per family: moved into shared helpers they changed the shipped ISA -- see DESIGN.md section 3.)
 // Generation 1 (gemm_f16.hip) is the suite's independent cross-check and deliberately does NOT include this file.
 #pragma once
 #include "gemm_common.h"
 #include <type_traits>
-
-// ---------------- wait / fence / barrier ----------------
-// gfx9 s_waitcnt simm16: vmcnt[3:0]=bits3:0, expcnt=bits6:4, lgkmcnt=bits11:8, vmcnt[5:4]=bits15:14.  The BUILTIN form is
-// used for lgkmcnt so that hipcc's own waitcnt model knows the LDS queue is empty (an inline-asm wait is opaque to it).
-__device__ __forceinline__ void ew_wait_lgkm0() { __builtin_amdgcn_s_waitcnt(0xC07F); }
-// vmcnt keeps the inline-asm form: the counts are the kernels' own (instructions issued since the DMA / stores waited for)
-template <int N>
-__device__ __forceinline__ void ew_wait_vmcnt() {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void ew_fence() { asm volatile("" ::: "memory"); }                  // compiler-only
-__device__ __forceinline__ void ew_block_barrier() { ew_fence(); __builtin_amdgcn_s_barrier(); ew_fence(); }
-__device__ __forceinline__ void ew_pin() { __builtin_amdgcn_sched_barrier(0); }                // nothing is scheduled across
 
 // ---------------- K walk of the A loaders: channel-chunk major, tap minor (dense / conv3x3 / temporal 3-tap) ----------------
 template <int MODE>
