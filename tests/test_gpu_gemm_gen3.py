@@ -1,7 +1,9 @@
 """-m gpu: the generation-3 GEMM (256x320 tile; taken when N % 320 == 0 and the problem fills the chip) against a plain
 PyTorch fp32 reference AND against the independent generation-1 kernels, on problems large enough to be routed to it:
 ragged M (edge tiles), every epilogue operand set that occurs in the U-Net, all three A addressing modes (dense, conv3x3 with
-stride / upsample / dual source, temporal 3-tap).  test_gpu_ops.py's GEMM cases are small and run on generation 2."""
+stride / upsample / dual source, temporal 3-tap).  test_gpu_ops.py's GEMM cases are small and run on generation 2, at most one
+tile per workgroup; generation 2's chained-tile (multi-round) schedules are covered by test_gpu_gemm_gen2.py.  The helpers shared
+with that file (guarded, the fp64 conv references) live in gemm_cases.py."""
 import ctypes
 import math
 
@@ -10,7 +12,8 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_l2
-from kernel_checks import report, two_prefills
+from gemm_cases import _nhwc, _pack3, conv3x3_ref64, convt3_ref64, guarded
+from kernel_checks import report
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -112,26 +115,6 @@ WORST_ROW = {
 }
 
 
-def guarded(lib, gen, want, run, M, n_out, ld_pad, split=False):
-    """run(out, ld_out) under generation `gen`, into guarded outputs (one 256-row tile of pad rows, ld_out = n_out + ld_pad; the
-    lo8 plane guarded too when `split`) with two prefills; asserts the kernel name starts with `want`.  Returns the result (float)."""
-    from evoworld_amd.ops import Res
-    ld = n_out + ld_pad
-    names = []
-
-    def call(hi, *rest):
-        run(Res(hi, rest[0]) if split else hi, ld)
-        names.append(lib.ew_gemm_last_kernel().decode())
-    specs = [(M, n_out, torch.float16, dict(ld=ld))] + ([(M, n_out, torch.int8, dict(ld=ld))] if split else [])
-    lib.ew_set_gemm_generation(gen)
-    try:
-        gs = two_prefills(call, *specs)
-    finally:
-        lib.ew_set_gemm_generation(3)
-    assert all(n.startswith(want) for n in names), names
-    return Res(gs[0].view, gs[1].view).float() if split else gs[0].view.float()
-
-
 def both(lib, run, M, n_out, ld_pad, split=False, want3="gemm3_kernel", gen_b=1, want_b="gemm_kernel"):
     """run(out, ld_out) under generation 3 (asserting that `want3` took the problem) and under generation `gen_b`, each into its
     own guarded, twice-prefilled output (a tile one generation skips cannot inherit the other's values)."""
@@ -202,34 +185,6 @@ def _geglu_case(ops, lib, M, ld_pad):
     ref = y[:, :n] * F.gelu(y[:, n:])
     check_both(f"geglu {M}x{8 * C}x128 ld+{ld_pad}", g3, g1, ref, 1e-3)
     assert rel_l2(g3.cpu(), g1.cpu()) < 1e-3
-
-
-def _nhwc(x):
-    return x.permute(0, 2, 3, 1).reshape(-1, x.shape[1]).half().contiguous().to(DEV)
-
-
-def _pack3(w):
-    from evoworld_amd.ops import pack_conv_weight
-    return pack_conv_weight(w.half().float()).to(DEV)
-
-
-def conv3x3_ref64(xin, w, b, stride=1, pad=1):
-    """fp64 3x3 conv of xin [N,C,H,W] (already upsampled / padded as the kernel reads it) by im2col, one image at a time ->
-    [N*Ho*Wo, O] rows in the kernel's NHWC order"""
-    O = w.shape[0]
-    wm = w.reshape(O, -1).double().to(DEV)
-    out = [(wm @ F.unfold(xi[None].double().to(DEV), 3, padding=pad, stride=stride)[0]).T for xi in xin]
-    y = torch.cat(out)
-    return y + b.double().to(DEV) if b is not None else y
-
-
-def convt3_ref64(x, w, b):
-    """fp64 temporal conv, kernel (3,1,1) padding (1,0,0): x [B,T,P,C], w [O,C,3,1,1] -> [B*T*P, O]"""
-    xd = F.pad(x.double().to(DEV), (0, 0, 0, 0, 1, 1))                  # zero frames at both ends
-    T = x.shape[1]
-    wd = w.double().to(DEV).reshape(w.shape[0], w.shape[1], 3)
-    y = sum(xd[:, kt: kt + T] @ wd[:, :, kt].T for kt in range(3))
-    return y.reshape(-1, w.shape[0]) + b.double().to(DEV)
 
 
 @pytest.mark.parametrize("N,C,c2,O,H,W,stride,up,eps", [(13, 64, 0, 320, 61, 65, 1, 0, "rb"), (7, 64, 64, 320, 44, 170, 1, 0, "r1"),

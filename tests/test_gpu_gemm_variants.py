@@ -31,8 +31,10 @@ def rejected(mode, rb, r1, r2, split, geglu):
 
 
 def geometry(ops, gen, mode):
-    """gemm() keywords, M, rows per row-bias group, taps.  Generation 2: the smallest that can still go wrong -- 300 rows = one full 256-row tile + a ragged one.
-    Generation 3: 51237 rows (201 tiles per 320 columns: enough for its router, ragged last tile)."""
+    """gemm() keywords, M, rows per row-bias group, taps.  Generation 2: the smallest at which the variant TABLE can still go wrong -- 300 rows = one full
+    256-row tile + a ragged one, every workgroup computing at most one tile (what only shows when a workgroup chains tiles -- ring across tiles, counted
+    vmcnt waits after an epilogue -- is covered by test_gpu_gemm_gen2.py).  Generation 3: 51237 rows (201 tiles per 320 columns: enough for its router,
+    ragged last tile)."""
     if gen == 2:
         n, h, w, B, T, P = 2, 10, 15, 2, 5, 30
     else:
