@@ -11,15 +11,14 @@ State-dict keys are the HF keys (vision_model.embeddings.*, vision_model.encoder
 ViT-H/14 is 257 tokens per image and ONE image per clip: every contraction is ew_gemm_f16 (patch embedding as im2col GEMM,
 fused q|k|v projection, MLP with the erf-GELU epilogue), LayerNorms are ew_layernorm_f16, the 16-head attention with
 head_dim 80 runs on ew_attn_small_f16; the residual stream is split fp16 like the U-Net's."""
-import json
 import math
-import os
 from collections import OrderedDict
 from types import SimpleNamespace
 
 import torch
 
 from . import ops
+from ._model import PackedModel, Spec, Weights
 from .ops import ACT_GELU, Res
 
 DEFAULT_CLIP_CONFIG = dict(hidden_size=1280, intermediate_size=5120, num_hidden_layers=32, num_attention_heads=16,
@@ -29,24 +28,24 @@ CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 
 
 def clip_param_spec(cfg):
+    """name -> (shape, kind) in module-registration order (_model.Spec; HF key names); the class / position embeddings count as fan-in 1."""
     D, I, L, P = cfg["hidden_size"], cfg["intermediate_size"], cfg["num_hidden_layers"], cfg["patch_size"]
     n_pos = (cfg["image_size"] // P) ** 2 + 1
-    spec = OrderedDict()
+    spec = Spec()
     e = "vision_model.embeddings."
-    spec[e + "class_embedding"] = ((D,), 1.0)
-    spec[e + "patch_embedding.weight"] = ((D, 3, P, P), 3 * P * P)
-    spec[e + "position_embedding.weight"] = ((n_pos, D), 1.0)
-    spec["vision_model.pre_layrnorm.weight"] = ((D,), "gamma"); spec["vision_model.pre_layrnorm.bias"] = ((D,), "beta")
+    spec.add(e + "class_embedding", (D,), 1)
+    spec.add(e + "patch_embedding.weight", (D, 3, P, P), 3 * P * P)
+    spec.add(e + "position_embedding.weight", (n_pos, D), 1)
+    spec.norm("vision_model.pre_layrnorm", D)
     for i in range(L):
         p = f"vision_model.encoder.layers.{i}."
         for n in ("k_proj", "v_proj", "q_proj", "out_proj"):
-            spec[p + f"self_attn.{n}.weight"] = ((D, D), D); spec[p + f"self_attn.{n}.bias"] = ((D,), D)
-        spec[p + "layer_norm1.weight"] = ((D,), "gamma"); spec[p + "layer_norm1.bias"] = ((D,), "beta")
-        spec[p + "mlp.fc1.weight"] = ((I, D), D); spec[p + "mlp.fc1.bias"] = ((I,), D)
-        spec[p + "mlp.fc2.weight"] = ((D, I), I); spec[p + "mlp.fc2.bias"] = ((D,), I)
-        spec[p + "layer_norm2.weight"] = ((D,), "gamma"); spec[p + "layer_norm2.bias"] = ((D,), "beta")
-    spec["vision_model.post_layernorm.weight"] = ((D,), "gamma"); spec["vision_model.post_layernorm.bias"] = ((D,), "beta")
-    spec["visual_projection.weight"] = ((cfg["projection_dim"], D), D)
+            spec.lin(p + "self_attn." + n, D, D)
+        spec.norm(p + "layer_norm1", D)
+        spec.lin(p + "mlp.fc1", I, D); spec.lin(p + "mlp.fc2", D, I)
+        spec.norm(p + "layer_norm2", D)
+    spec.norm("vision_model.post_layernorm", D)
+    spec.lin("visual_projection", cfg["projection_dim"], D, bias=False)
     return spec
 
 
@@ -93,7 +92,12 @@ def encode_image_preprocess(image01, image_mean=CLIP_MEAN, image_std=CLIP_STD):
     return resize_with_antialiasing(x, (224, 224), (0.5 / std).to(dev).contiguous(), ((0.5 - mean) / std).to(dev).contiguous())
 
 
-class CLIPVisionModelWithProjection:
+class CLIPVisionModelWithProjection(PackedModel):
+    DEFAULTS = DEFAULT_CLIP_CONFIG
+    WEIGHT_FILES = ("model.safetensors", "model.fp16.safetensors")
+    MISSING = "CLIP state dict is missing"
+    _spec, _random = staticmethod(clip_param_spec), staticmethod(random_clip_state_dict)
+
     def __init__(self, **config):
         cfg = dict(DEFAULT_CLIP_CONFIG)
         cfg.update({k: v for k, v in config.items() if k in DEFAULT_CLIP_CONFIG})
@@ -101,65 +105,20 @@ class CLIPVisionModelWithProjection:
             raise NotImplementedError("only the erf GELU of CLIP ViT-H/14 (hidden_act='gelu') is built")
         if cfg["hidden_size"] % 64 or cfg["intermediate_size"] % 64 or (cfg["hidden_size"] // cfg["num_attention_heads"]) % 8:
             raise ValueError("evoworld_amd CLIP: hidden / intermediate sizes must be multiples of 64, head_dim of 8")
-        self._cfg = cfg
-        self.config = SimpleNamespace(**cfg)
-        self.dtype = torch.float32
-        self.device, self.w = None, None
+        super().__init__(cfg, torch.float32)
 
     @classmethod
-    def from_pretrained(cls, path, subfolder=None, device="cuda", **_ignored):
-        root = os.path.join(path, subfolder) if subfolder else path
-        cfg = {}
-        cj = os.path.join(root, "config.json")
-        if os.path.exists(cj):
-            raw = json.load(open(cj))
-            raw = {**raw.get("vision_config", {}), **raw}          # CLIPVisionConfig fields may sit at the top level
-            cfg = {k: raw[k] for k in DEFAULT_CLIP_CONFIG if k in raw}
-        m = cls(**cfg)
-        from safetensors.torch import load_file
-        for fn in ("model.safetensors", "model.fp16.safetensors"):
-            f = os.path.join(root, fn)
-            if os.path.exists(f):
-                return m.load_state_dict(load_file(f), device=device)
-        raise FileNotFoundError(f"no model*.safetensors under {root}")
-
-    @classmethod
-    def from_random(cls, seed=0, device="cuda", **config):
-        m = cls(**config)
-        return m.load_state_dict(random_clip_state_dict(m._cfg, seed), device=device)
+    def _config_from_json(cls, raw):
+        return super()._config_from_json({**raw.get("vision_config", {}), **raw})      # CLIPVisionConfig fields may sit at the top level
 
     def parameters(self):
         return iter([torch.empty(0, dtype=torch.float32)])        # `next(image_encoder.parameters()).dtype` (:262)
 
-    def to(self, *a, **k):
-        return self
-
-    def eval(self):
-        return self
-
-    def requires_grad_(self, _f=False):
-        return self
-
-    def load_state_dict(self, sd, device="cuda"):
-        spec = clip_param_spec(self._cfg)
-        missing = [k for k in spec if k not in sd]
-        if missing:
-            raise KeyError(f"CLIP state dict is missing {len(missing)} keys, e.g. {missing[:3]}")
-        for k, (shape, _) in spec.items():
-            if tuple(sd[k].shape) != tuple(shape):
-                raise ValueError(f"{k}: expected shape {shape}, got {tuple(sd[k].shape)}")
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("evoworld_amd.CLIPVisionModelWithProjection needs a GPU device (no CPU path)")
-        dev = self.device
+    def _pack(self, sd):
+        f = Weights(sd, self.device)
+        f32, h, dev = f.f32, f.h, self.device
         cfg = self._cfg
         D, P = cfg["hidden_size"], cfg["patch_size"]
-
-        def f32(k):
-            return sd[k].to(device=dev, dtype=torch.float32)
-
-        def h(t):
-            return t.to(torch.float16).contiguous()
         W = {}
         kp = (3 * P * P + 63) // 64 * 64
         pe = torch.zeros(D, kp, device=dev)
@@ -167,31 +126,26 @@ class CLIPVisionModelWithProjection:
         W["patch"], W["kp"] = h(pe), kp
         W["cls"] = f32("vision_model.embeddings.class_embedding")
         W["pos"] = f32("vision_model.embeddings.position_embedding.weight")
-        W["pre"] = (h(f32("vision_model.pre_layrnorm.weight")), h(f32("vision_model.pre_layrnorm.bias")))
+        W["pre"] = f.pair("vision_model.pre_layrnorm")
         W["layers"] = []
         for i in range(cfg["num_hidden_layers"]):
             p = f"vision_model.encoder.layers.{i}."
             a = p + "self_attn."
             W["layers"].append({
-                "ln1": (h(f32(p + "layer_norm1.weight")), h(f32(p + "layer_norm1.bias"))),
+                "ln1": f.pair(p + "layer_norm1"), "ln2": f.pair(p + "layer_norm2"),
                 "qkv": (h(torch.cat([f32(a + "q_proj.weight"), f32(a + "k_proj.weight"), f32(a + "v_proj.weight")])),
                         h(torch.cat([f32(a + "q_proj.bias"), f32(a + "k_proj.bias"), f32(a + "v_proj.bias")]))),
-                "out": (h(f32(a + "out_proj.weight")), h(f32(a + "out_proj.bias"))),
-                "ln2": (h(f32(p + "layer_norm2.weight")), h(f32(p + "layer_norm2.bias"))),
-                "fc1": (h(f32(p + "mlp.fc1.weight")), h(f32(p + "mlp.fc1.bias"))),
-                "fc2": (h(f32(p + "mlp.fc2.weight")), h(f32(p + "mlp.fc2.bias")))})
-        W["post"] = (h(f32("vision_model.post_layernorm.weight")), h(f32("vision_model.post_layernorm.bias")))
+                "out": f.pair(a + "out_proj"), "fc1": f.pair(p + "mlp.fc1"), "fc2": f.pair(p + "mlp.fc2")})
+        W["post"] = f.pair("vision_model.post_layernorm")
         pd = cfg["projection_dim"]
         pw = torch.zeros((pd + 3) // 4 * 4, D, device=dev)
         pw[:pd] = f32("visual_projection.weight")
         W["proj"] = h(pw)
         self.w = W
-        return self
 
     @torch.no_grad()
     def __call__(self, pixel_values, **_kw):
-        if self.w is None:
-            raise RuntimeError("weights not loaded")
+        self._require_loaded()
         cfg, W = self._cfg, self.w
         S_img, P, D, H = cfg["image_size"], cfg["patch_size"], cfg["hidden_size"], cfg["num_attention_heads"]
         if pixel_values.ndim != 4 or tuple(pixel_values.shape[1:]) != (3, S_img, S_img):

@@ -20,7 +20,6 @@ MI355X-first execution plan:
   * all time-embedding projections (44) and all cross-attention vectors (32) are two batched tiny GEMMs per forward.
 No torch.nn compute: torch provides device memory, the HIP stream and trivially small host-side glue only.
 """
-import json
 import math
 import os
 from collections import OrderedDict
@@ -29,7 +28,8 @@ from types import SimpleNamespace
 import torch
 
 from . import ops
-from .ops import A_CONV3X3, A_CONVT3, A_DENSE, ACT_GEGLU, ACT_NONE, ACT_SILU, Res
+from ._model import PackedModel, Spec, Weights
+from .ops import ACT_GEGLU, ACT_SILU, Res
 
 DEFAULT_CONFIG = dict(  # evoworld/trainer/unet_plucker.py:69-94 with in_channels=18 (trainer_utils.py:19)
     sample_size=None, in_channels=18, out_channels=4,
@@ -138,24 +138,12 @@ def _arch(cfg):
 
 
 def param_spec(cfg):
-    """OrderedDict name -> (shape, kind) in module-registration order; kind in {w, b, gamma, beta, mix}."""
-    spec = OrderedDict()
+    """name -> (shape, kind) in module-registration order (_model.Spec)."""
+    spec = Spec()
+    lin, conv, norm = spec.lin, spec.conv, spec.norm
     boc = tuple(cfg["block_out_channels"])
     temb = boc[0] * 4
     X = cfg["cross_attention_dim"]
-
-    def lin(p, o, i, bias=True):
-        spec[p + ".weight"] = ((o, i), "w")
-        if bias:
-            spec[p + ".bias"] = ((o,), "b:%d" % i)
-
-    def conv(p, o, i, k):
-        spec[p + ".weight"] = ((o, i) + k, "w")
-        spec[p + ".bias"] = ((o,), "b:%d" % (i * math.prod(k)))
-
-    def norm(p, c):
-        spec[p + ".weight"] = ((c,), "gamma")
-        spec[p + ".bias"] = ((c,), "beta")
 
     def resblock(r):
         s, t = r.p + ".spatial_res_block", r.p + ".temporal_res_block"
@@ -165,7 +153,7 @@ def param_spec(cfg):
             conv(s + ".conv_shortcut", r.cout, r.cin, (1, 1))
         norm(t + ".norm1", r.cout); conv(t + ".conv1", r.cout, r.cout, (3, 1, 1)); lin(t + ".time_emb_proj", r.cout, temb)
         norm(t + ".norm2", r.cout); conv(t + ".conv2", r.cout, r.cout, (3, 1, 1))
-        spec[r.p + ".time_mixer.mix_factor"] = ((1,), "mix")
+        spec.add(r.p + ".time_mixer.mix_factor", (1,), "mix")
 
     def attn(p, c, ctx):
         lin(p + ".to_q", c, c, False); lin(p + ".to_k", c, ctx or c, False); lin(p + ".to_v", c, ctx or c, False)
@@ -184,7 +172,7 @@ def param_spec(cfg):
         norm(b + ".norm_in", c); ff(b + ".ff_in", c); norm(b + ".norm1", c); attn(b + ".attn1", c, None)
         norm(b + ".norm2", c); attn(b + ".attn2", c, X); norm(b + ".norm3", c); ff(b + ".ff", c)
         lin(t.p + ".time_pos_embed.linear_1", 4 * c, c); lin(t.p + ".time_pos_embed.linear_2", c, 4 * c)
-        spec[t.p + ".time_mixer.mix_factor"] = ((1,), "mix")
+        spec.add(t.p + ".time_mixer.mix_factor", (1,), "mix")
         lin(t.p + ".proj_out", c, c)
 
     conv("conv_in", boc[0], cfg["in_channels"], (3, 3))
@@ -216,12 +204,8 @@ def random_state_dict(cfg, seed=0, device="cpu"):
     g = torch.Generator(device=device).manual_seed(seed)
     sd = OrderedDict()
     for name, (shape, kind) in param_spec(cfg).items():
-        if kind == "w":
-            fan_in = math.prod(shape[1:])
-            bound = 1.0 / math.sqrt(fan_in)
-            sd[name] = (torch.rand(shape, generator=g, device=device) * 2 - 1) * bound
-        elif kind.startswith("b:"):
-            bound = 1.0 / math.sqrt(int(kind[2:]))
+        if isinstance(kind, int):      # fan-in
+            bound = 1.0 / math.sqrt(kind)
             sd[name] = (torch.rand(shape, generator=g, device=device) * 2 - 1) * bound
         elif kind == "gamma":
             sd[name] = torch.ones(shape, device=device)
@@ -232,20 +216,23 @@ def random_state_dict(cfg, seed=0, device="cpu"):
     return sd
 
 
-class UNetSpatioTemporalConditionModel:
+class UNetSpatioTemporalConditionModel(PackedModel):
+    """from_pretrained: diffusers folder layout, <path>/<subfolder>/config.json + diffusion_pytorch_model.safetensors
+    (unified_loop_consistency.py:190-192); its qkv_fp8 keyword is the config key of the same name (None: EW_QKV_FP8 decides)."""
+    DEFAULTS = DEFAULT_CONFIG
+    WEIGHT_FILES = ("diffusion_pytorch_model.safetensors", "diffusion_pytorch_model.fp16.safetensors")
+    PRETRAINED_KW = ("qkv_fp8",)
+    _spec, _random = staticmethod(param_spec), staticmethod(random_state_dict)
+
     def __init__(self, **config):
         cfg = dict(DEFAULT_CONFIG)
         cfg["qkv_fp8"] = os.environ.get("EW_QKV_FP8", "0") == "1"      # a keyword argument overrides the environment switch
         cfg.update(config)
         cfg["qkv_fp8"] = bool(cfg["qkv_fp8"])
-        self._cfg = cfg
-        self.config = SimpleNamespace(**cfg)
+        super().__init__(cfg, torch.float16)
         self.arch = _arch(cfg)
-        self.device = None
-        self.w = None
         self.add_embedding = SimpleNamespace(linear_1=SimpleNamespace(
             in_features=cfg["projection_class_embeddings_input_dim"]))
-        self.dtype = torch.float16
         # residual stream: split fp16 (hi + lo, ~21 bits; default) or plain fp16 (EW_RESIDUAL=fp16: -15 % HBM traffic,
         # +30 % rel-L2 distance to the fp32 reference -- DESIGN.md section 4)
         mode = os.environ.get("EW_RESIDUAL", "split")
@@ -293,40 +280,15 @@ class UNetSpatioTemporalConditionModel:
 
     # ---------------- construction / loading ----------------
     @classmethod
-    def from_pretrained(cls, path, subfolder=None, device="cuda", qkv_fp8=None, **_ignored):
-        """diffusers folder layout: <path>/<subfolder>/config.json + diffusion_pytorch_model.safetensors
-        (unified_loop_consistency.py:190-192).  qkv_fp8: the config key of the same name (None: EW_QKV_FP8 decides)."""
-        root = os.path.join(path, subfolder) if subfolder else path
-        cfg = {}
-        cj = os.path.join(root, "config.json")
-        if os.path.exists(cj):
-            raw = json.load(open(cj))
-            cfg = {k: (tuple(v) if isinstance(v, list) else v) for k, v in raw.items() if k in DEFAULT_CONFIG}
-        if qkv_fp8 is not None:
-            cfg["qkv_fp8"] = qkv_fp8
-        m = cls(**cfg)
-        from safetensors.torch import load_file
-        for fn in ("diffusion_pytorch_model.safetensors", "diffusion_pytorch_model.fp16.safetensors"):
-            f = os.path.join(root, fn)
-            if os.path.exists(f):
-                m.load_state_dict(load_file(f), device=device)
-                return m
-        raise FileNotFoundError(f"no diffusion_pytorch_model*.safetensors under {root}")
-
-    @classmethod
-    def from_random(cls, seed=0, device="cuda", **config):
-        m = cls(**config)
-        m.load_state_dict(random_state_dict(m._cfg, seed), device=device)
-        return m
+    def _config_from_json(cls, raw):
+        return {k: (tuple(v) if isinstance(v, list) else v) for k, v in raw.items() if k in DEFAULT_CONFIG}
 
     @classmethod
     def from_zeros(cls, device="cuda", **config):
         """Same packed layout with all-zero weights: what a rank that does NOT read the checkpoint builds before
         `broadcast_weights` fills it over RCCL."""
         m = cls(**config)
-        sd = OrderedDict((k, torch.zeros(shape)) for k, (shape, _) in param_spec(m._cfg).items())
-        m.load_state_dict(sd, device=device)
-        return m
+        return m.load_state_dict(OrderedDict((k, torch.zeros(shape)) for k, (shape, _) in param_spec(m._cfg).items()), device=device)
 
     def packed_tensors(self):
         """Every device tensor of the packed weight set, in a fixed order (3.04 GB fp16 for the full U-Net)."""
@@ -361,61 +323,37 @@ class UNetSpatioTemporalConditionModel:
         """fp64 sum of all packed weights (cheap equality check across ranks after the broadcast)."""
         return float(sum(t.double().sum() for t in self.packed_tensors()))
 
-    def requires_grad_(self, _flag=False):
-        return self
-
-    def eval(self):
-        return self
-
     def to(self, device=None, dtype=None):
         if device is not None and self.w is not None and torch.device(device) != self.device:
             raise NotImplementedError("weights are packed on the device given at load time")
         return self
 
-    def load_state_dict(self, sd, device="cuda"):
-        spec = param_spec(self._cfg)
-        missing = [k for k in spec if k not in sd]
-        if missing:
-            raise KeyError(f"state dict is missing {len(missing)} keys, e.g. {missing[:3]}")
-        for k, (shape, _) in spec.items():
-            if tuple(sd[k].shape) != tuple(shape):
-                raise ValueError(f"{k}: expected shape {shape}, got {tuple(sd[k].shape)}")
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("evoworld_amd.UNetSpatioTemporalConditionModel needs a GPU device (no CPU path)")
-        self._pack(sd)
-        return self
-
     # ---------------- weight packing (once) ----------------
     def _pack(self, sd):
-        dev = self.device
+        f = Weights(sd, self.device)
+        f32, h = f.f32, f.h
         self._pos_cache = {}   # time_pos_embed outputs depend on the weights being replaced
         W = {}
-
-        def f32(k):
-            return sd[k].to(device=dev, dtype=torch.float32)
-
-        def h(t):
-            return t.to(torch.float16).contiguous()
-
-        def conv3(k, cpad=None):   # [O,I,3,3] -> [O, K], K = [I/64][9][64]
-            return ops.pack_conv_weight(f32(k + ".weight"), cpad)
-
-        def convt(k):              # [O,I,3,1,1] -> [O, K], K = [I/64][3][64]
-            return ops.pack_conv_weight(f32(k + ".weight"))
 
         def lin2(k, c, acts=False):  # [O, I] -> [O, 2 I] = [W_hi | W_lo] for the level-0 projections (a2 = a), plain fp16 otherwise;
             w = f32(k + ".weight")    # acts: [O, 3 I] = [W_hi | W_hi | W_lo] against the split A operand [x_hi | x_lo] + x_hi again
             if not (self.split_operands and c == self._cfg["block_out_channels"][0]):
-                return h(w)
+                return h(w), h(f32(k + ".bias"))
             w_hi, w_lo = hi_lo(w)
-            return h(torch.cat([w_hi, w_hi, w_lo] if acts else [w_hi, w_lo], dim=1))
+            return h(torch.cat([w_hi, w_hi, w_lo] if acts else [w_hi, w_lo], dim=1)), h(f32(k + ".bias"))
 
         def geglu(k):              # interleave value/gate rows in blocks of 16 (see ew_gemm_f16)
             w, b = f32(k + ".weight"), f32(k + ".bias")
             n = w.shape[0] // 2
-            idx = torch.arange(2 * n, device=dev).reshape(2, n // 16, 16).permute(1, 0, 2).reshape(-1)
+            idx = torch.arange(2 * n, device=self.device).reshape(2, n // 16, 16).permute(1, 0, 2).reshape(-1)
             return h(w[idx]), h(b[idx])
+
+        def ff(k, norm, c):        # one GEGLU feed-forward behind its LayerNorm: what `_ff` issues
+            d = {"norm": f.pair(norm), "up": geglu(k + ".net.0.proj"), "down": f.pair(k + ".net.2")}
+            if c == 320 and 4 * c == sd[k + ".net.2.weight"].shape[1]:
+                # level 0: the GEGLU feed-forward pair runs as ONE kernel (ew_ff_geglu320_f16) on LDS-image packs
+                d["pack"] = ops.ff_pack(f32(k + ".net.0.proj.weight"), f32(k + ".net.0.proj.bias"), f32(k + ".net.2.weight"))
+            return d
 
         def fp8(w):                # [O, I] fp32 -> (e4m3 bytes uint8 [O, I], fp32 scale [O]), one scale per output row, on the device
             return ops.quant_rows_fp8(h(w))
@@ -425,116 +363,69 @@ class UNetSpatioTemporalConditionModel:
         off = 0
         for r in self.arch.res:
             s, t = r.p + ".spatial_res_block", r.p + ".temporal_res_block"
-            d = {}
-            d["n1g"], d["n1b"] = h(f32(s + ".norm1.weight")), h(f32(s + ".norm1.bias"))
-            d["c1w"], d["c1b"] = conv3(s + ".conv1"), h(f32(s + ".conv1.bias"))
-            d["n2g"], d["n2b"] = h(f32(s + ".norm2.weight")), h(f32(s + ".norm2.bias"))
-            d["c2w"], d["c2b"] = conv3(s + ".conv2"), h(f32(s + ".conv2.bias"))
+            d = {"n1": f.pair(s + ".norm1"), "c1": f.conv(s + ".conv1"), "n2": f.pair(s + ".norm2"), "c2": f.conv(s + ".conv2"),
+                 "tn1": f.pair(t + ".norm1"), "t1": f.conv(t + ".conv1"), "tn2": f.pair(t + ".norm2"), "t2": f.conv(t + ".conv2"),
+                 "mix": float(torch.sigmoid(f32(r.p + ".time_mixer.mix_factor")).item())}
             if r.cin != r.cout:
-                d["scw"] = h(f32(s + ".conv_shortcut.weight")[:, :, 0, 0])
-                d["scb"] = h(f32(s + ".conv_shortcut.bias"))
-            d["tn1g"], d["tn1b"] = h(f32(t + ".norm1.weight")), h(f32(t + ".norm1.bias"))
-            d["t1w"], d["t1b"] = convt(t + ".conv1"), h(f32(t + ".conv1.bias"))
-            d["tn2g"], d["tn2b"] = h(f32(t + ".norm2.weight")), h(f32(t + ".norm2.bias"))
-            d["t2w"], d["t2b"] = convt(t + ".conv2"), h(f32(t + ".conv2.bias"))
-            d["mix"] = float(torch.sigmoid(f32(r.p + ".time_mixer.mix_factor")).item())
+                d["sc"] = (h(f32(s + ".conv_shortcut.weight")[:, :, 0, 0]), h(f32(s + ".conv_shortcut.bias")))
             for which in (s, t):
                 temb_w.append(f32(which + ".time_emb_proj.weight"))
                 temb_b.append(f32(which + ".time_emb_proj.bias"))
                 self._temb_off[which] = off
                 off += r.cout
             W[r.p] = d
-        W["temb_w"], W["temb_b"] = h(torch.cat(temb_w)), h(torch.cat(temb_b))
+        W["temb"] = (h(torch.cat(temb_w)), h(torch.cat(temb_b)))
         self._temb_total = off
 
         cv_w, cv_b, self._cv_off = [], [], {}
         off = 0
         for t in self.arch.trs:
-            d = {}
             c = t.ch
             use_fp8 = self._cfg["qkv_fp8"] and c % 64 == 0      # ew_gemm_fp8 needs K % 64 == 0: other widths keep fp16 projections
             if use_fp8:
                 self.fp8_blocks.append(t.p)
-            d["ng"], d["nb"] = h(f32(t.p + ".norm.weight")), h(f32(t.p + ".norm.bias"))
-            d["piw"], d["pib"] = lin2(t.p + ".proj_in", c, self.split_acts), h(f32(t.p + ".proj_in.bias"))
-            d["pow"], d["pob"] = lin2(t.p + ".proj_out", c), h(f32(t.p + ".proj_out.bias"))
-            d["mix"] = float(torch.sigmoid(f32(t.p + ".time_mixer.mix_factor")).item())
-            d["pe1w"], d["pe1b"] = h(f32(t.p + ".time_pos_embed.linear_1.weight")), h(f32(t.p + ".time_pos_embed.linear_1.bias"))
-            d["pe2w"], d["pe2b"] = h(f32(t.p + ".time_pos_embed.linear_2.weight")), h(f32(t.p + ".time_pos_embed.linear_2.bias"))
+            d = {"norm": f.pair(t.p + ".norm"), "proj_in": lin2(t.p + ".proj_in", c, self.split_acts), "proj_out": lin2(t.p + ".proj_out", c),
+                 "mix": float(torch.sigmoid(f32(t.p + ".time_mixer.mix_factor")).item()),
+                 "pe1": f.pair(t.p + ".time_pos_embed.linear_1"), "pe2": f.pair(t.p + ".time_pos_embed.linear_2")}
             for tag, b in (("s", t.p + ".transformer_blocks.0"), ("t", t.p + ".temporal_transformer_blocks.0")):
-                for nm in (["norm_in"] if tag == "t" else []) + ["norm1", "norm3"]:
-                    d[f"{tag}_{nm}g"], d[f"{tag}_{nm}b"] = h(f32(f"{b}.{nm}.weight")), h(f32(f"{b}.{nm}.bias"))
                 q, k_, v = f32(b + ".attn1.to_q.weight"), f32(b + ".attn1.to_k.weight"), f32(b + ".attn1.to_v.weight")
+                # qkv_fp8: (bytes, scales) packs in place of the fp16 matrices: they travel through packed_tensors() like any other tuple
                 if tag == "s":
-                    if use_fp8:     # (bytes, scales) packs in place of the fp16 matrices: they travel through packed_tensors() like any other tuple
-                        d["s_qk8"], d["s_v8"] = fp8(torch.cat([q, k_])), fp8(v)
-                    else:
-                        d["s_qk"], d["s_v"] = h(torch.cat([q, k_])), h(v)
-                elif use_fp8:
-                    d["t_qkv8"] = fp8(torch.cat([q, k_, v]))
+                    d["s_qk"], d["s_v"] = (fp8(torch.cat([q, k_])), fp8(v)) if use_fp8 else (h(torch.cat([q, k_])), h(v))
                 else:
-                    d["t_qkv"] = h(torch.cat([q, k_, v]))
-                d[f"{tag}_ow"], d[f"{tag}_ob"] = h(f32(b + ".attn1.to_out.0.weight")), h(f32(b + ".attn1.to_out.0.bias"))
+                    d["t_qkv"] = fp8(torch.cat([q, k_, v])) if use_fp8 else h(torch.cat([q, k_, v]))
+                    d["t_ff_in"] = ff(b + ".ff_in", b + ".norm_in", c)
+                d[tag + "_norm1"], d[tag + "_out"] = f.pair(b + ".norm1"), f.pair(b + ".attn1.to_out.0")
+                d[tag + "_ff"] = ff(b + ".ff", b + ".norm3", c)
                 # cross attention with ONE key/value token: out = to_out(to_v(ctx)) -> fold the two matrices
                 cv_w.append(f32(b + ".attn2.to_out.0.weight") @ f32(b + ".attn2.to_v.weight"))
                 cv_b.append(f32(b + ".attn2.to_out.0.bias"))
                 self._cv_off[(t.p, tag)] = off
                 off += c
-                d[f"{tag}_f1w"], d[f"{tag}_f1b"] = geglu(b + ".ff.net.0.proj")
-                d[f"{tag}_f2w"], d[f"{tag}_f2b"] = h(f32(b + ".ff.net.2.weight")), h(f32(b + ".ff.net.2.bias"))
-                if tag == "t":
-                    d["t_fi1w"], d["t_fi1b"] = geglu(b + ".ff_in.net.0.proj")
-                    d["t_fi2w"], d["t_fi2b"] = h(f32(b + ".ff_in.net.2.weight")), h(f32(b + ".ff_in.net.2.bias"))
-                if c == 320 and 4 * c == sd[b + ".ff.net.2.weight"].shape[1]:
-                    # level 0: the LayerNorm + GEGLU feed-forward pairs run as ONE kernel (ew_ff_geglu320_f16) on LDS-image packs
-                    for nm, ff in ((f"{tag}_ffp", ".ff"),) + (((f"{tag}_fip", ".ff_in"),) if tag == "t" else ()):
-                        d[nm] = ops.ff_pack(f32(b + ff + ".net.0.proj.weight"), f32(b + ff + ".net.0.proj.bias"), f32(b + ff + ".net.2.weight"))
             W[t.p] = d
-        W["cv_w"], W["cv_b"] = h(torch.cat(cv_w)), h(torch.cat(cv_b))
+        W["cv"] = (h(torch.cat(cv_w)), h(torch.cat(cv_b)))
         self._cv_total = off
 
-        for blk in self.arch.downs:
-            if blk.down:
-                W[blk.down.p] = (conv3(blk.down.p), h(f32(blk.down.p + ".bias")))
-        for blk in self.arch.ups:
-            if blk.up:
-                W[blk.up.p] = (conv3(blk.up.p), h(f32(blk.up.p + ".bias")))
+        for smp in [blk.down for blk in self.arch.downs if blk.down] + [blk.up for blk in self.arch.ups if blk.up]:
+            W[smp.p] = f.conv(smp.p)
         if self.in_split:
             W["conv_in"] = (ops.pack_conv_weight(split_conv_in_weight(f32("conv_in.weight"), self.in_split)), h(f32("conv_in.bias")))
         else:
-            W["conv_in"] = (conv3("conv_in", CPAD_IN), h(f32("conv_in.bias")))
+            W["conv_in"] = f.conv("conv_in", CPAD_IN)
         if self.split_operands:     # [W_hi | W_lo] over the input channels: the second block reads the same tensor again (a2 = a);
             w_hi, w_lo = hi_lo(f32("conv_out.weight"))      # split_acts: [W_hi | W_hi | W_lo] against the [x_hi | x_lo] rows of conv_norm_out
             W["conv_out"] = (ops.pack_conv_weight(torch.cat([w_hi, w_hi, w_lo] if self.split_acts else [w_hi, w_lo], dim=1)), h(f32("conv_out.bias")))
         else:
-            W["conv_out"] = (conv3("conv_out"), h(f32("conv_out.bias")))
-        W["no_g"], W["no_b"] = h(f32("conv_norm_out.weight")), h(f32("conv_norm_out.bias"))
-        W["te1w"], W["te1b"] = h(f32("time_embedding.linear_1.weight")), h(f32("time_embedding.linear_1.bias"))
-        W["ae1w"], W["ae1b"] = h(f32("add_embedding.linear_1.weight")), h(f32("add_embedding.linear_1.bias"))
+            W["conv_out"] = f.conv("conv_out")
+        W["norm_out"], W["te1"], W["ae1"] = f.pair("conv_norm_out"), f.pair("time_embedding.linear_1"), f.pair("add_embedding.linear_1")
         # emb = time_embedding.linear_2(.) + add_embedding.linear_2(.): one GEMM over the K-concat
-        W["e2w"] = h(torch.cat([f32("time_embedding.linear_2.weight"), f32("add_embedding.linear_2.weight")], dim=1))
-        W["e2b"] = h(f32("time_embedding.linear_2.bias") + f32("add_embedding.linear_2.bias"))
+        W["e2"] = (h(torch.cat([f32("time_embedding.linear_2.weight"), f32("add_embedding.linear_2.weight")], dim=1)),
+                   h(f32("time_embedding.linear_2.bias") + f32("add_embedding.linear_2.bias")))
         self.w = W
 
     # ---------------- building blocks ----------------
     def _res(self, rows, C, dev, head=False):
         return Res.empty(rows, C, dev, self.split_heads if head else self.split_residual)
-
-    def _conv3x3(self, x, x2, w, b, N, H, W_, Ho, Wo, stride=1, upsample=0, res_out=False, c2=None, **kw):
-        """c2: channels of the second source when they are fewer than its row width (x2 = the [x_hi | x_lo] rows read again for x_hi)."""
-        c1 = x.shape[-1]
-        lda2 = x2.shape[-1] if x2 is not None else 0
-        c2 = lda2 if c2 is None else c2
-        M = N * Ho * Wo
-        out = self._res(M, w.shape[0], x.device, head="r1" not in kw) if res_out else torch.empty(M, w.shape[0], dtype=torch.float16, device=x.device)
-        return ops.gemm(x, w, out, M=M, N=w.shape[0], c1=c1, lda=c1, a2=x2, c2=c2, lda2=lda2, bias=b,
-                        mode=A_CONV3X3, conv=(N, H, W_, Ho, Wo, stride, upsample), **kw)
-
-    def _convt(self, x, w, b, B, T, P, res_out=False, **kw):
-        C = x.shape[-1]
-        M = B * T * P
-        out = self._res(M, w.shape[0], x.device) if res_out else torch.empty(M, w.shape[0], dtype=torch.float16, device=x.device)
-        return ops.gemm(x, w, out, M=M, N=w.shape[0], c1=C, lda=C, bias=b, mode=A_CONVT3, tconv=(B, T, P), **kw)
 
     def _lin2(self, x, w, b, out, **kw):
         """Linear whose weight may be packed [W_hi | W_lo] (twice the input width): the second K block reads x again (a2 = a); or
@@ -557,26 +448,26 @@ class UNetSpatioTemporalConditionModel:
         dev = x1.hi.device
         tb_s = tembs[:, self._temb_off[s]:]
         tb_t = tembs[:, self._temb_off[t]:]
-        hN = ops.groupnorm(xs, d["n1g"], d["n1b"], N, HW, r.eps, True, pool=self._gn_pool)
-        h1 = self._conv3x3(hN, None, d["c1w"], d["c1b"], N, H, W_, H, W_, rowbias=tb_s, rows_per_group=T * HW,
+        hN = ops.groupnorm(xs, *d["n1"], N, HW, r.eps, True, pool=self._gn_pool)
+        h1 = self._conv3x3(hN, *d["c1"], N, H, W_, H, W_, rowbias=tb_s, rows_per_group=T * HW,
                            ld_rowbias=self._temb_total, res_out=self.split_h1)
-        h2 = ops.groupnorm([h1], d["n2g"], d["n2b"], N, HW, r.eps, True, pool=self._gn_pool)
-        if "scw" in d:
+        h2 = ops.groupnorm([h1], *d["n2"], N, HW, r.eps, True, pool=self._gn_pool)
+        if "sc" in d:
             sc = self._res(rows, r.cout, dev, head=True)
             c1 = x1.hi.shape[-1]
             c2 = x2.hi.shape[-1] if x2 is not None else 0
-            ops.gemm(x1.hi, d["scw"], sc, M=rows, N=r.cout, c1=c1, lda=c1, a2=x2.hi if x2 is not None else None, c2=c2,
-                     lda2=c2, bias=d["scb"])
+            ops.gemm(x1.hi, d["sc"][0], sc, M=rows, N=r.cout, c1=c1, lda=c1, a2=x2.hi if x2 is not None else None, c2=c2,
+                     lda2=c2, bias=d["sc"][1])
         else:
             sc = x1
-        xsp = self._conv3x3(h2, None, d["c2w"], d["c2b"], N, H, W_, H, W_, r1=sc, ld_r1=r.cout, res_out=True)
-        g1 = ops.groupnorm([xsp], d["tn1g"], d["tn1b"], B, T * HW, r.eps, True, pool=self._gn_pool)
-        t1 = self._convt(g1, d["t1w"], d["t1b"], B, T, HW, rowbias=tb_t, rows_per_group=T * HW,
+        xsp = self._conv3x3(h2, *d["c2"], N, H, W_, H, W_, r1=sc, ld_r1=r.cout, res_out=True)
+        g1 = ops.groupnorm([xsp], *d["tn1"], B, T * HW, r.eps, True, pool=self._gn_pool)
+        t1 = self._convt(g1, *d["t1"], B, T, HW, rowbias=tb_t, rows_per_group=T * HW,
                          ld_rowbias=self._temb_total)
-        g2 = ops.groupnorm([t1], d["tn2g"], d["tn2b"], B, T * HW, r.eps, True, pool=self._gn_pool)
+        g2 = ops.groupnorm([t1], *d["tn2"], B, T * HW, r.eps, True, pool=self._gn_pool)
         # x_temporal = xsp + conv2(..); AlphaBlender (switch_spatial_to_temporal_mix=False, the SpatioTemporalResBlock
         # default the U-Net blocks use): out = a*xsp + (1-a)*x_temporal = xsp + (1-a)*conv2(..), a = sigmoid(mix)
-        return self._convt(g2, d["t2w"], d["t2b"], B, T, HW, r1=xsp, ld_r1=r.cout, c_acc=1.0 - d["mix"], c_r1=1.0,
+        return self._convt(g2, *d["t2"], B, T, HW, r1=xsp, ld_r1=r.cout, c_acc=1.0 - d["mix"], c_r1=1.0,
                            res_out=True)
 
     def _pos_emb(self, t, B, T):
@@ -584,9 +475,18 @@ class UNetSpatioTemporalConditionModel:
         if key not in self._pos_cache:
             d = self.w[t.p]
             sin = ops.sinusoid_embed(torch.arange(T, device=self.device, dtype=torch.float32), T, t.ch)
-            e = ops.linear(ops.linear(sin, d["pe1w"], d["pe1b"], act=ACT_SILU), d["pe2w"], d["pe2b"])
+            e = ops.linear(ops.linear(sin, *d["pe1"], act=ACT_SILU), *d["pe2"])
             self._pos_cache[key] = e.repeat(B, 1).contiguous()
         return self._pos_cache[key]
+
+    def _ff(self, ff, x, out, ln_kw={}, **epi):
+        """One GEGLU feed-forward: out = epilogue(down(GEGLU(up(LayerNorm(x))))), `epi` = the residual / row-bias operands both forms share.
+        Level 0 (the block has the LDS-image pack) with fused_ff: one kernel after the LayerNorm; otherwise two GEMMs."""
+        n = ops.layernorm(x, *ff["norm"], **ln_kw)
+        if self.fused_ff and "pack" in ff:
+            return ops.ff_geglu320(n, ff["pack"], ff["down"][1], out, **epi)
+        C = n.shape[-1]
+        return ops.linear(ops.linear(n, *ff["up"], act=ACT_GEGLU), *ff["down"], out=out, ld_r1=C, ld_r2=C if "r2" in epi else 0, **epi)
 
     def _transformer(self, t, x, cvecs, B, T, H, W_):
         """TransformerSpatioTemporalModel.  x and the result are `Res`; every tensor of the block's
@@ -596,40 +496,30 @@ class UNetSpatioTemporalConditionModel:
         C, N, S = t.ch, B * T, H * W_
         rows = N * S
         dev = x.hi.device
+        fp8 = isinstance(d["s_qk"], tuple)      # qkv_fp8: (bytes, scales) packs
         cv_s = cvecs[:, self._cv_off[(t.p, "s")]:]
         cv_t = cvecs[:, self._cv_off[(t.p, "t")]:]
-        hn = ops.groupnorm([x], d["ng"], d["nb"], N, S, 1e-6, False, pool=self._gn_pool, split_out=d["piw"].shape[1] == 3 * C)
-        h = self._lin2(hn, d["piw"], d["pib"], self._res(rows, C, dev, head=True))
+        hn = ops.groupnorm([x], *d["norm"], N, S, 1e-6, False, pool=self._gn_pool, split_out=d["proj_in"][0].shape[1] == 3 * C)
+        h = self._lin2(hn, *d["proj_in"], self._res(rows, C, dev, head=True))
         # --- spatial BasicTransformerBlock ---
-        n1 = ops.layernorm(h, d["s_norm1g"], d["s_norm1b"])
+        n1 = ops.layernorm(h, *d["s_norm1"])
         prescale = ops.QK_LOG2_PRESCALE if self.attn_log2 else 1.0
-        if "s_qk8" in d:          # qkv_fp8: n1 is quantised once (one scale per token) and feeds both projections
+        if fp8:                   # qkv_fp8: n1 is quantised once (one scale per token) and feeds both projections
             n1q, n1s = ops.quant_rows_fp8(n1)
-            qk = ops.gemm_fp8(n1q, n1s, *d["s_qk8"], c_acc=prescale)
-            vt = ops.gemm_fp8(*d["s_v8"], n1q, n1s)                   # V^T = W_v X^T (swapped roles) -> [C, rows]
+            qk = ops.gemm_fp8(n1q, n1s, *d["s_qk"], c_acc=prescale)
+            vt = ops.gemm_fp8(*d["s_v"], n1q, n1s)                    # V^T = W_v X^T (swapped roles) -> [C, rows]
             del n1q, n1s
         else:
             qk = ops.linear(n1, d["s_qk"], c_acc=prescale)
             vt = torch.empty(C, rows, dtype=torch.float16, device=dev)
             ops.gemm(d["s_v"], n1, vt, M=C, N=rows, c1=C, lda=C)      # V^T = W_v X^T (swapped operands)
         ao = torch.empty(rows, C, dtype=torch.float16, device=dev)
-        if self.attn_log2:
-            ops.attn_spatial_log2(qk, qk[:, C:], vt, ao, N, S, t.heads, 2 * C, rows, C)
-        else:
-            ops.attn_spatial(qk, qk[:, C:], vt, ao, N, S, t.heads, 2 * C, rows, C)
+        (ops.attn_spatial_log2 if self.attn_log2 else ops.attn_spatial)(qk, qk[:, C:], vt, ao, N, S, t.heads, 2 * C, rows, C)
         del qk, vt
         # attn1 out-proj + residual + folded single-token cross attention (per batch row)
-        h = ops.linear(ao, d["s_ow"], d["s_ob"], out=self._res(rows, C, dev), rowbias=cv_s, rows_per_group=T * S,
+        h = ops.linear(ao, *d["s_out"], out=self._res(rows, C, dev), rowbias=cv_s, rows_per_group=T * S,
                        ld_rowbias=self._cv_total, r1=h, ld_r1=C)
-        fused = self.fused_ff if "s_ffp" in d else 0     # level 0: LayerNorm + GEGLU up-projection + down-projection + residual in one kernel
-        if fused:
-            n3 = ops.layernorm(h, d["s_norm3g"], d["s_norm3b"])
-            h = ops.ff_geglu320(n3, d["s_ffp"], d["s_f2b"], self._res(rows, C, dev), r1=h)
-        else:
-            n3 = ops.layernorm(h, d["s_norm3g"], d["s_norm3b"])
-            ffh = ops.linear(n3, d["s_f1w"], d["s_f1b"], act=ACT_GEGLU)
-            h = ops.linear(ffh, d["s_f2w"], d["s_f2b"], out=self._res(rows, C, dev), r1=h, ld_r1=C)
-            del ffh
+        h = self._ff(d["s_ff"], h, self._res(rows, C, dev), r1=h)
         # --- TemporalBasicTransformerBlock on frame-major tokens (regroup = addressing) ---
         # x_temporal stream starts as h + time_pos_embed: the sum is formed inside the LayerNorm (for norm_in) and again in
         # the ff_in epilogue (r1 = h, row-bias = the frame's embedding) -- it is never written to HBM
@@ -637,32 +527,17 @@ class UNetSpatioTemporalConditionModel:
         # hm after ff_in and after the temporal attention are the two stream tensors whose fp16 rounding matters least
         # (tests/analysis_fp16_floor.py per-tensor ablation: +0.036e-6 and +0.021e-6 of squared rel-L2 against 0.25e-6 for a
         # resblock output): they are kept as plain fp16, which saves their lo halves' write + two reads
-        if fused:
-            nin = ops.layernorm(h, d["t_norm_ing"], d["t_norm_inb"], addvec=pos, rows_per_group=S)
-            hm = ops.ff_geglu320(nin, d["t_fip"], d["t_fi2b"], Res.empty(rows, C, dev, False), r1=h, rowbias=pos, rows_per_group=S, ld_rowbias=C)
-        else:
-            nin = ops.layernorm(h, d["t_norm_ing"], d["t_norm_inb"], addvec=pos, rows_per_group=S)
-            ffh = ops.linear(nin, d["t_fi1w"], d["t_fi1b"], act=ACT_GEGLU)
-            hm = ops.linear(ffh, d["t_fi2w"], d["t_fi2b"], out=Res.empty(rows, C, dev, False), r1=h, ld_r1=C, rowbias=pos,
-                            rows_per_group=S, ld_rowbias=C)
-            del ffh
-        n1 = ops.layernorm(hm, d["t_norm1g"], d["t_norm1b"])
-        qkv = ops.gemm_fp8(*ops.quant_rows_fp8(n1), *d["t_qkv8"]) if "t_qkv8" in d else ops.linear(n1, d["t_qkv"])
+        hm = self._ff(d["t_ff_in"], h, Res.empty(rows, C, dev, False), dict(addvec=pos, rows_per_group=S), r1=h, rowbias=pos,
+                      rows_per_group=S, ld_rowbias=C)
+        n1 = ops.layernorm(hm, *d["t_norm1"])
+        qkv = ops.gemm_fp8(*ops.quant_rows_fp8(n1), *d["t_qkv"]) if fp8 else ops.linear(n1, d["t_qkv"])
         ops.attn_temporal(qkv, qkv[:, C:], qkv[:, 2 * C:], ao, B, T, S, t.heads, 3 * C, C)
         del qkv
-        hm = ops.linear(ao, d["t_ow"], d["t_ob"], out=Res.empty(rows, C, dev, False), rowbias=cv_t, rows_per_group=T * S,
+        hm = ops.linear(ao, *d["t_out"], out=Res.empty(rows, C, dev, False), rowbias=cv_t, rows_per_group=T * S,
                         ld_rowbias=self._cv_total, r1=hm, ld_r1=C)
         a = d["mix"]  # AlphaBlender: a*x_spatial + (1-a)*x_temporal, x_temporal = hm + ff(..); hb is only a GEMM operand
-        if fused:
-            n3 = ops.layernorm(hm, d["t_norm3g"], d["t_norm3b"])
-            hb = ops.ff_geglu320(n3, d["t_ffp"], d["t_f2b"], torch.empty(rows, C, dtype=torch.float16, device=dev), c_acc=1.0 - a, r1=hm,
-                                 c_r1=1.0 - a, r2=h, c_r2=a)
-        else:
-            n3 = ops.layernorm(hm, d["t_norm3g"], d["t_norm3b"])
-            ffh = ops.linear(n3, d["t_f1w"], d["t_f1b"], act=ACT_GEGLU)
-            hb = ops.linear(ffh, d["t_f2w"], d["t_f2b"], c_acc=1.0 - a, r1=hm, ld_r1=C, c_r1=1.0 - a, r2=h, ld_r2=C, c_r2=a)
-            del ffh
-        return self._lin2(hb, d["pow"], d["pob"], self._res(rows, C, dev), r1=x, ld_r1=C)
+        hb = self._ff(d["t_ff"], hm, torch.empty(rows, C, dtype=torch.float16, device=dev), c_acc=1.0 - a, r1=hm, c_r1=1.0 - a, r2=h, c_r2=a)
+        return self._lin2(hb, *d["proj_out"], self._res(rows, C, dev), r1=x, ld_r1=C)
 
     # ---------------- forward ----------------
     def forward_nhwc(self, x, timestep, encoder_hidden_states, added_time_ids, B, T, H, W_, taps=None):
@@ -681,16 +556,16 @@ class UNetSpatioTemporalConditionModel:
         t_emb = ops.sinusoid_embed(ts, B, boc[0])                          # one timestep broadcast over the batch rows, or one per row
         ids = added_time_ids if (added_time_ids.device == dev and added_time_ids.dtype == torch.float32) else added_time_ids.to(device=dev, dtype=torch.float32)
         a_emb = ops.sinusoid_embed(ids.reshape(-1).contiguous(), B * ids.shape[-1], cfg["addition_time_embed_dim"]).reshape(B, -1)
-        h1 = ops.linear(t_emb, Wt["te1w"], Wt["te1b"], act=ACT_SILU)
-        h2 = ops.linear(a_emb, Wt["ae1w"], Wt["ae1b"], act=ACT_SILU)
+        h1 = ops.linear(t_emb, *Wt["te1"], act=ACT_SILU)
+        h2 = ops.linear(a_emb, *Wt["ae1"], act=ACT_SILU)
         td = boc[0] * 4
         semb = torch.empty(B, td, dtype=torch.float16, device=dev)   # silu(emb): the only form emb is consumed in
-        ops.gemm(h1, Wt["e2w"], semb, M=B, N=td, c1=td, lda=td, a2=h2, c2=td, lda2=td, bias=Wt["e2b"], act=ACT_SILU)
-        tembs = ops.linear(semb, Wt["temb_w"], Wt["temb_b"])          # all 44 time_emb_proj at once
+        ops.gemm(h1, Wt["e2"][0], semb, M=B, N=td, c1=td, lda=td, a2=h2, c2=td, lda2=td, bias=Wt["e2"][1], act=ACT_SILU)
+        tembs = ops.linear(semb, *Wt["temb"])         # all 44 time_emb_proj at once
         ehs = encoder_hidden_states.to(device=dev, dtype=torch.float16).reshape(B, -1).contiguous()
-        cvecs = ops.linear(ehs, Wt["cv_w"], Wt["cv_b"])               # all 32 cross-attention vectors at once
+        cvecs = ops.linear(ehs, *Wt["cv"])            # all 32 cross-attention vectors at once
 
-        h = self._conv3x3(x, None, *Wt["conv_in"], N, H, W_, H, W_, res_out=True)
+        h = self._conv3x3(x, *Wt["conv_in"], N, H, W_, H, W_, res_out=True)
         if taps is not None:
             taps["conv_in"] = (h.float(), H, W_)
         skips = [(h, H, W_)]
@@ -701,8 +576,7 @@ class UNetSpatioTemporalConditionModel:
                     h = self._transformer(blk.attn[l], h, cvecs, B, T, H, W_)
                 skips.append((h, H, W_))
             if blk.down:
-                w, b = Wt[blk.down.p]
-                h = self._conv3x3(h.hi, None, w, b, N, H, W_, H // 2, W_ // 2, stride=2, res_out=True)
+                h = self._conv3x3(h.hi, *Wt[blk.down.p], N, H, W_, H // 2, W_ // 2, stride=2, res_out=True)
                 H, W_ = H // 2, W_ // 2
                 skips.append((h, H, W_))
             if taps is not None:
@@ -721,21 +595,19 @@ class UNetSpatioTemporalConditionModel:
                 if blk.attn:
                     h = self._transformer(blk.attn[l], h, cvecs, B, T, H, W_)
             if blk.up:
-                w, b = Wt[blk.up.p]
-                h = self._conv3x3(h.hi, None, w, b, N, H, W_, 2 * H, 2 * W_, upsample=1, res_out=True)
+                h = self._conv3x3(h.hi, *Wt[blk.up.p], N, H, W_, 2 * H, 2 * W_, upsample=1, res_out=True)
                 H, W_ = 2 * H, 2 * W_
             if taps is not None:
                 taps[f"up{bi}"] = (h.float(), H, W_)
         wco, bco = Wt["conv_out"]       # packed [W_hi | W_lo] (twice the input channels): the second block reads hn again;
         C0 = h.hi.shape[-1]             # or [W_hi | W_hi | W_lo] against the split rows [hn_hi | hn_lo] + hn_hi again
         blocks = wco.shape[1] // (9 * C0)
-        hn = ops.groupnorm([h], Wt["no_g"], Wt["no_b"], N, H * W_, 1e-5, True, pool=self._gn_pool, split_out=blocks == 3)
-        return self._conv3x3(hn, hn if blocks > 1 else None, wco, bco, N, H, W_, H, W_, c2=C0 if blocks > 1 else None)
+        hn = ops.groupnorm([h], *Wt["norm_out"], N, H * W_, 1e-5, True, pool=self._gn_pool, split_out=blocks == 3)
+        return self._conv3x3(hn, wco, bco, N, H, W_, H, W_, x2=hn if blocks > 1 else None, c2=C0 if blocks > 1 else None)
 
     @torch.no_grad()
     def __call__(self, sample, timestep, encoder_hidden_states, added_time_ids, return_dict=True, taps=None):
-        if self.w is None:
-            raise RuntimeError("weights not loaded")
+        self._require_loaded()
         if sample.ndim != 5 or sample.shape[2] != self._cfg["in_channels"]:
             raise ValueError(f"sample must be [B,T,{self._cfg['in_channels']},h,w], got {tuple(sample.shape)}")
         B, T, C, H, W_ = sample.shape

@@ -15,7 +15,6 @@ the exponential sees fp32 scores); exact algebra removes work: the key bias shif
 (softmax-invariant, dropped), the value bias passes through the row-stochastic P unchanged (folded into the out-projection
 bias), quant_conv (1x1, 8->8) is folded into the encoder's conv_out and only the 4 mean channels mode() returns are computed.
 """
-import json
 import math
 import os
 from collections import OrderedDict
@@ -24,7 +23,8 @@ from types import SimpleNamespace
 import torch
 
 from . import ops
-from .ops import A_CONV3X3, A_CONVT3, Res
+from ._model import PackedModel, Spec, Weights
+from .ops import Res
 
 DEFAULT_VAE_CONFIG = dict(block_out_channels=(128, 256, 512, 512), layers_per_block=2, latent_channels=4,
                           scaling_factor=0.18215, force_upcast=True)
@@ -32,22 +32,11 @@ CPAD = 64
 
 
 def vae_param_spec(cfg):
-    """OrderedDict name -> (shape, fan_in or None) in module-registration order (diffusers key names)."""
+    """name -> (shape, kind) in module-registration order (_model.Spec; diffusers key names)."""
     boc = tuple(cfg["block_out_channels"])
     L, lat = cfg["layers_per_block"], cfg["latent_channels"]
-    spec = OrderedDict()
-
-    def conv(p, o, i, k):
-        spec[p + ".weight"] = ((o, i) + k, i * math.prod(k))
-        spec[p + ".bias"] = ((o,), i * math.prod(k))
-
-    def lin(p, o, i):
-        spec[p + ".weight"] = ((o, i), i)
-        spec[p + ".bias"] = ((o,), i)
-
-    def norm(p, c):
-        spec[p + ".weight"] = ((c,), "gamma")
-        spec[p + ".bias"] = ((c,), "beta")
+    spec = Spec()
+    conv, lin, norm = spec.conv, spec.lin, spec.norm
 
     def res2d(p, ci, co):
         norm(p + ".norm1", ci); conv(p + ".conv1", co, ci, (3, 3)); norm(p + ".norm2", co); conv(p + ".conv2", co, co, (3, 3))
@@ -58,7 +47,7 @@ def vae_param_spec(cfg):
         res2d(p + ".spatial_res_block", ci, co)
         t = p + ".temporal_res_block"
         norm(t + ".norm1", co); conv(t + ".conv1", co, co, (3, 1, 1)); norm(t + ".norm2", co); conv(t + ".conv2", co, co, (3, 1, 1))
-        spec[p + ".time_mixer.mix_factor"] = ((1,), "mix")
+        spec.add(p + ".time_mixer.mix_factor", (1,), "mix")
 
     def attn(p, c):
         norm(p + ".group_norm", c)
@@ -108,7 +97,12 @@ def random_vae_state_dict(cfg, seed=0):
     return sd
 
 
-class AutoencoderKLTemporalDecoder:
+class AutoencoderKLTemporalDecoder(PackedModel):
+    DEFAULTS = DEFAULT_VAE_CONFIG
+    WEIGHT_FILES = ("diffusion_pytorch_model.safetensors", "diffusion_pytorch_model.fp16.safetensors")
+    MISSING = "VAE state dict is missing"
+    _spec, _random = staticmethod(vae_param_spec), staticmethod(random_vae_state_dict)
+
     def __init__(self, **config):
         cfg = dict(DEFAULT_VAE_CONFIG)
         cfg.update(config)
@@ -116,74 +110,18 @@ class AutoencoderKLTemporalDecoder:
         for c in cfg["block_out_channels"]:
             if c % 64:
                 raise ValueError("evoworld_amd VAE: block_out_channels must be multiples of 64")
-        self._cfg = cfg
-        self.config = SimpleNamespace(**cfg)
-        self.dtype = torch.float32          # API dtype: fp32 tensors in and out (the reference keeps the VAE in fp32, force_upcast)
-        self.device, self.w = None, None
+        super().__init__(cfg, torch.float32)  # API dtype: fp32 tensors in and out (the reference keeps the VAE in fp32, force_upcast)
         self.split_residual = os.environ.get("EW_RESIDUAL", "split") != "fp16"
         self.chunk = 8                      # frames per encoder pass (the encoder has no frame-axis op: chunking is exact)
 
-    # ---------------- construction ----------------
-    @classmethod
-    def from_pretrained(cls, path, subfolder=None, device="cuda", **_ignored):
-        root = os.path.join(path, subfolder) if subfolder else path
-        cfg = {}
-        cj = os.path.join(root, "config.json")
-        if os.path.exists(cj):
-            cfg = {k: v for k, v in json.load(open(cj)).items() if k in DEFAULT_VAE_CONFIG}
-        m = cls(**cfg)
-        from safetensors.torch import load_file
-        for fn in ("diffusion_pytorch_model.safetensors", "diffusion_pytorch_model.fp16.safetensors"):
-            f = os.path.join(root, fn)
-            if os.path.exists(f):
-                return m.load_state_dict(load_file(f), device=device)
-        raise FileNotFoundError(f"no diffusion_pytorch_model*.safetensors under {root}")
-
-    @classmethod
-    def from_random(cls, seed=0, device="cuda", **config):
-        m = cls(**config)
-        return m.load_state_dict(random_vae_state_dict(m._cfg, seed), device=device)
-
-    def to(self, *a, **k):
-        return self
-
-    def eval(self):
-        return self
-
-    def requires_grad_(self, _f=False):
-        return self
-
-    def load_state_dict(self, sd, device="cuda"):
-        spec = vae_param_spec(self._cfg)
-        missing = [k for k in spec if k not in sd]
-        if missing:
-            raise KeyError(f"VAE state dict is missing {len(missing)} keys, e.g. {missing[:3]}")
-        for k, (shape, _) in spec.items():
-            if tuple(sd[k].shape) != tuple(shape):
-                raise ValueError(f"{k}: expected shape {shape}, got {tuple(sd[k].shape)}")
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("evoworld_amd.AutoencoderKLTemporalDecoder needs a GPU device (no CPU path)")
-        self._pack(sd)
-        return self
-
     # ---------------- weight packing ----------------
     def _pack(self, sd):
-        dev = self.device
+        f = Weights(sd, self.device)
+        f32, h, conv, dev = f.f32, f.h, f.conv, self.device
         boc, L, lat = self._cfg["block_out_channels"], self._cfg["layers_per_block"], self._cfg["latent_channels"]
 
-        def f32(k):
-            return sd[k].to(device=dev, dtype=torch.float32)
-
-        def h(t):
-            return t.to(torch.float16).contiguous()
-
-        def conv(k, cpad=None):
-            return ops.pack_conv_weight(f32(k + ".weight"), cpad), h(f32(k + ".bias"))
-
         def res2d(p, ci, co):
-            d = {"n1": (h(f32(p + ".norm1.weight")), h(f32(p + ".norm1.bias"))), "c1": conv(p + ".conv1"),
-                 "n2": (h(f32(p + ".norm2.weight")), h(f32(p + ".norm2.bias"))), "c2": conv(p + ".conv2"), "ci": ci, "co": co}
+            d = {"n1": f.pair(p + ".norm1"), "c1": conv(p + ".conv1"), "n2": f.pair(p + ".norm2"), "c2": conv(p + ".conv2"), "ci": ci, "co": co}
             if ci != co:
                 d["sc"] = (h(f32(p + ".conv_shortcut.weight")[:, :, 0, 0]), h(f32(p + ".conv_shortcut.bias")))
             return d
@@ -191,15 +129,13 @@ class AutoencoderKLTemporalDecoder:
         def st_res(p, ci, co):
             d = res2d(p + ".spatial_res_block", ci, co)
             t = p + ".temporal_res_block"
-            d["tn1"] = (h(f32(t + ".norm1.weight")), h(f32(t + ".norm1.bias"))); d["t1"] = conv(t + ".conv1")
-            d["tn2"] = (h(f32(t + ".norm2.weight")), h(f32(t + ".norm2.bias"))); d["t2"] = conv(t + ".conv2")
+            d["tn1"], d["t1"], d["tn2"], d["t2"] = f.pair(t + ".norm1"), conv(t + ".conv1"), f.pair(t + ".norm2"), conv(t + ".conv2")
             d["mix"] = float(torch.sigmoid(f32(p + ".time_mixer.mix_factor")).item())
             return d
 
         def attn(p, c):
             wo, bo = f32(p + ".to_out.0.weight"), f32(p + ".to_out.0.bias")
-            return {"gn": (h(f32(p + ".group_norm.weight")), h(f32(p + ".group_norm.bias"))),
-                    "q": (h(f32(p + ".to_q.weight")), h(f32(p + ".to_q.bias"))),
+            return {"gn": f.pair(p + ".group_norm"), "q": f.pair(p + ".to_q"),
                     "k": h(f32(p + ".to_k.weight")),                       # key bias: constant per query row -> softmax-invariant
                     "v": h(f32(p + ".to_v.weight")),                       # value bias: rows of P sum to 1 -> moves to the out bias
                     "o": (h(wo), h(wo @ f32(p + ".to_v.bias") + bo)), "c": c}
@@ -216,7 +152,7 @@ class AutoencoderKLTemporalDecoder:
             W["e_down"].append(blk)
         W["e_mid"] = (res2d("encoder.mid_block.resnets.0", boc[-1], boc[-1]), attn("encoder.mid_block.attentions.0", boc[-1]),
                       res2d("encoder.mid_block.resnets.1", boc[-1], boc[-1]))
-        W["e_no"] = (h(f32("encoder.conv_norm_out.weight")), h(f32("encoder.conv_norm_out.bias")))
+        W["e_no"] = f.pair("encoder.conv_norm_out")
         # quant_conv (1x1) folded into conv_out; only the `lat` mean channels
         wq, bq = f32("quant_conv.weight")[:lat, :, 0, 0], f32("quant_conv.bias")[:lat]
         wo, bo = f32("encoder.conv_out.weight"), f32("encoder.conv_out.bias")
@@ -233,42 +169,29 @@ class AutoencoderKLTemporalDecoder:
             if i < len(rev) - 1:
                 blk["up"] = conv(f"decoder.up_blocks.{i}.upsamplers.0.conv")
             W["d_up"].append(blk)
-        W["d_no"] = (h(f32("decoder.conv_norm_out.weight")), h(f32("decoder.conv_norm_out.bias")))
+        W["d_no"] = f.pair("decoder.conv_norm_out")
         wc, bc = f32("decoder.conv_out.weight"), f32("decoder.conv_out.bias")
         W["d_out"] = (ops.pack_conv_weight(torch.cat([wc, torch.zeros_like(wc[:1])])), h(torch.cat([bc, torch.zeros(1, device=dev)])))  # 3 -> 4 rows
         W["d_time"] = (f32("decoder.time_conv_out.weight")[:, :, :, 0, 0].contiguous(), f32("decoder.time_conv_out.bias").contiguous())
         self.w = W
 
     # ---------------- building blocks (activations: fp16 [N*H*W, C], residual stream: Res) ----------------
-    def _res(self, rows, C, dev):
+    def _res(self, rows, C, dev, head=False):      # `head` (the U-Net's second policy) does not apply: one stream format
         return Res.empty(rows, C, dev, self.split_residual)
-
-    def _conv(self, x, wb, N, H, W_, Ho, Wo, res_out=False, **kw):
-        w, b = wb
-        M = N * Ho * Wo
-        out = self._res(M, w.shape[0], x.device) if res_out else torch.empty(M, w.shape[0], dtype=torch.float16, device=x.device)
-        return ops.gemm(x, w, out, M=M, N=w.shape[0], c1=x.shape[-1], lda=x.shape[-1], bias=b, mode=A_CONV3X3,
-                        conv=(N, H, W_, Ho, Wo, kw.pop("stride", 1), kw.pop("upsample", 0)), **kw)
-
-    def _convt(self, x, wb, B, T, P, res_out=False, **kw):
-        w, b = wb
-        out = self._res(B * T * P, w.shape[0], x.device) if res_out else torch.empty(B * T * P, w.shape[0], dtype=torch.float16, device=x.device)
-        return ops.gemm(x, w, out, M=B * T * P, N=w.shape[0], c1=x.shape[-1], lda=x.shape[-1], bias=b, mode=A_CONVT3,
-                        tconv=(B, T, P), **kw)
 
     def _resnet2d(self, d, x, N, H, W_):
         """ResnetBlock2D without time embedding: x + conv2(silu(gn(conv1(silu(gn(x))))))  (x: Res) -> Res"""
         HW = H * W_
         dev = x.hi.device
         hN = ops.groupnorm([x], *d["n1"], N, HW, 1e-6, True, pool=self._pool)
-        h1 = self._conv(hN, d["c1"], N, H, W_, H, W_)
+        h1 = self._conv3x3(hN, *d["c1"], N, H, W_, H, W_)
         h2 = ops.groupnorm([h1], *d["n2"], N, HW, 1e-6, True, pool=self._pool)
         if "sc" in d:
             sc = self._res(N * HW, d["co"], dev)
             ops.gemm(x.hi, d["sc"][0], sc, M=N * HW, N=d["co"], c1=d["ci"], lda=d["ci"], bias=d["sc"][1])
         else:
             sc = x
-        return self._conv(h2, d["c2"], N, H, W_, H, W_, res_out=True, r1=sc, ld_r1=d["co"])
+        return self._conv3x3(h2, *d["c2"], N, H, W_, H, W_, res_out=True, r1=sc, ld_r1=d["co"])
 
     def _st_resblock(self, d, x, B, T, H, W_):
         """SpatioTemporalResBlock of the decoder: AlphaBlender 'learned' with switch_spatial_to_temporal_mix=True:
@@ -276,9 +199,9 @@ class AutoencoderKLTemporalDecoder:
         HW = H * W_
         xsp = self._resnet2d(d, x, B * T, H, W_)
         g1 = ops.groupnorm([xsp], *d["tn1"], B, T * HW, 1e-5, True, pool=self._pool)
-        t1 = self._convt(g1, d["t1"], B, T, HW)
+        t1 = self._convt(g1, *d["t1"], B, T, HW)
         g2 = ops.groupnorm([t1], *d["tn2"], B, T * HW, 1e-5, True, pool=self._pool)
-        return self._convt(g2, d["t2"], B, T, HW, res_out=True, r1=xsp, ld_r1=d["co"], c_acc=d["mix"], c_r1=1.0)
+        return self._convt(g2, *d["t2"], B, T, HW, res_out=True, r1=xsp, ld_r1=d["co"], c_acc=d["mix"], c_r1=1.0)
 
     def _attention(self, d, x, N, H, W_):
         """single-head attention over the H*W tokens of each frame, residual outside (diffusers Attention)"""
@@ -315,12 +238,12 @@ class AutoencoderKLTemporalDecoder:
         self._begin(dev)
         xin = torch.zeros(n * H * W_, CPAD, dtype=torch.float16, device=dev)
         ops.nchw_f32_to_nhwc_f16(x.contiguous(), xin, CPAD)
-        h = self._conv(xin, Wt["e_in"], n, H, W_, H, W_, res_out=True)
+        h = self._conv3x3(xin, *Wt["e_in"], n, H, W_, H, W_, res_out=True)
         for blk in Wt["e_down"]:
             for d in blk["res"]:
                 h = self._resnet2d(d, h, n, H, W_)
             if "down" in blk:
-                h = self._conv(h.hi, blk["down"], n, H, W_, H // 2, W_ // 2, res_out=True, stride=2, conv_shift=1)
+                h = self._conv3x3(h.hi, *blk["down"], n, H, W_, H // 2, W_ // 2, res_out=True, stride=2, conv_shift=1)
                 H, W_ = H // 2, W_ // 2
         r0, at, r1 = Wt["e_mid"]
         h = self._resnet2d(r0, h, n, H, W_)
@@ -328,13 +251,12 @@ class AutoencoderKLTemporalDecoder:
         h = self._resnet2d(r1, h, n, H, W_)
         hn = ops.groupnorm([h], *Wt["e_no"], n, H * W_, 1e-6, True, pool=self._pool)
         lat = self._cfg["latent_channels"]
-        z = self._conv(hn, Wt["e_out"], n, H, W_, H, W_)
+        z = self._conv3x3(hn, *Wt["e_out"], n, H, W_, H, W_)
         return ops.nhwc_f16_to_nchw_f32(z, n, lat, H, W_, lat)
 
     @torch.no_grad()
     def encode(self, x, return_dict=True):
-        if self.w is None:
-            raise RuntimeError("weights not loaded")
+        self._require_loaded()
         if x.ndim != 4 or x.shape[1] != 3 or x.shape[2] % 8 or x.shape[3] % 8:
             raise ValueError(f"encode expects [N,3,H,W] with H, W multiples of 8, got {tuple(x.shape)}")
         x = x.to(device=self.device, dtype=torch.float32)
@@ -349,8 +271,7 @@ class AutoencoderKLTemporalDecoder:
     @torch.no_grad()
     def decode(self, z, num_frames=1, return_dict=True):
         """z fp32 [N,4,h,w] (already divided by scaling_factor by the caller, pipeline_evoworld.py:360); N % num_frames == 0."""
-        if self.w is None:
-            raise RuntimeError("weights not loaded")
+        self._require_loaded()
         if z.ndim != 4 or z.shape[1] != self._cfg["latent_channels"] or z.shape[0] % num_frames:
             raise ValueError(f"decode expects [N,{self._cfg['latent_channels']},h,w] with N a multiple of num_frames, got {tuple(z.shape)}")
         Wt = self.w
@@ -361,7 +282,7 @@ class AutoencoderKLTemporalDecoder:
         self._begin(dev)
         zin = torch.zeros(N * H * W_, CPAD, dtype=torch.float16, device=dev)
         ops.nchw_f32_to_nhwc_f16(z, zin, CPAD)
-        h = self._conv(zin, Wt["d_in"], N, H, W_, H, W_, res_out=True)
+        h = self._conv3x3(zin, *Wt["d_in"], N, H, W_, H, W_, res_out=True)
         r0, at, r1 = Wt["d_mid"]
         h = self._st_resblock(r0, h, B, T, H, W_)
         h = self._attention(at, h, N, H, W_)
@@ -370,10 +291,10 @@ class AutoencoderKLTemporalDecoder:
             for d in blk["res"]:
                 h = self._st_resblock(d, h, B, T, H, W_)
             if "up" in blk:
-                h = self._conv(h.hi, blk["up"], N, H, W_, 2 * H, 2 * W_, res_out=True, upsample=1)
+                h = self._conv3x3(h.hi, *blk["up"], N, H, W_, 2 * H, 2 * W_, res_out=True, upsample=1)
                 H, W_ = 2 * H, 2 * W_
         hn = ops.groupnorm([h], *Wt["d_no"], N, H * W_, 1e-6, True, pool=self._pool)
-        y = self._conv(hn, Wt["d_out"], N, H, W_, H, W_)                               # [N*H*W, 4] (3 real channels)
+        y = self._conv3x3(hn, *Wt["d_out"], N, H, W_, H, W_)                               # [N*H*W, 4] (3 real channels)
         img = ops.nhwc_f16_to_nchw_f32(y, N, 3, H, W_, 4).reshape(B, T, 3, H, W_)
         out = ops.time_conv3(img, *Wt["d_time"]).reshape(N, 3, H, W_)
         return SimpleNamespace(sample=out) if return_dict else (out,)

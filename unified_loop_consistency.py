@@ -182,10 +182,9 @@ def main(argv=None):
             unet = UNetSpatioTemporalConditionModel.from_pretrained(args.unet_path, subfolder=sub, device=dev, **fp8)
     else:
         cfg = {"num_frames": args.num_frames}
-        cj = os.path.join(args.unet_path, sub or "", "config.json")
-        if not args.random_init and os.path.exists(cj):
-            from evoworld_amd.unet import DEFAULT_CONFIG
-            cfg = {k: (tuple(v) if isinstance(v, list) else v) for k, v in json.load(open(cj)).items() if k in DEFAULT_CONFIG}
+        root = os.path.join(args.unet_path, sub or "")
+        if not args.random_init and os.path.exists(os.path.join(root, "config.json")):
+            cfg = UNetSpatioTemporalConditionModel.read_config(root)
         unet = UNetSpatioTemporalConditionModel.from_zeros(device=dev, **cfg, **fp8)
     if world > 1:
         unet.broadcast_weights(src=0)
