@@ -5,6 +5,8 @@
 # what was not computed under "not_computed".
 # LPIPS_WEIGHTS (optional: one file with a lpips.LPIPS state dict, or torchvision's AlexNet and the lpips package's alex.pth, as
 # .safetensors or torch checkpoints) adds LPIPS; LPIPS_CHANNEL_ORDER (default bgr, as the reference feeds its network; rgb) goes with it.
+# FVD_WEIGHTS (optional: a state dict in InceptionI3d's key layout, e.g. i3d_pretrained_400.pt, as .safetensors or a torch checkpoint) adds
+# FVD, the styleganv method at every clip length from 10 frames; FVD_CHANNEL_ORDER (default bgr, as the reference feeds its network; rgb).
 # PAIR_BY_NAME (default: true for SEGMENT_ID > 0) pairs the frame files both folders share: a later segment holds 24 generated and
 # 25 ground-truth frames, on which the reference's shape assertion fails.
 set -e
@@ -25,5 +27,8 @@ make -s -C evoworld_amd/csrc
 CMD="-m evoworld_amd.metrics --data_path $VIDEO_PATH --gt_subdir predictions_gt_$SEGMENT_ID --gen_subdir predictions_$SEGMENT_ID \
  --result_file $RESULT_PATH --test_length 25 --num_video $NUM_VIDEO"
 [ "$PAIR_BY_NAME" = true ] && CMD="$CMD --pair_by_name"
-[ -n "$LPIPS_WEIGHTS" ] && CMD="$CMD --metrics psnr,ssim,lpips --lpips_weights $LPIPS_WEIGHTS --lpips_channel_order ${LPIPS_CHANNEL_ORDER:-bgr}"
+METRICS=psnr,ssim
+[ -n "$LPIPS_WEIGHTS" ] && METRICS=psnr,ssim,lpips && CMD="$CMD --lpips_weights $LPIPS_WEIGHTS --lpips_channel_order ${LPIPS_CHANNEL_ORDER:-bgr}"
+[ -n "$FVD_WEIGHTS" ] && METRICS=$METRICS,fvd && CMD="$CMD --fvd_weights $FVD_WEIGHTS --fvd_channel_order ${FVD_CHANNEL_ORDER:-bgr}"
+CMD="$CMD --metrics $METRICS"
 python $CMD

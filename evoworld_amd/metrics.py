@@ -5,10 +5,12 @@ other_metrics/calculate_psnr.py and calculate_ssim.py.
 Per-frame values come from one kernel pass over each frame pair (ops.video_metrics, csrc/metrics.hip); the per-timestamp mean
 and std and the overall mean are the reference's numpy aggregation over those fp64 values.  FVD, LPIPS and the latent MSEs need
 pretrained networks (I3D, LPIPS/AlexNet, the SVD VAE) that this project does not ship: they are listed under `not_computed`.
-LPIPS is computed as well (evoworld_amd/lpips.py, csrc/lpips.hip) when the user names a file with its weights.
+LPIPS is computed as well (evoworld_amd/lpips.py, csrc/lpips.hip) when the user names a file with its weights, and so is FVD
+(evoworld_amd/fvd.py, csrc/i3d.hip: the styleganv method over I3D's 400 logits) when the user names a file with the I3D weights.
 
     python -m evoworld_amd.metrics --data_path OUT --gt_subdir predictions_gt_2 --gen_subdir predictions_2 [--pair_by_name]
                                    [--metrics psnr,ssim,lpips --lpips_weights lpips_alex.safetensors]
+                                   [--metrics psnr,ssim,fvd --fvd_weights i3d_pretrained_400.pt]
 """
 import argparse
 import json
@@ -124,16 +126,24 @@ def parse_args(argv=None):
     p.add_argument("--lpips_channel_order", type=str, choices=("bgr", "rgb"), default="bgr",
                    help="bgr (default): the network sees B, G, R planes as in the reference, whose cv2.imread frames are never "
                         "swapped; rgb: LPIPS as its authors define it")
+    p.add_argument("--fvd_weights", type=str, nargs="+", default=None, metavar="PATH",
+                   help="I3D (Kinetics-400) weights, .safetensors or a torch checkpoint: a state dict in InceptionI3d's key layout, such "
+                        "as the i3d_pretrained_400.pt of the reference's videogpt method (a TorchScript archive is refused); allows fvd "
+                        "in --metrics")
+    p.add_argument("--fvd_channel_order", type=str, choices=("bgr", "rgb"), default="bgr",
+                   help="bgr (default): the network sees B, G, R planes as in the reference, whose cv2.imread frames are never "
+                        "swapped; rgb: the order I3D was trained on")
     args = p.parse_args(argv)
     args.result_file = os.path.join(args.data_path, args.result_file)
     return args
 
 
-def selected_metrics(spec, lpips_weights=False):
-    """The metric names of --metrics.  lpips_weights: the user supplied LPIPS weights, which lifts the refusal of `lpips`."""
+def selected_metrics(spec, lpips_weights=False, fvd_weights=False):
+    """The metric names of --metrics.  lpips_weights / fvd_weights: the user supplied LPIPS / I3D weights, which lifts the refusal of
+    `lpips` / `fvd`."""
     names = [m.strip() for m in spec.split(",") if m.strip()]
     for m in names:
-        if m == "lpips" and lpips_weights:
+        if (m == "lpips" and lpips_weights) or (m == "fvd" and fvd_weights):
             continue
         if m in NOT_COMPUTED:
             raise ValueError(f"metric {m!r} cannot be computed: it {NOT_COMPUTED[m]}")
@@ -176,12 +186,16 @@ def _decode(path):
 def evaluate(args, device="cuda"):
     """main(args) of calculate_all_metrics.py:209-236 for PSNR / SSIM: one episode at a time is decoded (thread pool) and streamed
     to the device as uint8.  Returns (result dict, timing dict)."""
-    weights = getattr(args, "lpips_weights", None)
-    names = selected_metrics(args.metrics, lpips_weights=bool(weights))
+    weights, fvd_weights = getattr(args, "lpips_weights", None), getattr(args, "fvd_weights", None)
+    names = selected_metrics(args.metrics, lpips_weights=bool(weights), fvd_weights=bool(fvd_weights))
     lpips_model, lpips_order, lpips = None, getattr(args, "lpips_channel_order", "bgr"), []
     if "lpips" in names:
         from .lpips import LPIPSAlex
         lpips_model = LPIPSAlex.from_files(weights, device)
+    fvd_model, fvd_order, fvd_feats = None, getattr(args, "fvd_channel_order", "bgr"), ({}, {})     # {clip length: [logits per episode]}
+    if "fvd" in names:
+        from . import fvd as fvd_mod
+        fvd_model = fvd_mod.I3D.from_files(fvd_weights, device)
     episodes = list_episode_folders(args.data_path, args.num_videos)
     if not episodes:
         raise ValueError(f"no episode folders under {args.data_path}")
@@ -203,6 +217,12 @@ def evaluate(args, device="cuda"):
             p, s = video_metrics_u8(gt_d, gen_d)
             if lpips_model is not None:
                 lpips.append(lpips_model(gt_d, gen_d, lpips_order).cpu().numpy())
+            if fvd_model is not None:
+                if gt.shape[0] < 10:
+                    raise ValueError(f"episode {ep}: FVD compares clips of 10 frames and more, the folders hold {gt.shape[0]}")
+                for feats, clip in zip(fvd_feats, (gt_d, gen_d)):                # ground truth first, as the reference's main
+                    for L, v in fvd_mod.clip_features(fvd_model, clip, fvd_order).items():
+                        feats.setdefault(L, []).append(v)
             t_device += time.perf_counter() - t1
             t_decode += t1 - t0
             psnr.append(p)
@@ -210,13 +230,19 @@ def evaluate(args, device="cuda"):
     T, H, W, C = shape
     setting = torch.Size([T, C, H, W])
     result = {}
+    if fvd_model is not None:
+        from .ops import streamk_check
+        streamk_check()                            # results leave here
+        result["fvd"] = fvd_mod.fvd_result(*({L: np.stack(v) for L, v in f.items()} for f in fvd_feats),
+                                           torch.Size([len(episodes), C, T, H, W]))
     if "ssim" in names:
         result["ssim"] = aggregate(ssim, setting)
     if "psnr" in names:
         result["psnr"] = aggregate(psnr, setting)
     if lpips_model is not None:
         result["lpips"] = aggregate(lpips, setting)
-    result["not_computed"] = {k: v for k, v in NOT_COMPUTED.items() if not (k == "lpips" and lpips_model is not None)}
+    computed = {"lpips": lpips_model is not None, "fvd": fvd_model is not None}
+    result["not_computed"] = {k: v for k, v in NOT_COMPUTED.items() if not computed.get(k, False)}
     return result, {"episodes": len(episodes), "frames": len(episodes) * T, "decode_s": t_decode, "device_s": t_device}
 
 

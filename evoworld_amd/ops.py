@@ -622,6 +622,73 @@ def lpips_head(fa, fb, lin, wy, wx, n_out, acc):
     return acc
 
 
+def video_preprocess(clip, h_resized, w_resized, y0, x0, swap_rb=False):
+    """styleganv preprocess_single of one clip (ew_video_preprocess_f16): uint8 [T,H,W,3] or fp32 [T,3,H,W] in [0,1] -> fp16
+    [T,224,224,8] in [-1,1], channels 3..7 zero: bilinear resize to h_resized x w_resized, 224 x 224 crop at (y0, x0), (x - 0.5) * 2."""
+    if clip.dtype == torch.uint8:
+        _req(clip, torch.uint8, "clip")
+        kind = 1
+        T, H, W, C = clip.shape if clip.ndim == 4 else (0, 0, 0, 0)
+    else:
+        _req(clip, torch.float32, "clip")
+        kind = 2
+        T, C, H, W = clip.shape if clip.ndim == 4 else (0, 0, 0, 0)
+    if C != 3:
+        raise ValueError(f"clip: expected uint8 [T,H,W,3] or fp32 [T,3,H,W] frames, got {tuple(clip.shape)}")
+    out = torch.empty(T, 224, 224, 8, dtype=torch.float16, device=clip.device)
+    _call("ew_video_preprocess_f16", _ptr(clip), kind, _ptr(out), T, H, W, h_resized, w_resized, y0, x0, int(bool(swap_rb)))
+    return out
+
+
+def _thwc(x, name):
+    _req(x, torch.float16, name)
+    if x.ndim != 4:
+        raise ValueError(f"{name}: expected fp16 [T,H,W,C], got {tuple(x.shape)}")
+    return x.shape
+
+
+def im2col3d(x, kernel, stride, pads, out_size, ldk, relu=False, out=None):
+    """Patch rows of one clip for a 3-D convolution on ew_gemm_f16 (ew_im2col3d_f16): x fp16 [T,H,W,C] (C % 8 == 0; relu: read
+    max(x, 0)), kernel / stride / front pads / out_size triples over (t, h, w) -> fp16 [To*Ho*Wo, ldk], column ((dt*kh + dy)*kw + dx)*C + c,
+    zero outside the input and beyond kt*kh*kw*C."""
+    T, H, W, C = _thwc(x, "x")
+    rows = out_size[0] * out_size[1] * out_size[2]
+    if out is None:
+        out = torch.empty(rows, ldk, dtype=torch.float16, device=x.device)
+    else:
+        _req(out, torch.float16, "out")
+        if out.numel() != rows * ldk:
+            raise ValueError(f"out holds {out.numel()} values for {rows} rows of {ldk}")
+    _call("ew_im2col3d_f16", _ptr(x), _ptr(out), T, H, W, C, *kernel, *stride, *pads, *out_size, ldk, int(bool(relu)))
+    return out
+
+
+def maxpool3d_relu(x, kernel, stride, pads, out_size):
+    """Max pool of max(x, 0) over the taps inside the input (ew_maxpool3d_relu_f16): x fp16 [T,H,W,C] -> [To,Ho,Wo,C]."""
+    T, H, W, C = _thwc(x, "x")
+    out = torch.empty(*out_size, C, dtype=torch.float16, device=x.device)
+    _call("ew_maxpool3d_relu_f16", _ptr(x), _ptr(out), T, H, W, C, *kernel, *stride, *pads, *out_size)
+    return out
+
+
+def i3d_head(x, w, b, out=None):
+    """The pre-ReLU Mixed_5c output fp16 [T' >= 2,7,7,1024] -> I3D's 400 logits, fp32 (ew_i3d_head): W @ (mean over the (2,7,7) average
+    pool's windows of max(x, 0)) + b, with w fp32 [400,1024] and b fp32 [400]."""
+    T, H, W, C = _thwc(x, "x")
+    _req(w, torch.float32, "w"); _req(b, torch.float32, "b")
+    if tuple(w.shape) != (400, 1024) or tuple(b.shape) != (400,):
+        raise ValueError(f"i3d_head: w {tuple(w.shape)} / b {tuple(b.shape)}: expected [400,1024] and [400]")
+    if out is None:
+        out = torch.empty(400, dtype=torch.float32, device=x.device)
+    else:
+        _req(out, torch.float32, "out")
+        if out.numel() != 400:
+            raise ValueError(f"out holds {out.numel()} values, expected 400")
+    ws = torch.empty(_lib.load().ew_i3d_head_workspace_bytes(), dtype=torch.uint8, device=x.device)
+    _call("ew_i3d_head", _ptr(x), T, H, W, C, _ptr(w), _ptr(b), _ptr(out), _ptr(ws))
+    return out
+
+
 def blur_axis(x, kern, axis):
     """x fp32 [..., H, W], kern fp32 [k] -> correlation along H (axis 0) or W (axis 1), reflect padding."""
     _req(x, torch.float32, "x"); _req(kern, torch.float32, "kern")

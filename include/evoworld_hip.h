@@ -27,7 +27,7 @@ typedef int ew_status;
 #define EW_ERR_UNSUPPORTED (-2)
 #define EW_ERR_HIP (-3)
 
-#define EW_ABI_VERSION 15
+#define EW_ABI_VERSION 16
 int ew_abi_version(void);
 const char* ew_last_error(void);
 
@@ -433,6 +433,38 @@ ew_status ew_maxpool3s2_relu_f16(const void* src, void* out, int n_img, int h_in
 size_t ew_lpips_head_workspace_bytes(int F, int h, int w, int C);
 ew_status ew_lpips_head(const void* fa, const void* fb, const float* lin, const double* wy, const double* wx, int F, int h, int w, int C,
                         double n_out, double* acc, void* workspace, void* stream);
+
+/* FVD's I3D network (ABI 16; evoworld/metrics/fvd/styleganv/fvd.py preprocess_single and evoworld/metrics/fvd/videogpt/pytorch_i3d.py
+ * InceptionI3d(400): Inception-v1 inflated to 3-D, one clip per call).  The 57 BatchNorm-folded convolutions run on ew_gemm_f16 (dense
+ * mode, bias vector, ld_out = the module's concat width) over the patch rows of ew_im2col3d_f16; their outputs are stored PRE-ReLU and
+ * the kernels below apply max(x, 0) where they read.  Weights come from the caller: the project ships none.  All tensors are fp16
+ * [T,H,W,C] (channels innermost, C % 8 == 0), 16-byte aligned; no atomics, fixed summation orders: two calls are bit-identical.
+ *
+ * ew_video_preprocess_f16: preprocess_single of one clip.  src_kind 1: uint8 [T,H,W,3] (a pixel is float32(k) / 255.0f); 2: fp32 [T,3,H,W] in
+ *   [0,1] -> out [T,224,224,8], channels 3..7 zero.  Bilinear resize (align_corners=False, no antialias) to h_resized x w_resized with torch's
+ *   float32 index arithmetic (scale = in / out, src = max(0, scale * (i + 0.5) - 0.5), i0 = floor(src), i1 = min(i0 + 1, in - 1)), rounded as
+ *   torch's CPU kernel rounds (fma(scale, i + 0.5, -0.5); each blend t0 * w0 + t1 * w1 as fma(t0, w0, t1 * w1)), the 224 x 224
+ *   crop at (y0, x0) of the resized frame, then (x - 0.5) * 2.  Network channel c reads frame channel (swap_rb ? 2 - c : c).  The caller
+ *   computes h_resized, w_resized, y0, x0 (evoworld_amd.fvd.preprocess_geometry); only the cropped pixels are evaluated.
+ * ew_im2col3d_f16: (kt,kh,kw) / stride (st,sh,sw) patch gather with front pads (pt,ph,pw), 0 <= pad < kernel -> out [t_out*h_out*w_out, ldk],
+ *   column ((dt*kh + dy)*kw + dx)*C + c; taps outside the input and the columns [kt*kh*kw*C, ldk) are zero (ldk % 8 == 0: pad K to the
+ *   multiple of 64 ew_gemm_f16 wants).  The caller chooses the output size (TensorFlow "SAME": ceil(in / stride), front pad = total // 2;
+ *   evoworld_amd.fvd.same_pad); every window must overlap the input.  relu = 1 reads max(x, 0).
+ * ew_maxpool3d_relu_f16: max over the window's taps inside the input of max(x, 0), same geometry arguments -> out [t_out,h_out,w_out,C].
+ *   Equals the reference's zero-padded MaxPool3dSamePadding of post-ReLU input: every value is >= 0.
+ * ew_i3d_head: x = the pre-ReLU Mixed_5c output [t_in >= 2, 7, 7, 1024] (any other shape is refused) -> logits fp32 [400] =
+ *   mean over time of logits(AvgPool3d((2,7,7), 1)(relu(x))) = W v + b with v[c] = sum_j cnt_j sum_yx max(x[j,y,x,c], 0) / (98 (t_in - 1)),
+ *   cnt_j = the number of windows frame j lies in.  w fp32 [400,1024], b fp32 [400]; fp32 throughout; workspace: ew_i3d_head_workspace_bytes()
+ *   bytes, 16-byte aligned. */
+ew_status ew_video_preprocess_f16(const void* src, int src_kind, void* out, int T, int H, int W, int h_resized, int w_resized, int y0, int x0,
+                                  int swap_rb, void* stream);
+ew_status ew_im2col3d_f16(const void* src, void* out, int t_in, int h_in, int w_in, int C, int kt, int kh, int kw, int st, int sh, int sw,
+                          int pt, int ph, int pw, int t_out, int h_out, int w_out, int ldk, int relu, void* stream);
+ew_status ew_maxpool3d_relu_f16(const void* src, void* out, int t_in, int h_in, int w_in, int C, int kt, int kh, int kw, int st, int sh, int sw,
+                                int pt, int ph, int pw, int t_out, int h_out, int w_out, void* stream);
+size_t ew_i3d_head_workspace_bytes(void);
+ew_status ew_i3d_head(const void* x, int t_in, int h_in, int w_in, int C, const float* w, const float* b, float* logits, void* workspace,
+                      void* stream);
 
 #ifdef __cplusplus
 }

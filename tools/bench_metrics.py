@@ -12,6 +12,10 @@
                                                            evoworld_amd.lpips: ms per clip, host clock around a synchronised call; with
                                                            --cpu_baseline the same clip once through the fp32 PyTorch restatement
                                                            (tests/lpips_ref.py) on this machine's CPU, and the two results compared
+  python tools/bench_metrics.py --fvd [--iters N]          FVD's I3D (seeded random weights) on one 25-frame 576x1024 uint8 clip through
+                                                           evoworld_amd.fvd: ms for the clip's 16 clip lengths 10..25 (one preprocess, 16
+                                                           passes: what the CLI spends per episode and set) and ms for the 25-frame pass
+                                                           alone, host clock around synchronised calls
 Each mode prints one JSON line."""
 import argparse
 import json
@@ -90,6 +94,29 @@ def bench_lpips(iters, cpu_baseline):
     return rec
 
 
+def bench_fvd(iters):
+    from evoworld_amd import fvd as V
+    model = V.I3D.from_random(0, "cuda")
+    clip, _ = seeded_pair(0)
+
+    def timed(fn):
+        for _ in range(2):
+            out = fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / iters, out
+    ms_all, feats = timed(lambda: V.clip_features(model, clip, "bgr"))
+    ms_one, logits = timed(lambda: model.logits(clip, channel_order="bgr"))
+    return {"mode": "fvd", "frames": F, "shape": [H, W, 3], "clip_lengths": [min(feats), max(feats)], "ms_per_clip_all_lengths": round(ms_all, 2),
+            "ms_per_25_frame_pass": round(ms_one, 2), "iters": iters, "logits_abs_mean": float(logits.abs().mean()), "weights": "random (seed 0)",
+            "patch_row_cap_MiB": model.workspace_bytes >> 20,
+            "note": "host clock around the whole call (uint8 frames already on the device), synchronised; the all-lengths figure includes "
+                    "the 16 device-to-host copies of 400 logits"}
+
+
 def write_cli_tree(root, episodes):
     from concurrent.futures import ThreadPoolExecutor
     from PIL import Image
@@ -144,15 +171,18 @@ def main():
     p = argparse.ArgumentParser()
     p.add_argument("mode", nargs="?", choices=["kernel", "cli", "episode"])
     p.add_argument("--lpips", action="store_true", help="time LPIPS (random weights) on a 25-pair 576x1024 clip")
+    p.add_argument("--fvd", action="store_true", help="time FVD's I3D (random weights) on a 25-frame 576x1024 clip")
     p.add_argument("--cpu_baseline", action="store_true", help="with --lpips: also run the clip through tests/lpips_ref.py on the CPU")
-    p.add_argument("--iters", type=int, default=None, help="timed calls (default: 50 for kernel, 5 for --lpips)")
+    p.add_argument("--iters", type=int, default=None, help="timed calls (default: 50 for kernel, 5 for --lpips and --fvd)")
     p.add_argument("--root", help="directory the cli / episode modes write their PNG trees to")
     p.add_argument("--episodes", type=int, default=20)
     p.add_argument("--poses", type=int, default=80)
     a = p.parse_args()
-    if a.lpips == (a.mode is not None):
-        p.error("give one of kernel / cli / episode, or --lpips")
-    if a.lpips:
+    if (a.lpips + a.fvd + (a.mode is not None)) != 1:
+        p.error("give one of kernel / cli / episode, or --lpips, or --fvd")
+    if a.fvd:
+        rec = bench_fvd(a.iters or 5)
+    elif a.lpips:
         rec = bench_lpips(a.iters or 5, a.cpu_baseline)
     elif a.mode == "kernel":
         rec = bench_kernel(a.iters or 50)
