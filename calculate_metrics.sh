@@ -1,12 +1,14 @@
 #!/bin/bash
 # PSNR / SSIM of a run's per-segment dumps on the MI355X: counterpart of the reference's calculate_metrics.sh (same variables).
 # Compares $VIDEO_PATH/<episode>/predictions_gt_$SEGMENT_ID with predictions_$SEGMENT_ID and writes $VIDEO_PATH/$RESULT_PATH.
-# FVD and the latent MSEs need networks this project does not ship, and LPIPS needs weights it does not ship either; the JSON lists
-# what was not computed under "not_computed".
+# FVD, LPIPS and the latent MSEs need network weights this project does not ship; the JSON lists what was not computed under
+# "not_computed".
 # LPIPS_WEIGHTS (optional: one file with a lpips.LPIPS state dict, or torchvision's AlexNet and the lpips package's alex.pth, as
 # .safetensors or torch checkpoints) adds LPIPS; LPIPS_CHANNEL_ORDER (default bgr, as the reference feeds its network; rgb) goes with it.
 # FVD_WEIGHTS (optional: a state dict in InceptionI3d's key layout, e.g. i3d_pretrained_400.pt, as .safetensors or a torch checkpoint) adds
 # FVD, the styleganv method at every clip length from 10 frames; FVD_CHANNEL_ORDER (default bgr, as the reference feeds its network; rgb).
+# LATENT_MSE_WEIGHTS (optional: a state dict in timm inception_v4's key layout, as .safetensors or a torch checkpoint) adds latent_mse
+# and loop_closure_latent_mse (the last frame alone); LATENT_MSE_CHANNEL_ORDER (default bgr, as the reference feeds its network; rgb).
 # PAIR_BY_NAME (default: true for SEGMENT_ID > 0) pairs the frame files both folders share: a later segment holds 24 generated and
 # 25 ground-truth frames, on which the reference's shape assertion fails.
 set -e
@@ -30,5 +32,7 @@ CMD="-m evoworld_amd.metrics --data_path $VIDEO_PATH --gt_subdir predictions_gt_
 METRICS=psnr,ssim
 [ -n "$LPIPS_WEIGHTS" ] && METRICS=psnr,ssim,lpips && CMD="$CMD --lpips_weights $LPIPS_WEIGHTS --lpips_channel_order ${LPIPS_CHANNEL_ORDER:-bgr}"
 [ -n "$FVD_WEIGHTS" ] && METRICS=$METRICS,fvd && CMD="$CMD --fvd_weights $FVD_WEIGHTS --fvd_channel_order ${FVD_CHANNEL_ORDER:-bgr}"
+[ -n "$LATENT_MSE_WEIGHTS" ] && METRICS=$METRICS,latent_mse,loop_closure_latent_mse \
+  && CMD="$CMD --latent_mse_weights $LATENT_MSE_WEIGHTS --latent_mse_channel_order ${LATENT_MSE_CHANNEL_ORDER:-bgr}"
 CMD="$CMD --metrics $METRICS"
 python $CMD

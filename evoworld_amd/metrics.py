@@ -4,13 +4,16 @@ other_metrics/calculate_psnr.py and calculate_ssim.py.
 
 Per-frame values come from one kernel pass over each frame pair (ops.video_metrics, csrc/metrics.hip); the per-timestamp mean
 and std and the overall mean are the reference's numpy aggregation over those fp64 values.  FVD, LPIPS and the latent MSEs need
-pretrained networks (I3D, LPIPS/AlexNet, the SVD VAE) that this project does not ship: they are listed under `not_computed`.
+pretrained networks (I3D, LPIPS/AlexNet, Inception-v4) that this project does not ship: they are listed under `not_computed`.
 LPIPS is computed as well (evoworld_amd/lpips.py, csrc/lpips.hip) when the user names a file with its weights, and so is FVD
-(evoworld_amd/fvd.py, csrc/i3d.hip: the styleganv method over I3D's 400 logits) when the user names a file with the I3D weights.
+(evoworld_amd/fvd.py, csrc/i3d.hip: the styleganv method over I3D's 400 logits) when the user names a file with the I3D weights, and so
+are latent_mse and loop_closure_latent_mse (evoworld_amd/latent_mse.py, csrc/inception.hip: calculate_latent_mse.py:11-79 as
+calculate_all_metrics.py:220-221 calls it, over timm inception_v4's 1536 pooled features) when the user names the Inception-v4 weights.
 
     python -m evoworld_amd.metrics --data_path OUT --gt_subdir predictions_gt_2 --gen_subdir predictions_2 [--pair_by_name]
                                    [--metrics psnr,ssim,lpips --lpips_weights lpips_alex.safetensors]
                                    [--metrics psnr,ssim,fvd --fvd_weights i3d_pretrained_400.pt]
+                                   [--metrics psnr,ssim,latent_mse,loop_closure_latent_mse --latent_mse_weights inception_v4.safetensors]
 """
 import argparse
 import json
@@ -28,8 +31,10 @@ MAX_DECODE_THREADS = 16
 NOT_COMPUTED = {
     "fvd": "needs the I3D network (styleganv i3d_torchscript weights) and its code, absent from this project; no network access",
     "lpips": "needs the LPIPS network (AlexNet backbone and linear-layer weights) and its package, absent; no network access",
-    "latent_mse": "needs the VAE encoder weights (stable-video-diffusion) that map frames to latents, absent; no network access",
-    "loop_closure_latent_mse": "needs the same VAE encoder weights as latent_mse, absent; no network access",
+    "latent_mse": "needs Inception-v4 (timm inception_v4) weights passed with --latent_mse_weights, which this project does not ship; "
+                  "despite the metric's name its features are not latents of the SVD VAE",
+    "loop_closure_latent_mse": "needs the same Inception-v4 (timm inception_v4) weights as latent_mse, passed with --latent_mse_weights; "
+                               "despite the metric's name it does not use the SVD VAE",
 }
 SUPPORTED = ("psnr", "ssim")
 
@@ -133,17 +138,26 @@ def parse_args(argv=None):
     p.add_argument("--fvd_channel_order", type=str, choices=("bgr", "rgb"), default="bgr",
                    help="bgr (default): the network sees B, G, R planes as in the reference, whose cv2.imread frames are never "
                         "swapped; rgb: the order I3D was trained on")
+    p.add_argument("--latent_mse_weights", type=str, nargs="+", default=None, metavar="PATH",
+                   help="Inception-v4 weights, .safetensors or a torch checkpoint: a state dict in timm inception_v4's key layout "
+                        "(last_linear.* is ignored); allows latent_mse and loop_closure_latent_mse in --metrics")
+    p.add_argument("--latent_mse_channel_order", type=str, choices=("bgr", "rgb"), default="bgr",
+                   help="bgr (default): the network sees B, G, R planes under the ImageNet mean and std of R, G, B, as in the reference, "
+                        "whose cv2.imread frames are never swapped; rgb: the order Inception-v4 was trained on")
     args = p.parse_args(argv)
     args.result_file = os.path.join(args.data_path, args.result_file)
     return args
 
 
-def selected_metrics(spec, lpips_weights=False, fvd_weights=False):
-    """The metric names of --metrics.  lpips_weights / fvd_weights: the user supplied LPIPS / I3D weights, which lifts the refusal of
-    `lpips` / `fvd`."""
+LATENT_METRICS = ("latent_mse", "loop_closure_latent_mse")
+
+
+def selected_metrics(spec, lpips_weights=False, fvd_weights=False, latent_mse_weights=False):
+    """The metric names of --metrics.  lpips_weights / fvd_weights / latent_mse_weights: the user supplied LPIPS / I3D / Inception-v4
+    weights, which lifts the refusal of `lpips` / `fvd` / both latent MSEs."""
     names = [m.strip() for m in spec.split(",") if m.strip()]
     for m in names:
-        if (m == "lpips" and lpips_weights) or (m == "fvd" and fvd_weights):
+        if (m == "lpips" and lpips_weights) or (m == "fvd" and fvd_weights) or (m in LATENT_METRICS and latent_mse_weights):
             continue
         if m in NOT_COMPUTED:
             raise ValueError(f"metric {m!r} cannot be computed: it {NOT_COMPUTED[m]}")
@@ -187,7 +201,8 @@ def evaluate(args, device="cuda"):
     """main(args) of calculate_all_metrics.py:209-236 for PSNR / SSIM: one episode at a time is decoded (thread pool) and streamed
     to the device as uint8.  Returns (result dict, timing dict)."""
     weights, fvd_weights = getattr(args, "lpips_weights", None), getattr(args, "fvd_weights", None)
-    names = selected_metrics(args.metrics, lpips_weights=bool(weights), fvd_weights=bool(fvd_weights))
+    latent_weights = getattr(args, "latent_mse_weights", None)
+    names = selected_metrics(args.metrics, lpips_weights=bool(weights), fvd_weights=bool(fvd_weights), latent_mse_weights=bool(latent_weights))
     lpips_model, lpips_order, lpips = None, getattr(args, "lpips_channel_order", "bgr"), []
     if "lpips" in names:
         from .lpips import LPIPSAlex
@@ -196,6 +211,10 @@ def evaluate(args, device="cuda"):
     if "fvd" in names:
         from . import fvd as fvd_mod
         fvd_model = fvd_mod.I3D.from_files(fvd_weights, device)
+    latent_model, latent_order, latent_feats = None, getattr(args, "latent_mse_channel_order", "bgr"), ([], [])   # [T,1536] per episode
+    if any(m in names for m in LATENT_METRICS):
+        from . import latent_mse as latent_mod
+        latent_model = latent_mod.InceptionV4.from_files(latent_weights, device)
     episodes = list_episode_folders(args.data_path, args.num_videos)
     if not episodes:
         raise ValueError(f"no episode folders under {args.data_path}")
@@ -223,6 +242,9 @@ def evaluate(args, device="cuda"):
                 for feats, clip in zip(fvd_feats, (gt_d, gen_d)):                # ground truth first, as the reference's main
                     for L, v in fvd_mod.clip_features(fvd_model, clip, fvd_order).items():
                         feats.setdefault(L, []).append(v)
+            if latent_model is not None:                                         # one pass per clip serves both metrics
+                for feats, clip in zip(latent_feats, (gt_d, gen_d)):
+                    feats.append(latent_model.features(clip, latent_order).cpu().numpy())
             t_device += time.perf_counter() - t1
             t_decode += t1 - t0
             psnr.append(p)
@@ -241,7 +263,15 @@ def evaluate(args, device="cuda"):
         result["psnr"] = aggregate(psnr, setting)
     if lpips_model is not None:
         result["lpips"] = aggregate(lpips, setting)
-    computed = {"lpips": lpips_model is not None, "fvd": fvd_model is not None}
+    if latent_model is not None:
+        f_gt, f_gen = (np.stack(f) for f in latent_feats)                        # [B,T,1536], ground truth first as the reference's main
+        side = latent_mod.SIDE
+        if "latent_mse" in names:
+            result["latent_mse"] = latent_mod.latent_mse_result(f_gt, f_gen, torch.Size([len(episodes) * T, C, side, side]))
+        if "loop_closure_latent_mse" in names:                                   # video[:, -1:]: does the last frame come back to the start?
+            result["loop_closure_latent_mse"] = latent_mod.latent_mse_result(f_gt[:, -1:], f_gen[:, -1:],
+                                                                             torch.Size([len(episodes), C, side, side]))
+    computed = {"lpips": lpips_model is not None, "fvd": fvd_model is not None, **{m: m in result for m in LATENT_METRICS}}
     result["not_computed"] = {k: v for k, v in NOT_COMPUTED.items() if not computed.get(k, False)}
     return result, {"episodes": len(episodes), "frames": len(episodes) * T, "decode_s": t_decode, "device_s": t_device}
 

@@ -689,6 +689,51 @@ def i3d_head(x, w, b, out=None):
     return out
 
 
+def frames_resize_aa_norm(frames, table_h, table_w, mean, std, swap_rb=False):
+    """The Inception-v4 input of a batch of frames (ew_frames_resize_aa_norm_f16): uint8 [F,H,W,3] or fp32 [F,3,H,W] in [0,1] -> fp16
+    [F,out_h,out_w,8], channels 3..7 zero: the antialiased bilinear resize of torchvision's Resize on a float tensor, then (x - mean[c]) /
+    std[c].  table_h / table_w = (first int32 [n_out], count int32 [n_out], weights fp32 [n_out, taps]) device tensors, as
+    latent_mse.resize_table(H, out_h) / (W, out_w) gives them."""
+    if frames.dtype == torch.uint8:
+        _req(frames, torch.uint8, "frames")
+        kind = 1
+        F_, H, W, C = frames.shape if frames.ndim == 4 else (0, 0, 0, 0)
+    else:
+        _req(frames, torch.float32, "frames")
+        kind = 2
+        F_, C, H, W = frames.shape if frames.ndim == 4 else (0, 0, 0, 0)
+    if C != 3:
+        raise ValueError(f"frames: expected uint8 [F,H,W,3] or fp32 [F,3,H,W] frames, got {tuple(frames.shape)}")
+    args = []
+    for name, (first, count, weights) in (("table_h", table_h), ("table_w", table_w)):
+        _req(first, torch.int32, f"{name}[0]"); _req(count, torch.int32, f"{name}[1]"); _req(weights, torch.float32, f"{name}[2]")
+        if first.ndim != 1 or count.shape != first.shape or weights.ndim != 2 or weights.shape[0] != first.shape[0]:
+            raise ValueError(f"{name}: expected (first [n], count [n], weights [n, taps]), got {tuple(first.shape)}, {tuple(count.shape)}, "
+                             f"{tuple(weights.shape)}")
+        args += [_ptr(first), _ptr(count), _ptr(weights), weights.shape[1]]
+    out_h, out_w = table_h[0].shape[0], table_w[0].shape[0]
+    out = torch.empty(F_, out_h, out_w, 8, dtype=torch.float16, device=frames.device)
+    mean_std = (ctypes.c_float * 6)(*[float(v) for v in mean], *[float(v) for v in std])
+    _call("ew_frames_resize_aa_norm_f16", _ptr(frames), kind, _ptr(out), F_, H, W, out_h, out_w, *args, int(bool(swap_rb)), mean_std)
+    return out
+
+
+def avgpool3x3_relu(x):
+    """AvgPool2d(3, stride=1, padding=1, count_include_pad=False) of max(x, 0) (ew_avgpool3x3_relu_f16): fp16 [n,H,W,C] -> the same shape."""
+    n, H, W, C = _thwc(x, "x")
+    out = torch.empty_like(x)
+    _call("ew_avgpool3x3_relu_f16", _ptr(x), _ptr(out), n, H, W, C)
+    return out
+
+
+def global_avgpool_relu(x):
+    """fp16 [n,h,w,C] -> fp32 [n,C]: the mean over h * w of max(x, 0), a sequential fp32 sum (ew_global_avgpool_relu_f32)."""
+    n, h, w, C = _thwc(x, "x")
+    out = torch.empty(n, C, dtype=torch.float32, device=x.device)
+    _call("ew_global_avgpool_relu_f32", _ptr(x), _ptr(out), n, h, w, C)
+    return out
+
+
 def blur_axis(x, kern, axis):
     """x fp32 [..., H, W], kern fp32 [k] -> correlation along H (axis 0) or W (axis 1), reflect padding."""
     _req(x, torch.float32, "x"); _req(kern, torch.float32, "kern")

@@ -27,7 +27,7 @@ typedef int ew_status;
 #define EW_ERR_UNSUPPORTED (-2)
 #define EW_ERR_HIP (-3)
 
-#define EW_ABI_VERSION 16
+#define EW_ABI_VERSION 17
 int ew_abi_version(void);
 const char* ew_last_error(void);
 
@@ -465,6 +465,31 @@ ew_status ew_maxpool3d_relu_f16(const void* src, void* out, int t_in, int h_in, 
 size_t ew_i3d_head_workspace_bytes(void);
 ew_status ew_i3d_head(const void* x, int t_in, int h_in, int w_in, int C, const float* w, const float* b, float* logits, void* workspace,
                       void* stream);
+
+/* The latent MSE's Inception-v4 network (ABI 17; evoworld/metrics/other_metrics/calculate_latent_mse.py:11-79, run by
+ * evoworld/metrics/calculate_all_metrics.py:220-221: timm's `inception_v4` with the classifier removed, 1536 pooled features per frame,
+ * behind torchvision's Resize((299, 299)) + Normalize(ImageNet mean, std)).  The 149 BatchNorm-folded convolutions run on ew_gemm_f16
+ * (dense mode, bias vector, ld_out = the module's concat width) over the patch rows of ew_im2col3d_f16 with kt = 1, the max pools on
+ * ew_maxpool3d_relu_f16; conv outputs are stored PRE-ReLU and the kernels below apply max(x, 0) where they read.  Weights come from the
+ * caller: the project ships none.  No atomics, fixed summation orders: two calls are bit-identical.
+ *
+ * ew_frames_resize_aa_norm_f16: the first layer's input.  src_kind 1: uint8 [F,H,W,3] (a pixel is float32(k) / 255.0f); 2: fp32 [F,3,H,W] in
+ *   [0,1] -> out fp16 [F,out_h,out_w,8], channels 3..7 zero.  The resize is F.interpolate(mode="bilinear", align_corners=False,
+ *   antialias=True), what Resize does to a float tensor: a separable triangle filter, the W pass then the H pass, each a float32 chain
+ *   t = fma(src[j], w[j], t) in tap order (what torch's x86 builds compile their loop to).  Per axis and output index i the DEVICE
+ *   tables give the first source index (int [n_out]), the tap count (int [n_out]) and the weights (float [n_out, taps], rows padded), as evoworld_amd.latent_mse.resize_table computes them on the host; also an upscale
+ *   goes through the table (with antialias it is not plain bilinear).  Indices are clamped to the frame and counts to `taps`.  Then
+ *   (x - mean[c]) / std[c] in float32, then fp16.  Network channel c reads frame channel (swap_rb ? 2 - c : c); mean and std are indexed
+ *   by the network channel.  mean_std: HOST pointer to {mean[3], std[3]} (read during the call), std > 0.
+ * ew_avgpool3x3_relu_f16: AvgPool2d(3, stride=1, padding=1, count_include_pad=False) of max(x, 0), fp16 [n_img,H,W,C] -> the same shape,
+ *   C % 8 == 0: the taps inside the image added in fp32 in (dy, dx) order, divided by their number (4, 6 or 9 when H, W >= 3).
+ * ew_global_avgpool_relu_f32: fp16 [n_img,h,w,C] -> fp32 [n_img,C], the mean over h * w of max(x, 0): per (image, channel) one fp32 sum
+ *   in row-major pixel order, divided by h * w.  C % 8 == 0, pointers 16-byte aligned. */
+ew_status ew_frames_resize_aa_norm_f16(const void* src, int src_kind, void* out, int F, int H, int W, int out_h, int out_w, const int* y_first,
+                                       const int* y_count, const float* y_weights, int y_taps, const int* x_first, const int* x_count,
+                                       const float* x_weights, int x_taps, int swap_rb, const float* mean_std, void* stream);
+ew_status ew_avgpool3x3_relu_f16(const void* src, void* out, int n_img, int H, int W, int C, void* stream);
+ew_status ew_global_avgpool_relu_f32(const void* src, float* out, int n_img, int h, int w, int C, void* stream);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,10 @@
                                                            evoworld_amd.fvd: ms for the clip's 16 clip lengths 10..25 (one preprocess, 16
                                                            passes: what the CLI spends per episode and set) and ms for the 25-frame pass
                                                            alone, host clock around synchronised calls
+  python tools/bench_metrics.py --latent_mse [--iters N]   the latent MSE's Inception-v4 (seeded random weights) on the same 25 pairs through
+                                                           evoworld_amd.latent_mse: ms for the features of both clips (50 frames: what the
+                                                           CLI spends per episode for latent_mse and loop_closure_latent_mse together),
+                                                           host clock around synchronised calls
 Each mode prints one JSON line."""
 import argparse
 import json
@@ -117,6 +121,29 @@ def bench_fvd(iters):
                     "the 16 device-to-host copies of 400 logits"}
 
 
+def bench_latent_mse(iters):
+    from evoworld_amd import latent_mse as L
+    model = L.InceptionV4.from_random(0, "cuda")
+    gt, gen = seeded_pair(0)
+
+    def both():
+        return model.features(gt, "bgr"), model.features(gen, "bgr")
+    for _ in range(2):
+        f1, f2 = both()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        f1, f2 = both()
+    torch.cuda.synchronize()
+    ms = (time.perf_counter() - t0) * 1e3 / iters
+    res = L.latent_mse_result(f1.cpu()[None], f2.cpu()[None], torch.Size([F, 3, L.SIDE, L.SIDE]))
+    return {"mode": "latent_mse", "frames": F, "shape": [H, W, 3], "ms_per_clip_pair": round(ms, 2), "ms_per_frame": round(ms / (2 * F), 3),
+            "iters": iters, "latent_mse_mean": res["value_mean"], "loop_closure_latent_mse": res["value"][F - 1], "weights": "random (seed 0)",
+            "chunk_frames": model.chunk,
+            "note": "host clock around the features of both clips (uint8 frames already on the device; each call ends in streamk_check, "
+                    "which synchronises)"}
+
+
 def write_cli_tree(root, episodes):
     from concurrent.futures import ThreadPoolExecutor
     from PIL import Image
@@ -172,15 +199,18 @@ def main():
     p.add_argument("mode", nargs="?", choices=["kernel", "cli", "episode"])
     p.add_argument("--lpips", action="store_true", help="time LPIPS (random weights) on a 25-pair 576x1024 clip")
     p.add_argument("--fvd", action="store_true", help="time FVD's I3D (random weights) on a 25-frame 576x1024 clip")
+    p.add_argument("--latent_mse", action="store_true", help="time the latent MSE's Inception-v4 (random weights) on a 25-pair 576x1024 clip")
     p.add_argument("--cpu_baseline", action="store_true", help="with --lpips: also run the clip through tests/lpips_ref.py on the CPU")
-    p.add_argument("--iters", type=int, default=None, help="timed calls (default: 50 for kernel, 5 for --lpips and --fvd)")
+    p.add_argument("--iters", type=int, default=None, help="timed calls (default: 50 for kernel, 5 for --lpips, --fvd and --latent_mse)")
     p.add_argument("--root", help="directory the cli / episode modes write their PNG trees to")
     p.add_argument("--episodes", type=int, default=20)
     p.add_argument("--poses", type=int, default=80)
     a = p.parse_args()
-    if (a.lpips + a.fvd + (a.mode is not None)) != 1:
-        p.error("give one of kernel / cli / episode, or --lpips, or --fvd")
-    if a.fvd:
+    if (a.lpips + a.fvd + a.latent_mse + (a.mode is not None)) != 1:
+        p.error("give one of kernel / cli / episode, or --lpips, or --fvd, or --latent_mse")
+    if a.latent_mse:
+        rec = bench_latent_mse(a.iters or 5)
+    elif a.fvd:
         rec = bench_fvd(a.iters or 5)
     elif a.lpips:
         rec = bench_lpips(a.iters or 5, a.cpu_baseline)
