@@ -1,5 +1,5 @@
-"""GEMM test helpers shared by test_gpu_gemm_gen3.py and test_gpu_gemm_gen2.py (a plain module, imported like kernel_checks.py and
-reproject_cases.py).
+"""GEMM test helpers shared by test_gpu_gemm_gen3.py, test_gpu_gemm_gen2.py and test_gpu_gemm_gen3_rounds.py (a plain module, imported
+like kernel_checks.py and reproject_cases.py).
 
 - guarded / guarded_planes: one ew_gemm_f16 problem under a given generation into guarded, twice-prefilled outputs.
 - conv3x3_ref64 / convt3_ref64: fp64 references of the two conv addressing modes.
@@ -7,8 +7,13 @@ reproject_cases.py).
 - GEN2_CASES + problem(): the multi-round generation-2 problems of test_gpu_gemm_gen2.py, each with a run(out, ld_out, r0, r1)
   that launches rows [r0, r1) alone, and piece_ranges / piece_diff for the piece-identity check: a launch cut into tile-aligned
   pieces of at most one tile per workgroup must reproduce the rows of the whole launch bit for bit.
-  tests/test_cpu_gemm_gen2_cases.py checks the table's tile counts and that piece_diff catches one stale fragment."""
+  tests/test_cpu_gemm_gen2_cases.py checks the table's tile counts and that piece_diff catches one stale fragment.
+- gen3_plan / tile_coords: generation 3's routing decision (csrc/gemm3_f16.hip: plan3), tile order and per-workgroup work-item lists
+  (whole-tile schedule, stream-K tail, half split) restated.
+- GEN3_CASES + gen3_piece_ranges: the multi-round generation-3 problems of test_gpu_gemm_gen3_rounds.py (problem() builds them too)
+  and their single-round pieces; tests/test_cpu_gemm_gen3_cases.py checks that every case has the schedule its comment claims."""
 import math
+from types import SimpleNamespace
 
 import torch
 import torch.nn.functional as F
@@ -113,12 +118,15 @@ def piece_ranges(M, N, geglu, G, unit=256, units_per_piece=None):
     return [(r0, min(r0 + rows, M)) for r0 in range(0, M, rows)]
 
 
-def piece_diff(whole, pieces, N, geglu, G, limit=6):
+def piece_diff(whole, pieces, N, geglu, G, limit=6, family=None, tile_id=None, row0=0):
     """whole / pieces: lists of same-shaped [M, n_out] planes (hi, then lo8 where present) of the whole launch and of the rows
     assembled from the piece launches.  Returns (number of differing words, description of the first `limit`: row, column, tile id,
-    round of its workgroup's sequence, wave tile)."""
-    BM, BN, WM, WN = gen2_family(N, geglu)
+    round of its workgroup's sequence, wave tile).
+    family: (BM, BN, WM, WN) where it is not generation 2's; tile_id(tm, tn): the tile order where it is not tm * tiles_n + tn
+    (generation 3's bands); row0: first row of the planes in the whole problem (one piece compared on its own)."""
+    BM, BN, WM, WN = family or gen2_family(N, geglu)
     tiles_n = -(-N // BN)
+    tile_id = tile_id or (lambda tm, tn: tm * tiles_n + tn)
     scale = 2 if geglu else 1                            # GEGLU: output column c comes from the tile columns around 2c
     count, where = 0, []
     for k, (a, b) in enumerate(zip(whole, pieces)):
@@ -128,7 +136,8 @@ def piece_diff(whole, pieces, N, geglu, G, limit=6):
         count += n
         if n:
             for r, c in d.nonzero()[:limit].tolist():
-                tid = (r // BM) * tiles_n + (scale * c) // BN
+                r += row0
+                tid = tile_id(r // BM, (scale * c) // BN)
                 where.append(f"{'lo8' if k else 'hi'} ({r}, {c}): tile {tid} = ({r // BM}, {(scale * c) // BN}), round {tid // G}, "
                              f"wave tile ({(r % BM) // WM}, {((scale * c) % BN) // WN}), fragment row {(r % WM) // 16}")
     return count, "; ".join(where)
@@ -215,9 +224,9 @@ def _residual(ops, kind, M, N, seed, scale):
     return ops.Res.from_float(r) if kind == "s" else r.half()
 
 
-def problem(ops, c, G):
-    """Build the operands of GEN2_CASES entry c on the device (seeded CPU randn: weights / sqrt(K), residuals x 2 / x 3, row-bias
-    groups aligned to the piece starts)."""
+def problem(ops, c, G, rpg=None):
+    """Build the operands of GEN2_CASES / GEN3_CASES entry c on the device (seeded CPU randn: weights / sqrt(K), residuals x 2 / x 3,
+    row-bias groups aligned to the piece starts; rpg: rows per row-bias group of a dense case where it is not generation 2's rule)."""
     M, N, K, geglu, unit, _ = case_dims(c)
     p = Problem()
     p.M, p.N, p.n_out, p.split = M, N, (N // 2 if geglu else N), c.get("split", False)
@@ -227,9 +236,11 @@ def problem(ops, c, G):
     b0 = rnd(N, seed=3).half() if c.get("bias", True) else None
     bias = None if b0 is None else b0.to(DEV)
     r1 = _residual(ops, c.get("r1"), M, N, 5, 3.0)
-    r2 = _residual(ops, "h" if c.get("r2") else None, M, N, 6, 2.0)
-    pieces = case_pieces(c, G)
-    if c["kind"] == "dense":
+    r2 = _residual(ops, {True: "h", False: None}.get(c.get("r2"), c.get("r2")), M, N, 6, 2.0)
+    if c["kind"] == "dense" and rpg is not None:
+        pass                                                        # GEN3_CASES: gen3_rowbias_rows
+    elif c["kind"] == "dense":
+        pieces = case_pieces(c, G)
         rpg = max(1, (pieces[0][1] - pieces[0][0]) // 2)            # two groups per piece: piece starts are group starts
     elif c["kind"] == "conv":
         rpg = c.get("rb_imgs", 0) * unit
@@ -249,7 +260,7 @@ def problem(ops, c, G):
         if r1 is not None:
             y = y + c_r1 * r1.float().double()
         if r2 is not None:
-            y = y + c_r2 * r2.double()
+            y = y + c_r2 * r2.float().double()
         return y
 
     if c["kind"] == "dense":
@@ -303,3 +314,222 @@ def problem(ops, c, G):
             return finish(convt3_ref64(x.half(), w0.half(), b0))
     p.run, p.ref = run, ref
     return p
+
+
+# ----------------------------------------------------------------------------- generation 3's plan and schedule, restated
+def gen3_family(N):
+    """(BM, BN, WM, WN): the 256x320 instance (4 x 2 waves of 64 x 160), or the 256x256 one when only 256 divides N"""
+    BN = 256 if N % 256 == 0 and N % 320 != 0 else 320
+    return 256, BN, 64, BN // 2
+
+
+def gen3_epi(mode, operands):
+    """ew_gemm_select_epi for generation 3: the EPI of an operand set (bit 0 row-bias, 1 r1, 2 r2, 3 GEGLU, 4 lo8 operands), or
+    None where no variant exists.  operands: subset of {"rb", "r1", "r2", "lo", "geglu", "silu", "gelu"}"""
+    dense = mode == "dense"
+    if "geglu" in operands:
+        return 8 if dense else None
+    mask = ("rb" in operands) | ("r1" in operands) << 1 | ("r2" in operands) << 2
+    if "lo" in operands:
+        if mask & 6 == 0:
+            return 16 | 1
+        if dense:
+            return 16 | 3 if mask & 4 == 0 else 16 | 7
+        if mask & 5 == 0:
+            return 16 | 2
+        return 16 | 3 if mask & 4 == 0 else None
+    if mask <= 2 or (dense and mask == 3):
+        return mask
+    return 6 if dense and mask in (4, 6) else 7
+
+
+def tile_coords(id, tiles_m, tiles_n, band):
+    """tile id -> (tm, tn): tn fastest, inside bands of `band` tile columns when there are more columns than that (the last band
+    takes what is left)"""
+    if band <= 0 or tiles_n <= band:
+        return divmod(id, tiles_n)
+    nb = -(-tiles_n // band)
+    per_band = band * tiles_m
+    k = min(id // per_band, nb - 1)
+    r = id - k * per_band
+    w = tiles_n - k * band if k == nb - 1 else band
+    return r // w, k * band + r % w
+
+
+def gen3_tile_ids(tiles_m, tiles_n, band):
+    """[tm][tn] -> tile id (tile_coords inverted)"""
+    ids = [[None] * tiles_n for _ in range(tiles_m)]
+    for i in range(tiles_m * tiles_n):
+        tm, tn = tile_coords(i, tiles_m, tiles_n, band)
+        assert ids[tm][tn] is None, (i, tm, tn)
+        ids[tm][tn] = i
+    return ids
+
+
+def gen3_plan(M, N, K, mode, operands, G, debug=0, ld=None):
+    """plan3 and the kernel's block sequence for one problem on a CU budget of G: mode "dense" / "conv" / "temporal", operands as
+    in gen3_epi, debug: ew_set_gemm_debug (bit 2: whole tiles only), ld: the largest of ld_out / ld_r1 / ld_r2 (default N).
+    Returns .taken (generation 3 runs it; with a split, given a stream-K workspace), .kernel (name with <MODE, EPI>), .BM / .BN,
+    .tiles_m / .tiles_n / .tiles / .nk / .band, .schedule ("whole", "tail" or "half"), .dp_rounds / .sk_tiles, .grid and
+    .items[b]: the (tile id, k0, k1) work items of workgroup b in the order it runs them."""
+    operands = set(operands)
+    BM, BN, _, _ = gen3_family(N)
+    dense = mode == "dense"
+    rb, r1, r2, lo = ("rb" in operands, "r1" in operands, "r2" in operands, "lo" in operands)
+    nk = K // 64
+    tiles_m, tiles_n = -(-M // BM), N // BN
+    tiles = tiles_m * tiles_n
+    epi = gen3_epi(mode, operands)
+    pl = SimpleNamespace(taken=False, BM=BM, BN=BN, epi=epi, tiles_m=tiles_m, tiles_n=tiles_n, tiles=tiles, nk=nk, band=0,
+                         schedule=None, dp_rounds=0, sk_tiles=0, grid=0, items=[],
+                         kernel=f"{'gemm3_kernel' if BN == 320 else 'gemm3b_kernel'}<{('dense', 'conv', 'temporal').index(mode)}, {epi}>")
+    if N % BN != 0 or M < 320 or epi is None:
+        return pl
+    if tiles > G * (8192 // 16 - 4):                                # work-item table of a persistent block
+        return pl
+    if "gelu" in operands and (not dense or rb or r1 or r2 or lo):
+        return pl
+    if "silu" in operands and (not dense or r1 or r2 or lo):
+        return pl
+    if M * (ld or N) * 2 >= 1 << 32 or (rb and (M + 2) * N * 2 >= 1 << 32):          # 32-bit epilogue offsets (row-bias: at most one row per M row)
+        return pl
+    if dense and N == BN and K <= 1280 and (r1 or r2):              # the short-K rule: generation 2's 256x160 tiles
+        return pl
+    sk_ok = not (dense and epi == 23) and not debug & 4
+    pl.band = 4 if N * K * 2 > 3 * 1024 * 1024 else 0
+    if tiles * 256 >= 200 * G:
+        pl.grid = G if tiles >= G else (tiles + 7) // 8 * 8
+        pl.schedule = "whole"
+        sk_shape = mode == "conv" or (tiles_n <= 2 and K >= 1280)
+        if sk_shape and sk_ok and tiles > G and tiles % G != 0:
+            rounds = -(-tiles // G)
+            if 1.0 - tiles / (G * rounds) > 0.04:
+                pl.dp_rounds = tiles // G - 1
+                pl.sk_tiles = tiles - G * pl.dp_rounds
+                pl.schedule = "tail"
+    else:
+        half_shape = tiles >= 8 and 2 * tiles <= G and (2 * tiles) % 8 == 0 and nk % 2 == 0 and K >= 8192
+        if not sk_ok or "geglu" in operands or not half_shape:
+            return pl
+        pl.grid, pl.sk_tiles, pl.schedule = 2 * tiles, tiles, "half"
+    pl.taken = True
+    Gk = pl.grid                                                    # the kernel's G is its grid
+    for b in range(Gk):
+        seq0 = (b & 7) * (Gk >> 3) + (b >> 3)
+        items = []
+        if pl.sk_tiles:
+            U = pl.sk_tiles * nk
+            u0, u1 = seq0 * U // Gk, (seq0 + 1) * U // Gk
+            (tA, kA), (tB, kB) = divmod(u0, nk), divmod(u1, nk)
+            n_sk, n_dp = (tB - tA) + (kB > 0), pl.dp_rounds
+            if u1 - u0 + n_dp * nk == 0:
+                n_sk = 0
+        else:
+            n_sk, n_dp = 0, ((tiles - 1 - seq0) // Gk + 1 if seq0 < tiles else 0)
+        for w in range(n_sk + n_dp):
+            if w < n_sk:
+                t = tA + w
+                items.append((pl.dp_rounds * Gk + t, kA if w == 0 else 0, kB if t == tB else nk))
+            else:
+                items.append(((w - n_sk) * Gk + seq0, 0, nk))
+        pl.items.append(items)
+    return pl
+
+
+# ----------------------------------------------------------------------------- the multi-round generation-3 cases
+# Same keys as GEN2_CASES (r2 may be "s" too).  schedule / band / dp_rounds / sk_tiles / tiles / per_wg (fewest, most work items of
+# a workgroup) are what gen3_plan must give at G = 256 (tests/test_cpu_gemm_gen3_cases.py).  Whole-tile schedule unless noted.
+GEN3_CASES = {
+    # nk = 1: every stream position ends a tile; bias + row-bias enter through init_acc; ragged last row tile
+    "G1": dict(kind="dense", tiles=392, per_wg=(1, 2), M=100100, N=320, K=64, rb=True),
+    # two tile columns, RES_LDS epilogue (EPI & 6): the next item's first K-tile is staged inside the epilogue; lo8 plane
+    "G2": dict(kind="dense", tiles=392, per_wg=(1, 2), M=50013, N=640, K=192, bias=False, rb=True, r1="s", split=True),
+    # three tile columns, nk = 2
+    "G3": dict(kind="dense", tiles=354, per_wg=(1, 2), M=30005, N=960, K=128, bias=False, r1="h", r2="h", coef=(0.7, 0.6, -1.5)),
+    # <0, 23>: the variant compiled without the tail split
+    "G4": dict(kind="dense", tiles=352, per_wg=(1, 2), M=45000, N=640, K=128, bias=False, rb=True, r1="s", r2="s", split=True,
+               epi="<0, 23>", debug=0),
+    # stream-K tail: every workgroup runs stream-K items and then one chained data-parallel tile
+    "G5": dict(kind="dense", tiles=548, per_wg=(3, 4), M=70013, N=640, K=1280, r1="s", split=True, schedule="tail", dp_rounds=1, sk_tiles=292),
+    # GEGLU: 8 tile columns, W = 1.6 MB (no band), n_out 1280, weight rows interleaved in 16s
+    "G6": dict(kind="dense", tiles=376, per_wg=(1, 2), M=12000, N=2560, K=320, geglu=True),
+    # banded tile order: one full and one ragged band (6 columns); a workgroup's two tiles lie in different bands
+    "G7": dict(kind="dense", tiles=354, per_wg=(1, 2), M=15000, N=1920, K=1024, r1="h", band=4),
+    # conv, nk = 9: 500 tiles lose 2.3 % <= 4 % of two rounds, so no tail
+    "G8": dict(kind="conv", tiles=500, per_wg=(1, 2), n=125, H=32, W=32, C=64, O=320, rb_imgs=1),
+    # ragged M, image seams inside tiles
+    "G8u": dict(kind="conv", tiles=500, per_wg=(1, 2), n=125, H=33, W=31, C=64, O=320, rb_imgs=3, pieces=False),
+    # per-row (dy, dx) codes and the a2 switch rebuilt at each tile change (100 images: 500 tiles, as G8, keep the plan whole-tile)
+    "G9": dict(kind="conv", tiles=500, per_wg=(1, 2), n=100, H=16, W=20, C=64, c2=64, O=320, up=1, r1="h"),
+    # conv with the stream-K tail and the RES_LDS epilogue
+    "G10": dict(kind="conv", tiles=544, per_wg=(3, 3), n=136, H=32, W=32, C=64, O=320, rb_imgs=1, r1="s", split=True,
+                schedule="tail", dp_rounds=1, sk_tiles=288),
+    # tap mask per tile, nk = 3
+    "G11": dict(kind="temporal", tiles=500, per_wg=(1, 2), B=5, T=4, P=6400, C=64, O=320, rb=True, r1="s", split=True),
+    # ragged, seams inside tiles
+    "G11u": dict(kind="temporal", tiles=501, per_wg=(1, 2), B=5, T=4, P=6403, C=64, O=320, rb=True, r1="h", pieces=False),
+    # the 256-wide instance, Downsample2D(padding=0) addressing, nk = 18, stream-K tail (110 images = 550 tiles: 150 images = 750 tiles
+    # lose 2.3 % of three rounds and run whole tiles)
+    "G12": dict(kind="conv", tiles=550, per_wg=(3, 4), n=110, H=64, W=80, C=128, O=256, stride=2, shift=1,
+                schedule="tail", dp_rounds=1, sk_tiles=294),
+}
+
+
+def case_operands(c):
+    """the operand set of a case, as gen3_epi / gen3_plan take it"""
+    s = set()
+    if c.get("rb") or c.get("rb_imgs"):
+        s.add("rb")
+    if c.get("r1"):
+        s.add("r1")
+    if c.get("r2"):
+        s.add("r2")
+    if c.get("split") or "s" in (c.get("r1"), c.get("r2")):
+        s.add("lo")
+    if c.get("geglu"):
+        s.add("geglu")
+    return s
+
+
+def gen3_case_plan(c, G, debug=0, rows=None):
+    """gen3_plan of a GEN3_CASES entry (of its first `rows` rows when given)"""
+    M, N, K, _, _, _ = case_dims(c)
+    return gen3_plan(M if rows is None else rows, N, K, c["kind"], case_operands(c), G, debug)
+
+
+def gen3_piece_ranges(c, G):
+    """Row ranges [(r0, r1)] covering [0, M), or None for a case that cannot tile-align: each starts at a multiple of 256 rows and of
+    the case's unit (rows of one image / batch element) and holds at least 200 * G / 256 and at most G tiles, so that plan3 takes
+    it and it runs as one round without a tail.  The last range is the last such window that ends at M: it may overlap the one
+    before it."""
+    if not c.get("pieces", True):
+        return None
+    M, N, _, _, unit, _ = case_dims(c)
+    BM, BN, _, _ = gen3_family(N)
+    tiles_n = N // BN
+    step = unit * BM // math.gcd(unit, BM)
+    lo_tiles = (200 * G + 255) // 256
+    lo_rows = (lo_tiles + tiles_n - 1) // tiles_n                   # fewest tile rows of a piece
+    rows = G // (step // BM * tiles_n) * step                       # most rows of a piece
+    assert rows > 0 and rows // BM >= lo_rows, (rows, step, lo_rows)
+    out, r0 = [], 0
+    while -(-(M - r0) // BM) * tiles_n > G:
+        out.append((r0, r0 + rows))
+        r0 += rows
+    if -(-(M - r0) // BM) < lo_rows:
+        r0 = (M - (lo_rows - 1) * BM - 1) // step * step
+    assert r0 >= 0 and lo_rows <= -(-(M - r0) // BM) <= G // tiles_n, (r0, M)
+    out.append((r0, M))
+    return out
+
+
+def gen3_rowbias_rows(c, G):
+    """rows per row-bias group of a dense GEN3_CASES entry: every piece start is a group start, and groups change inside tiles
+    (32 x the odd part of the starts' common divisor)"""
+    g = 0
+    for r0, _ in gen3_piece_ranges(c, G):
+        g = math.gcd(g, r0)
+    assert g > 0
+    while g % 64 == 0:
+        g //= 2
+    return g

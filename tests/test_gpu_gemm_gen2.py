@@ -1,7 +1,8 @@
 """-m gpu: the generation-2 GEMM (gemm2_kernel, 256x160 and 128x256 tiles) on MULTI-ROUND persistent schedules: more tiles than
 workgroups, so that a workgroup's K-tile stream crosses output tiles -- the loader changes tile mid-stream, the epilogue patch
 sits in the ring slot just freed, and the counted vmcnt waits after a full tile assume the epilogue's exact store count.  (The
-small generation-2 problems of test_gpu_ops.py and test_gpu_gemm_variants.py run at most one tile per workgroup.)
+small generation-2 problems of test_gpu_ops.py and test_gpu_gemm_variants.py run at most one tile per workgroup; generation 3's
+chained tiles get the same treatment in test_gpu_gemm_gen3_rounds.py.)
 
 Per case of gemm_cases.GEN2_CASES, under the default launch grid (G = ew_get_cu_budget(); every case asserts tiles > G):
   1. guards: output and lo8 plane in guarded buffers, two prefills bit-identical, nothing written outside the view;

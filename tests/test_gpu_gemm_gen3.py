@@ -1,9 +1,12 @@
 """-m gpu: the generation-3 GEMM (256x320 tile; taken when N % 320 == 0 and the problem fills the chip) against a plain
 PyTorch fp32 reference AND against the independent generation-1 kernels, on problems large enough to be routed to it:
 ragged M (edge tiles), every epilogue operand set that occurs in the U-Net, all three A addressing modes (dense, conv3x3 with
-stride / upsample / dual source, temporal 3-tap).  test_gpu_ops.py's GEMM cases are small and run on generation 2, at most one
-tile per workgroup; generation 2's chained-tile (multi-round) schedules are covered by test_gpu_gemm_gen2.py.  The helpers shared
-with that file (guarded, the fp64 conv references) live in gemm_cases.py."""
+stride / upsample / dual source, temporal 3-tap).  Most cases here are sized to about 200 tiles on 256 workgroups, one tile per
+workgroup, and the stream-K test compares the kernel with its own whole-tile twin: generation 3's chained tiles (multi-round
+schedules, banded order, stream-K tail then data-parallel tile) are covered by test_gpu_gemm_gen3_rounds.py against fp64, generation 1
+and single-round pieces.  test_gpu_ops.py's GEMM cases are small and run on generation 2, at most one tile per workgroup;
+generation 2's multi-round schedules are covered by test_gpu_gemm_gen2.py.  The helpers shared with those files (guarded, the fp64
+conv references) live in gemm_cases.py."""
 import ctypes
 import math
 
