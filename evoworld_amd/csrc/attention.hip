@@ -8,10 +8,13 @@
 //    layout yields, and the V^T tile is written to LDS in that same order, so no cross-lane shuffle of P
 //    is needed.  V arrives TRANSPOSED from the projection GEMM (swapped-operand ew_gemm_f16), so the PV
 //    A-operand is a plain ds_read_b128.
-//  * ew_attn_temporal_f16: attention over the frame axis (T<=64) for every (batch, pixel, head): one wave per
+//  * ew_attn_temporal_f16: attention over the frame axis for every (batch, pixel, head): one wave per
 //    problem, coalesced traffic staged through wave-private LDS, the same swapped MFMA products.  It is
 //    HBM-bound (0.13 TFLOP per forward vs ~1.2 GB of q/k/v per call at level 0); the [B*T,S,C]<->[B*S,T,C]
-//    regroup of the reference is pure addressing.
+//    regroup of the reference is pure addressing.  Three kernels: attn_temporal_kernel (T <= 32) and
+//    attn_temporal64_kernel (32 < T <= 64) here; attn_temporal_long_kernel (T > 64: keys streamed in blocks of
+//    32 with an online softmax) in attn_temporal_long.hip, a translation unit of its own so that the two
+//    kernels here keep their machine code.
 // Reference call sites: diffusers AttnProcessor2_0 / F.scaled_dot_product_attention inside
 // BasicTransformerBlock.attn1 and TemporalBasicTransformerBlock.attn1, instantiated through
 // evoworld/trainer/unet_plucker.py:13,161-233.
@@ -600,11 +603,13 @@ extern "C" ew_status ew_attn_spatial_log2_f16(const void* q, const void* k, cons
 extern "C" ew_status ew_attn_temporal_f16(const void* q, const void* k, const void* v, void* o, int B, int T, int S,
                                           int heads, int ld, int ld_o, float scale, void* stream) {
     EW_REQUIRE(q && k && v && o, "ew_attn_temporal_f16: null pointer");
-    EW_REQUIRE(B > 0 && S > 0 && heads > 0 && T > 0 && T <= 64, "ew_attn_temporal_f16: need 0 < T <= 64 (T=%d)", T);
+    EW_REQUIRE(B > 0 && S > 0 && heads > 0 && T > 0, "ew_attn_temporal_f16: need T > 0 (T=%d)", T);
     EW_REQUIRE(ld % 8 == 0 && ld_o % 8 == 0, "ew_attn_temporal_f16: strides must be 16-byte aligned");
     const long long n_prob = (long long)B * S * heads;
     const long long nblk = (n_prob + 3) / 4;
     EW_REQUIRE(nblk < 0x7fffffffLL, "ew_attn_temporal_f16: grid too large");
+    if (T > 64)                                                     // key-streaming kernel, any T (attn_temporal_long.hip)
+        return ew_attn_temporal_long_launch(q, k, v, o, B, T, S, heads, ld, ld_o, scale, n_prob, (unsigned)nblk, stream);
     if (T > 32) {
         const size_t lds = 4 * 3 * 64 * 144;                        // 110,592 B
         static std::atomic<unsigned long long> attr_mask{0};                   // per (kernel instantiation, device)

@@ -18,6 +18,9 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 void ew_set_error(const char* fmt, ...);
 int ew_cu_budget();                   // CUs the persistent kernels may assume (runtime.cpp; 256 unless ew_set_cu_budget changed it)
 ew_status ew_check_launch(const char* what);
+// T > 64 leg of ew_attn_temporal_f16 (attn_temporal_long.hip; the caller has validated the arguments and sized the grid)
+ew_status ew_attn_temporal_long_launch(const void* q, const void* k, const void* v, void* o, int B, int T, int S, int heads, int ld,
+                                       int ld_o, float scale, long long n_prob, unsigned nblk, void* stream);
 
 #define EW_REQUIRE(cond, ...)                    \
     do {                                         \

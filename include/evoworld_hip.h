@@ -218,9 +218,12 @@ ew_status ew_attn_spatial_f16(const void* q, const void* k, const void* vt, void
 ew_status ew_attn_spatial_log2_f16(const void* q, const void* k, const void* vt, void* o, int n_seq, int S, int heads,
                                    int ld_qk, long long ld_vt, int ld_o, void* stream);
 
-/* Temporal self-attention core over the frame axis (T <= 64, head_dim 64; T <= 32 runs the one-block kernel) on frame-major tokens
+/* Temporal self-attention core over the frame axis (any T > 0, head_dim 64) on frame-major tokens
  * [B, T, S, *]: sequence (b, s) attends over t -- the [B*T,S,C] <-> [B*S,T,C] regroup of
  * TemporalBasicTransformerBlock is done by addressing, not by a copy.  q,k,v row stride ld; o row stride ld_o.
+ * Three kernels, one wave per (b, s, head) each: T <= 32 the one-block kernel; 32 < T <= 64 the 2x2-block kernel with the whole
+ * problem resident in LDS; T > 64 the key-streaming kernel (32-query blocks, keys / values in blocks of 32, online softmax; LDS
+ * use independent of T).
  * Replaces SDPA in TemporalBasicTransformerBlock.attn1. */
 ew_status ew_attn_temporal_f16(const void* q, const void* k, const void* v, void* o, int B, int T, int S, int heads,
                                int ld, int ld_o, float scale, void* stream);

@@ -1,8 +1,43 @@
-"""Stand-alone timing of ew_attn_spatial_f16 at the level-0 shape (250 problems x S=9216 x 64) for counter runs."""
+"""Stand-alone timing of ew_attn_spatial_f16 at the level-0 shape (250 problems x S=9216 x 64) for counter runs.
+With --temporal T [T ...]: the temporal core (ew_attn_temporal_f16) at the level-0 shape instead (B = 2, S = 72*128, 5 heads, ld = 960, ld_o = 320;
+env B, S) at each frame count T, any T > 0, on random data, in interleaved rounds: ms and GB/s of algorithmic bytes (q, k, v read once, o written
+once)."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from evoworld_amd import ops
+
+
+def temporal(frames):
+    B, S, heads = int(os.environ.get("B", 2)), int(os.environ.get("S", 72 * 128)), 5
+    C = heads * 64
+    iters = int(os.environ.get("ITERS", 20))
+    g = torch.Generator(device="cuda").manual_seed(0)
+    bufs = {}
+    for T in frames:
+        rows = B * T * S
+        bufs[T] = (torch.randn(rows, 3 * C, generator=g, device="cuda", dtype=torch.float16), torch.empty(rows, C, dtype=torch.float16, device="cuda"))
+    for rep in range(int(os.environ.get("REPS", 3))):
+        for T in frames:
+            qkv, o = bufs[T]
+            fn = lambda: ops.attn_temporal(qkv, qkv[:, C:], qkv[:, 2 * C:], o, B, T, S, heads, 3 * C, C)
+            for _ in range(2):
+                fn()
+            torch.cuda.synchronize()
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(iters):
+                fn()
+            e.record()
+            torch.cuda.synchronize()
+            ms = s.elapsed_time(e) / iters
+            print(f"attn_temporal B={B} T={T} S={S} h={heads}: {ms:.3f} ms  {B * T * S * 4 * C * 2 / ms / 1e6:.0f} GB/s", flush=True)
+        assert all(bool(torch.isfinite(bufs[T][1][:4096]).all()) for T in frames)
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "--temporal":
+    temporal([int(a) for a in sys.argv[2:]] or [64, 97, 128])
+    sys.exit(0)
 n_seq, S, heads = int(os.environ.get("NSEQ", 50)), int(os.environ.get("S", 9216)), 5
 C, rows = heads * 64, n_seq * S
 g = torch.Generator().manual_seed(0)
