@@ -9,6 +9,11 @@
 # FVD, the styleganv method at every clip length from 10 frames; FVD_CHANNEL_ORDER (default bgr, as the reference feeds its network; rgb).
 # LATENT_MSE_WEIGHTS (optional: a state dict in timm inception_v4's key layout, as .safetensors or a torch checkpoint) adds latent_mse
 # and loop_closure_latent_mse (the last frame alone); LATENT_MSE_CHANNEL_ORDER (default bgr, as the reference feeds its network; rgb).
+# WS_METRICS=1 adds the latitude-weighted forms for equirectangular frames (a row counts with the cosine of its latitude; not in the
+# reference): ws_psnr and ws_ssim, and ws_lpips when LPIPS_WEIGHTS is set.
+# PROJECTION=cube scores every clip on its six 90-degree perspective viewports (front, right, back, left, up, down: each episode and face
+# one video of every selected metric) instead of the flat panorama; VIEWPORT_SIZE (default: frame width / 4) is a viewport's side.  It
+# cannot be combined with WS_METRICS: latitude weights mean nothing on a perspective face.
 # PAIR_BY_NAME (default: true for SEGMENT_ID > 0) pairs the frame files both folders share: a later segment holds 24 generated and
 # 25 ground-truth frames, on which the reference's shape assertion fails.
 set -e
@@ -34,5 +39,11 @@ METRICS=psnr,ssim
 [ -n "$FVD_WEIGHTS" ] && METRICS=$METRICS,fvd && CMD="$CMD --fvd_weights $FVD_WEIGHTS --fvd_channel_order ${FVD_CHANNEL_ORDER:-bgr}"
 [ -n "$LATENT_MSE_WEIGHTS" ] && METRICS=$METRICS,latent_mse,loop_closure_latent_mse \
   && CMD="$CMD --latent_mse_weights $LATENT_MSE_WEIGHTS --latent_mse_channel_order ${LATENT_MSE_CHANNEL_ORDER:-bgr}"
+if [ "${WS_METRICS:-0}" = 1 ]; then
+  METRICS=$METRICS,ws_psnr,ws_ssim
+  [ -n "$LPIPS_WEIGHTS" ] && METRICS=$METRICS,ws_lpips
+fi
+[ -n "$PROJECTION" ] && CMD="$CMD --projection $PROJECTION"
+[ -n "$VIEWPORT_SIZE" ] && CMD="$CMD --viewport_size $VIEWPORT_SIZE"
 CMD="$CMD --metrics $METRICS"
 python $CMD

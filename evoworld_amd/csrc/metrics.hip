@@ -1,4 +1,5 @@
-// metrics.hip -- per-frame PSNR / SSIM of video pairs and the 8-bit map of the ground-truth segment dumps (ABI 12).
+// metrics.hip -- per-frame PSNR / SSIM of video pairs and the 8-bit map of the ground-truth segment dumps (ABI 12); their
+// row-weighted forms for equirectangular frames, WS-PSNR / WS-SSIM (ABI 18: ew_video_metrics_ws, no counterpart in the reference).
 // Reference: evoworld/metrics/other_metrics/calculate_psnr.py:6-15, calculate_ssim.py:6-40 (run by calculate_all_metrics.py:222-226
 // on uint8 / 255.0), unified_loop_consistency.py:87-93,437-439 (tensor_to_pil of the ground-truth frames).
 // Compiled with -ffp-contract=off: the float32 difference and square of the PSNR, and the fp64 moment arithmetic of the SSIM map,
@@ -9,6 +10,9 @@
 // the window and evaluates the SSIM map at the tile's valid outputs.  The tile's own 24x32 pixels (the whole frame over all tiles)
 // give the squared error.  Partial sums go to the workspace in a fixed tree order, and a second kernel sums each frame's tiles in
 // a fixed order: no atomics, two calls are bit-identical.
+// The weighted form is the same kernel under a template flag: the tile's rows of the caller's fp64 weights are staged next to the
+// pixels, a squared error is multiplied by its row's weight and an SSIM value by the weight of its window's CENTRE row (output row
+// i sits on image row i + 5), both in fp64 before the sum.  The planar instantiation has no weighted operation in it.
 #include "common.h"
 #include <math.h>
 
@@ -37,24 +41,29 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
     return r;
 }
 
+template <bool WS>
 __global__ __launch_bounds__(NT) void metrics_tile_kernel(const void* __restrict__ a, const void* __restrict__ b, int layout, int C,
                                                           int H, int W, int tiles_x, int do_sse, int do_ssim, U8Table tab,
-                                                          Gauss11 gk, double* __restrict__ part) {
+                                                          Gauss11 gk, const double* __restrict__ row_w, double* __restrict__ part) {
     __shared__ float s_tab[256];
     __shared__ float s_a[IH][IW], s_b[IH][IW];
     __shared__ double s_h[5][IH][TW];
     __shared__ double s_red[NT];
     __shared__ double s_g[11];                             // the taps from LDS: held in SGPRs they spilled
+    __shared__ double s_w[WS ? IH : 1];                    // weights of the staged rows (image rows oy .. oy + IH - 1; 0 below the frame)
     const int t = threadIdx.x;
     const int tile = blockIdx.x, f = blockIdx.y;
     const int oy = (tile / tiles_x) * TH, ox = (tile % tiles_x) * TW;
     const int Ho = H - 10, Wo = W - 10;
     s_tab[t] = tab.v[t];
     if (t < 11) s_g[t] = gk.g[t];
+    if constexpr (WS) {
+        if (t < IH) s_w[t] = oy + t < H ? row_w[oy + t] : 0.0;
+    }
     double sse = 0.0;
     double ssim_c[3] = {0.0, 0.0, 0.0};
     for (int c = 0; c < C; ++c) {
-        __syncthreads();                                   // s_tab ready / previous channel's s_a, s_b, s_h consumed
+        __syncthreads();                                   // s_tab, s_w ready / previous channel's s_a, s_b, s_h consumed
         for (int i = t; i < IH * IW; i += NT) {
             const int r = i / IW, q = i - r * IW;
             const int y = oy + r, x = ox + q;
@@ -80,7 +89,8 @@ __global__ __launch_bounds__(NT) void metrics_tile_kernel(const void* __restrict
                 if (oy + r < H && ox + q < W) {
                     const float d = s_a[r][q] - s_b[r][q];
                     const float d2 = d * d;
-                    sse += (double)d2;
+                    if constexpr (WS) sse += s_w[r] * (double)d2;
+                    else sse += (double)d2;
                 }
             }
         }
@@ -119,7 +129,9 @@ __global__ __launch_bounds__(NT) void metrics_tile_kernel(const void* __restrict
                 const double C1 = 0.01 * 0.01, C2 = 0.03 * 0.03;
                 const double m1s = m1 * m1, m2s = m2 * m2, m12 = m1 * m2;
                 const double s1 = e11 - m1s, s2 = e22 - m2s, s12 = e12 - m12;
-                acc += ((2.0 * m12 + C1) * (2.0 * s12 + C2)) / ((m1s + m2s + C1) * (s1 + s2 + C2));
+                const double v = ((2.0 * m12 + C1) * (2.0 * s12 + C2)) / ((m1s + m2s + C1) * (s1 + s2 + C2));
+                if constexpr (WS) acc += s_w[r + 5] * v;   // the window's centre row
+                else acc += v;
             }
         }
         ssim_c[c] = acc;
@@ -134,11 +146,18 @@ __global__ __launch_bounds__(NT) void metrics_tile_kernel(const void* __restrict
 }
 
 // one block per frame: the tiles' partials in a fixed order -> sse[f] = sum of squared errors, ssim[f] = mean over channels of the
-// mean SSIM map (np.array(ssims).mean() of per-channel ssim_map.mean(): ((m0 + m1) + m2) / 3)
+// mean SSIM map (np.array(ssims).mean() of per-channel ssim_map.mean(): ((m0 + m1) + m2) / 3).  With row_w (the weighted form) the
+// divisor is n_valid (there W - 10, the windows per row) times the weights of the H - 10 centre rows, summed here in a fixed order.
 __global__ __launch_bounds__(NT) void metrics_reduce_kernel(const double* __restrict__ part, int ntiles, int C, double n_valid,
-                                                            double* __restrict__ sse, double* __restrict__ ssim) {
+                                                            const double* __restrict__ row_w, int H, double* __restrict__ sse,
+                                                            double* __restrict__ ssim) {
     __shared__ double s_red[NT];
     const int f = blockIdx.x, t = threadIdx.x;
+    if (row_w && ssim) {
+        double v = 0.0;
+        for (int i = t; i < H - 10; i += NT) v += row_w[i + 5];
+        n_valid = n_valid * block_sum(v, s_red);
+    }
     const double* p = part + (long long)f * ntiles * NQ;
     double tot[NQ];
     for (int k = 0; k < NQ; ++k) {
@@ -178,18 +197,22 @@ extern "C" size_t ew_video_metrics_workspace_bytes(int F, int C, int H, int W) {
     return (size_t)F * tiles_of(H, W, &tx) * NQ * sizeof(double);
 }
 
-extern "C" ew_status ew_video_metrics(const void* a, const void* b, int layout, int F, int C, int H, int W, int what, double* sse,
-                                      double* ssim, void* workspace, void* stream) {
-    EW_REQUIRE(a && b && workspace, "ew_video_metrics: NULL input or workspace");
-    EW_REQUIRE(layout == 0 || layout == 1, "ew_video_metrics: layout %d (0: uint8 [F,H,W,C], 1: fp32 [F,C,H,W])", layout);
-    EW_REQUIRE(C == 1 || C == 3, "ew_video_metrics: C = %d (the reference's SSIM takes 1 or 3 channels)", C);
-    EW_REQUIRE(F > 0 && H > 0 && W > 0, "ew_video_metrics: F, H, W = %d, %d, %d must be positive", F, H, W);
-    EW_REQUIRE(what >= 1 && what <= 3, "ew_video_metrics: what = %d (bit 0: SSE, bit 1: SSIM)", what);
+namespace {
+
+// both entry points: `name` prefixes the refusals; `weighted` selects the row-weighted instantiation, which needs row_w
+ew_status video_metrics_launch(const char* name, const void* a, const void* b, int layout, int F, int C, int H, int W, int what,
+                               const double* row_w, bool weighted, double* sse, double* ssim, void* workspace, void* stream) {
+    EW_REQUIRE(a && b && workspace, "%s: NULL input or workspace", name);
+    EW_REQUIRE(layout == 0 || layout == 1, "%s: layout %d (0: uint8 [F,H,W,C], 1: fp32 [F,C,H,W])", name, layout);
+    EW_REQUIRE(C == 1 || C == 3, "%s: C = %d (the reference's SSIM takes 1 or 3 channels)", name, C);
+    EW_REQUIRE(F > 0 && H > 0 && W > 0, "%s: F, H, W = %d, %d, %d must be positive", name, F, H, W);
+    EW_REQUIRE(what >= 1 && what <= 3, "%s: what = %d (bit 0: SSE, bit 1: SSIM)", name, what);
+    EW_REQUIRE(!weighted || row_w, "%s: NULL row_w (one fp64 weight per image row, on the device)", name);
     const int do_sse = what & 1, do_ssim = (what >> 1) & 1;
-    EW_REQUIRE(!do_sse || sse, "ew_video_metrics: SSE asked for with a NULL output");
-    EW_REQUIRE(!do_ssim || ssim, "ew_video_metrics: SSIM asked for with a NULL output");
-    EW_REQUIRE(!do_ssim || (H >= 11 && W >= 11), "ew_video_metrics: SSIM needs H, W >= 11 (got %d x %d)", H, W);
-    EW_REQUIRE((long long)H * W <= (1LL << 31) / 4, "ew_video_metrics: frame of %d x %d too large", H, W);
+    EW_REQUIRE(!do_sse || sse, "%s: SSE asked for with a NULL output", name);
+    EW_REQUIRE(!do_ssim || ssim, "%s: SSIM asked for with a NULL output", name);
+    EW_REQUIRE(!do_ssim || (H >= 11 && W >= 11), "%s: SSIM needs H, W >= 11 (got %d x %d)", name, H, W);
+    EW_REQUIRE((long long)H * W <= (1LL << 31) / 4, "%s: frame of %d x %d too large", name, H, W);
     U8Table tab;
     for (int k = 0; k < 256; ++k) tab.v[k] = (float)k / 255.0f;
     // cv2.getGaussianKernel(11, 1.5) for CV_64F: t_i = exp(-0.5 / sigma^2 * x_i^2), x_i = i - 5, then t_i * (1 / sum t)
@@ -206,14 +229,33 @@ extern "C" ew_status ew_video_metrics(const void* a, const void* b, int layout, 
     const int ntiles = tiles_of(H, W, &tiles_x);
     hipStream_t st = (hipStream_t)stream;
     double* part = (double*)workspace;
-    hipLaunchKernelGGL(metrics_tile_kernel, dim3(ntiles, F), dim3(NT), 0, st, a, b, layout, C, H, W, tiles_x, do_sse, do_ssim, tab, gk,
-                       part);
+    if (weighted)
+        hipLaunchKernelGGL(metrics_tile_kernel<true>, dim3(ntiles, F), dim3(NT), 0, st, a, b, layout, C, H, W, tiles_x, do_sse, do_ssim, tab,
+                           gk, row_w, part);
+    else
+        hipLaunchKernelGGL(metrics_tile_kernel<false>, dim3(ntiles, F), dim3(NT), 0, st, a, b, layout, C, H, W, tiles_x, do_sse, do_ssim, tab,
+                           gk, (const double*)nullptr, part);
     ew_status s = ew_check_launch("metrics_tile_kernel");
     if (s != EW_OK) return s;
-    const double n_valid = do_ssim ? (double)(H - 10) * (double)(W - 10) : 1.0;
-    hipLaunchKernelGGL(metrics_reduce_kernel, dim3(F), dim3(NT), 0, st, part, ntiles, C, n_valid, do_sse ? sse : nullptr,
-                       do_ssim ? ssim : nullptr);
+    // planar: the valid outputs of a frame; weighted: the windows per row, times the centre rows' weights in the reduce kernel
+    const double n_valid = !do_ssim ? 1.0 : weighted ? (double)(W - 10) : (double)(H - 10) * (double)(W - 10);
+    hipLaunchKernelGGL(metrics_reduce_kernel, dim3(F), dim3(NT), 0, st, part, ntiles, C, n_valid, weighted ? row_w : (const double*)nullptr, H,
+                       do_sse ? sse : nullptr, do_ssim ? ssim : nullptr);
     return ew_check_launch("metrics_reduce_kernel");
+}
+
+}  // namespace
+
+extern "C" ew_status ew_video_metrics(const void* a, const void* b, int layout, int F, int C, int H, int W, int what, double* sse,
+                                      double* ssim, void* workspace, void* stream) {
+    return video_metrics_launch("ew_video_metrics", a, b, layout, F, C, H, W, what, nullptr, false, sse, ssim, workspace, stream);
+}
+
+extern "C" size_t ew_video_metrics_ws_workspace_bytes(int F, int C, int H, int W) { return ew_video_metrics_workspace_bytes(F, C, H, W); }
+
+extern "C" ew_status ew_video_metrics_ws(const void* a, const void* b, int layout, int F, int C, int H, int W, int what,
+                                         const double* row_w, double* wsse, double* wssim, void* workspace, void* stream) {
+    return video_metrics_launch("ew_video_metrics_ws", a, b, layout, F, C, H, W, what, row_w, true, wsse, wssim, workspace, stream);
 }
 
 extern "C" ew_status ew_gt_dump_map_u8(const uint8_t* src, uint8_t* dst, size_t n, void* stream) {

@@ -20,20 +20,26 @@ K_ALIGN = 64                                           # ew_gemm_f16 takes K in 
 MIN_SIZE = 31                                          # smallest H, W that leave every tap at least 1 x 1
 
 
-def upsample_mean_weights(n_in, n_out):
+def upsample_mean_weights(n_in, n_out, out_weights=None):
     """float64 [n_in]: how often F.interpolate(size=n_out, mode='bilinear', align_corners=False) counts each of n_in input samples
     along one axis, so that mean(upsample(m)) = sum_yx wy[y] wx[x] m[y,x] / (H W).  torch's index arithmetic:
-    src = max(0, (i + 0.5) * n_in / n_out - 0.5), i0 = floor(src), i1 = min(i0 + 1, n_in - 1).  The weights sum to n_out."""
+    src = max(0, (i + 0.5) * n_in / n_out - 0.5), i0 = floor(src), i1 = min(i0 + 1, n_in - 1).  The weights sum to n_out.
+    out_weights (float64 [n_out], optional): output sample i counts out_weights[i] times instead of once, so that
+    sum_i out_weights[i] upsample(m)[i] = sum_y w[y] m[y]; the weights then sum to sum(out_weights)."""
     if n_in < 1 or n_out < 1:
         raise ValueError(f"upsample_mean_weights: n_in, n_out = {n_in}, {n_out} must be positive")
+    if out_weights is not None:
+        out_weights = np.asarray(out_weights, dtype=np.float64)
+        if out_weights.shape != (n_out,):
+            raise ValueError(f"upsample_mean_weights: expected {n_out} output weights, got shape {out_weights.shape}")
     i = np.arange(n_out, dtype=np.float64)
     src = np.maximum(0.0, (i + 0.5) * (float(n_in) / float(n_out)) - 0.5)
     i0 = np.minimum(np.floor(src).astype(np.int64), n_in - 1)
     i1 = np.minimum(i0 + 1, n_in - 1)
     l1 = src - i0
     w = np.zeros(n_in, dtype=np.float64)
-    np.add.at(w, i0, 1.0 - l1)
-    np.add.at(w, i1, l1)
+    np.add.at(w, i0, (1.0 - l1) if out_weights is None else (1.0 - l1) * out_weights)
+    np.add.at(w, i1, l1 if out_weights is None else l1 * out_weights)
     return w
 
 
@@ -178,9 +184,11 @@ class LPIPSAlex:
             x = ops.maxpool3s2_relu(y) if POOL_AFTER[i] else y
         return taps
 
-    def __call__(self, a, b, channel_order="rgb", chunk=None):
+    def __call__(self, a, b, channel_order="rgb", chunk=None, row_weights=None):
         """a, b: uint8 [F,H,W,3] or fp32 [F,3,H,W] in [0,1] on the device (channels R, G, B) -> fp64 [F] on the device.
-        channel_order 'bgr' hands the network B, G, R planes, as the reference's cv2.imread frames reach it."""
+        channel_order 'bgr' hands the network B, G, R planes, as the reference's cv2.imread frames reach it.
+        row_weights (H values, optional; metrics.latitude_weights(H) gives WS-LPIPS of equirectangular frames): every tap's upsampled
+        map is averaged under one weight per image row, sum_taps sum_yx w[y] up(y,x) / (W sum_y w[y]), instead of uniformly."""
         from . import ops
         if a.shape != b.shape or a.dtype != b.dtype or a.device != b.device:
             raise ValueError(f"a {tuple(a.shape)} {a.dtype} on {a.device} and b {tuple(b.shape)} {b.dtype} on {b.device} differ")
@@ -189,6 +197,11 @@ class LPIPSAlex:
         F_ = a.shape[0]
         H, W = (a.shape[1], a.shape[2]) if a.dtype == torch.uint8 else (a.shape[2], a.shape[3])
         sizes = tap_sizes(H, W)
+        n_out = H * W
+        if row_weights is not None:
+            row_weights = ops.check_row_weights(row_weights, H)
+            n_out = W * float(row_weights.sum())
+            wy_rows = [torch.from_numpy(upsample_mean_weights(h, H, row_weights)).to(self.device) for h, _ in sizes]
         chunk = max(1, int(chunk or self.chunk))
         acc = torch.zeros(F_, dtype=torch.float64, device=a.device)
         for f0 in range(0, F_, chunk):
@@ -196,7 +209,9 @@ class LPIPSAlex:
             taps = self.features(torch.cat([a[f0:f0 + n], b[f0:f0 + n]]).contiguous(), channel_order)
             for i, t in enumerate(taps):
                 wy, wx = self._weights_for(*sizes[i], H, W)
-                ops.lpips_head(t[:n], t[n:], self.lin[i], wy, wx, H * W, acc[f0:f0 + n])
+                if row_weights is not None:
+                    wy = wy_rows[i]
+                ops.lpips_head(t[:n], t[n:], self.lin[i], wy, wx, n_out, acc[f0:f0 + n])
         ops.streamk_check()                        # results leave here: a timed-out stream-K hand-over in a convolution must not pass silently
         return acc
 

@@ -14,6 +14,13 @@ calculate_all_metrics.py:220-221 calls it, over timm inception_v4's 1536 pooled 
                                    [--metrics psnr,ssim,lpips --lpips_weights lpips_alex.safetensors]
                                    [--metrics psnr,ssim,fvd --fvd_weights i3d_pretrained_400.pt]
                                    [--metrics psnr,ssim,latent_mse,loop_closure_latent_mse --latent_mse_weights inception_v4.safetensors]
+                                   [--metrics psnr,ssim,ws_psnr,ws_ssim[,ws_lpips --lpips_weights ...]]
+                                   [--projection cube [--viewport_size 256]]
+
+The frames are equirectangular panoramas, which the metrics above score as flat images.  Two additions, neither of them in the
+reference, account for the sphere: the latitude-weighted WS-PSNR / WS-SSIM / WS-LPIPS (a row counts with the cosine of its latitude:
+ops.video_metrics_ws, LPIPSAlex's row_weights), and --projection cube, which scores six 90-degree perspective viewports of every clip
+(cube_viewports, through reprojection.Equi2Pers) with the unchanged planar metrics.
 """
 import argparse
 import json
@@ -37,14 +44,28 @@ NOT_COMPUTED = {
                                "despite the metric's name it does not use the SVD VAE",
 }
 SUPPORTED = ("psnr", "ssim")
+SPHERICAL = ("ws_psnr", "ws_ssim", "ws_lpips")      # latitude-weighted forms for equirectangular frames; ws_lpips needs --lpips_weights
+PROJECTIONS = ("equirect", "cube")
+CUBE_FACES = ("front", "right", "back", "left", "up", "down")
+# Equi2Pers rotations of the faces, radians: a positive yaw turns the view to the left, a positive pitch turns it up
+CUBE_ROTS = ({}, {"yaw": -math.pi / 2}, {"yaw": math.pi}, {"yaw": math.pi / 2}, {"pitch": math.pi / 2}, {"pitch": -math.pi / 2})
 
 
 def psnr_from_sse(sse, n):
-    """img_psnr of calculate_psnr.py:6-15 from the frame's squared-error sum over n = C*H*W elements."""
+    """img_psnr of calculate_psnr.py:6-15 from the frame's squared-error sum over n = C*H*W elements.  WS-PSNR is the same rule on the
+    weighted sum with n = C * W * sum_y w[y]."""
     mse = float(sse) / n
     if mse < 1e-10:
         return 100
     return 20 * math.log10(1 / math.sqrt(mse))
+
+
+def latitude_weights(H):
+    """fp64 [H]: the cosine of the latitude of each row's centre of an equirectangular frame, cos((y + 0.5 - H/2) pi / H): the share
+    of the sphere a pixel of that row covers, up to a constant (the WS-PSNR weights of 360-degree video evaluation)."""
+    if H < 1:
+        raise ValueError(f"latitude_weights: H = {H} must be positive")
+    return np.cos((np.arange(H, dtype=np.float64) + 0.5 - H / 2) * np.pi / H)
 
 
 def aggregate(results, video_setting):
@@ -91,6 +112,68 @@ def calculate_ssim(videos1, videos2):
     return aggregate(ssim, videos1[0].shape)
 
 
+def _per_frame_ws(videos1, videos2, what, row_w):
+    """_per_frame under row weights (default: latitude_weights(H)) -> (wsse, wssim, the weights)"""
+    from . import ops
+    if videos1.shape != videos2.shape:
+        raise AssertionError(f"video shapes differ: {tuple(videos1.shape)} vs {tuple(videos2.shape)}")
+    B, T, C, H, W = videos1.shape
+    row_w = latitude_weights(H) if row_w is None else ops.check_row_weights(row_w, H)
+    a = videos1.reshape(B * T, C, H, W).to("cuda", torch.float32).contiguous()
+    b = videos2.reshape(B * T, C, H, W).to("cuda", torch.float32).contiguous()
+    wsse, wssim = ops.video_metrics_ws(a, b, row_w, what)
+    cpu = lambda x: None if x is None else x.cpu().numpy().reshape(B, T)
+    return cpu(wsse), cpu(wssim), row_w
+
+
+def calculate_ws_psnr(videos1, videos2, row_w=None):
+    """WS-PSNR of equirectangular videos: [B,T,C,H,W] in [0,1] -> calculate_psnr's result dict, every squared error weighted by the
+    cosine of its row's latitude (row_w: other weights, one per row)."""
+    from . import ops
+    wsse, _, w = _per_frame_ws(videos1, videos2, ops.METRIC_SSE, row_w)
+    n_w = videos1.shape[2] * videos1.shape[4] * float(w.sum())
+    return aggregate([[psnr_from_sse(s, n_w) for s in row] for row in wsse], videos1[0].shape)
+
+
+def calculate_ws_ssim(videos1, videos2, row_w=None):
+    """WS-SSIM of equirectangular videos (C = 1 or 3; H, W >= 11): calculate_ssim's result dict, every window of the SSIM map
+    weighted by the cosine of its centre row's latitude (row_w: other weights, one per row)."""
+    from . import ops
+    _, wssim, _ = _per_frame_ws(videos1, videos2, ops.METRIC_SSIM, row_w)
+    return aggregate(wssim, videos1[0].shape)
+
+
+def video_metrics_ws_u8(gt, gen, what=3, row_w=None):
+    """uint8 [F,H,W,3] device tensors -> (ws_psnr, ws_ssim) numpy fp64 [F] (None where `what`, ops.METRIC_SSE | ops.METRIC_SSIM, does
+    not ask for it) under latitude_weights(H), or row_w."""
+    from . import ops
+    F_, H, W, C = gt.shape
+    row_w = latitude_weights(H) if row_w is None else ops.check_row_weights(row_w, H)
+    wsse, wssim = ops.video_metrics_ws(gt.contiguous(), gen.contiguous(), row_w, what)
+    n_w = C * W * float(row_w.sum())
+    p = None if wsse is None else np.array([psnr_from_sse(s, n_w) for s in wsse.cpu().numpy()], dtype=np.float64)
+    return p, None if wssim is None else wssim.cpu().numpy()
+
+
+def cube_viewports(frames_u8, size=None):
+    """Equirectangular frames uint8 [T,H,W,3] on the device -> their six 90-degree perspective viewports, uint8 [6,T,S,S,3] on the
+    device in the order of CUBE_FACES (S = size, default W // 4): reprojection.Equi2Pers(S, S, 90) at CUBE_ROTS, one launch per face
+    over the same panoramas."""
+    from .reprojection import Equi2Pers
+    if frames_u8.ndim != 4 or frames_u8.shape[-1] != 3 or frames_u8.dtype != torch.uint8:
+        raise ValueError(f"cube_viewports: expected uint8 [T,H,W,3] frames, got {frames_u8.dtype} {tuple(frames_u8.shape)}")
+    T, _, W, _ = frames_u8.shape
+    S = int(size) if size else W // 4
+    if S < 1:
+        raise ValueError(f"cube_viewports: viewport size {S} must be positive")
+    frames_u8 = frames_u8.contiguous()
+    e2p = Equi2Pers(height=S, width=S, fov_x=90.0)
+    out = torch.empty(6, T, S, S, 3, dtype=torch.uint8, device=frames_u8.device)
+    for k, rots in enumerate(CUBE_ROTS):
+        out[k] = e2p.batch(frames_u8, [rots] * T)
+    return out
+
+
 def calculate_lpips(videos1, videos2, model, channel_order="rgb"):
     """calculate_lpips(videos1, videos2, device) of calculate_lpips.py: [B,T,3,H,W] in [0,1] -> the reference's result dict, with
     `model` an evoworld_amd.lpips.LPIPSAlex.  channel_order 'bgr' feeds the network B, G, R planes as the reference's main does."""
@@ -122,7 +205,8 @@ def parse_args(argv=None):
     p.add_argument("--num_videos", type=int, default=100)
     p.add_argument("--test_length", type=int, default=25, help="parsed and ignored, as in the reference")
     p.add_argument("--metrics", type=str, default="psnr,ssim",
-                   help="comma-separated; psnr and ssim are computed, the others need networks this project lacks")
+                   help="comma-separated; psnr and ssim are computed, and so are their latitude-weighted forms ws_psnr and ws_ssim (and "
+                        "ws_lpips with --lpips_weights); the others need networks this project lacks")
     p.add_argument("--pair_by_name", action="store_true",
                    help="pair the last 25 file names both folders share (segments >= 1 hold 24 generated and 25 GT frames)")
     p.add_argument("--lpips_weights", type=str, nargs="+", default=None, metavar="PATH",
@@ -144,6 +228,10 @@ def parse_args(argv=None):
     p.add_argument("--latent_mse_channel_order", type=str, choices=("bgr", "rgb"), default="bgr",
                    help="bgr (default): the network sees B, G, R planes under the ImageNet mean and std of R, G, B, as in the reference, "
                         "whose cv2.imread frames are never swapped; rgb: the order Inception-v4 was trained on")
+    p.add_argument("--projection", type=str, choices=PROJECTIONS, default="equirect",
+                   help="equirect (default): the frames as they are; cube: every clip is scored on its six 90-degree perspective "
+                        "viewports (front, right, back, left, up, down), each (episode, face) one video of every selected metric")
+    p.add_argument("--viewport_size", type=int, default=None, metavar="N", help="side of a cube viewport (default: frame width / 4)")
     args = p.parse_args(argv)
     args.result_file = os.path.join(args.data_path, args.result_file)
     return args
@@ -152,17 +240,26 @@ def parse_args(argv=None):
 LATENT_METRICS = ("latent_mse", "loop_closure_latent_mse")
 
 
-def selected_metrics(spec, lpips_weights=False, fvd_weights=False, latent_mse_weights=False):
+def selected_metrics(spec, lpips_weights=False, fvd_weights=False, latent_mse_weights=False, projection="equirect"):
     """The metric names of --metrics.  lpips_weights / fvd_weights / latent_mse_weights: the user supplied LPIPS / I3D / Inception-v4
-    weights, which lifts the refusal of `lpips` / `fvd` / both latent MSEs."""
+    weights, which lifts the refusal of `lpips` and `ws_lpips` / `fvd` / both latent MSEs.  projection 'cube' refuses the ws_* names."""
+    if projection not in PROJECTIONS:
+        raise ValueError(f"projection {projection!r}: expected one of {', '.join(PROJECTIONS)}")
     names = [m.strip() for m in spec.split(",") if m.strip()]
     for m in names:
+        if m in SPHERICAL:
+            if projection == "cube":
+                raise ValueError(f"metric {m!r} weights the rows of an equirectangular frame by latitude, which means nothing on a "
+                                 f"perspective cube face: drop it or --projection cube")
+            if m == "ws_lpips" and not lpips_weights:
+                raise ValueError(f"metric {m!r} cannot be computed: it {NOT_COMPUTED['lpips']}")
+            continue
         if (m == "lpips" and lpips_weights) or (m == "fvd" and fvd_weights) or (m in LATENT_METRICS and latent_mse_weights):
             continue
         if m in NOT_COMPUTED:
             raise ValueError(f"metric {m!r} cannot be computed: it {NOT_COMPUTED[m]}")
         if m not in SUPPORTED:
-            raise ValueError(f"unknown metric {m!r} (computed: {', '.join(SUPPORTED)}; not available: {', '.join(NOT_COMPUTED)})")
+            raise ValueError(f"unknown metric {m!r} (computed: {', '.join(SUPPORTED + SPHERICAL[:2])}; not available: {', '.join(NOT_COMPUTED)})")
     if not names:
         raise ValueError("--metrics selects nothing")
     return names
@@ -202,9 +299,12 @@ def evaluate(args, device="cuda"):
     to the device as uint8.  Returns (result dict, timing dict)."""
     weights, fvd_weights = getattr(args, "lpips_weights", None), getattr(args, "fvd_weights", None)
     latent_weights = getattr(args, "latent_mse_weights", None)
-    names = selected_metrics(args.metrics, lpips_weights=bool(weights), fvd_weights=bool(fvd_weights), latent_mse_weights=bool(latent_weights))
-    lpips_model, lpips_order, lpips = None, getattr(args, "lpips_channel_order", "bgr"), []
-    if "lpips" in names:
+    projection, viewport_size = getattr(args, "projection", "equirect"), getattr(args, "viewport_size", None)
+    names = selected_metrics(args.metrics, lpips_weights=bool(weights), fvd_weights=bool(fvd_weights), latent_mse_weights=bool(latent_weights),
+                             projection=projection)
+    ws_what = 1 * ("ws_psnr" in names) | 2 * ("ws_ssim" in names)                # ops.METRIC_SSE | ops.METRIC_SSIM
+    lpips_model, lpips_order, lpips, ws_lpips = None, getattr(args, "lpips_channel_order", "bgr"), [], []
+    if "lpips" in names or "ws_lpips" in names:
         from .lpips import LPIPSAlex
         lpips_model = LPIPSAlex.from_files(weights, device)
     fvd_model, fvd_order, fvd_feats = None, getattr(args, "fvd_channel_order", "bgr"), ({}, {})     # {clip length: [logits per episode]}
@@ -218,7 +318,7 @@ def evaluate(args, device="cuda"):
     episodes = list_episode_folders(args.data_path, args.num_videos)
     if not episodes:
         raise ValueError(f"no episode folders under {args.data_path}")
-    psnr, ssim, shape = [], [], None
+    psnr, ssim, ws_psnr, ws_ssim, shape, n_videos = [], [], [], [], None, 0
     t_decode = t_device = 0.0
     with ThreadPoolExecutor(max_workers=min(MAX_DECODE_THREADS, os.cpu_count() or 1)) as pool:
         for ep in episodes:
@@ -233,45 +333,63 @@ def evaluate(args, device="cuda"):
                 raise ValueError(f"episode {ep}: frames {gt.shape} differ from the first episode's {shape}")
             shape = gt.shape
             gt_d, gen_d = torch.from_numpy(gt).to(device), torch.from_numpy(gen).to(device)
-            p, s = video_metrics_u8(gt_d, gen_d)
-            if lpips_model is not None:
-                lpips.append(lpips_model(gt_d, gen_d, lpips_order).cpu().numpy())
-            if fvd_model is not None:
-                if gt.shape[0] < 10:
-                    raise ValueError(f"episode {ep}: FVD compares clips of 10 frames and more, the folders hold {gt.shape[0]}")
-                for feats, clip in zip(fvd_feats, (gt_d, gen_d)):                # ground truth first, as the reference's main
-                    for L, v in fvd_mod.clip_features(fvd_model, clip, fvd_order).items():
-                        feats.setdefault(L, []).append(v)
-            if latent_model is not None:                                         # one pass per clip serves both metrics
-                for feats, clip in zip(latent_feats, (gt_d, gen_d)):
-                    feats.append(latent_model.features(clip, latent_order).cpu().numpy())
+            clips = [(gt_d, gen_d)]
+            if projection == "cube":                                             # every (episode, face) is one video of every metric
+                clips = list(zip(cube_viewports(gt_d, viewport_size), cube_viewports(gen_d, viewport_size)))
+            for gt_c, gen_c in clips:
+                p, s = video_metrics_u8(gt_c, gen_c)
+                psnr.append(p)
+                ssim.append(s)
+                if ws_what:
+                    wp, wsm = video_metrics_ws_u8(gt_c, gen_c, ws_what)
+                    ws_psnr.append(wp)
+                    ws_ssim.append(wsm)
+                if "lpips" in names:
+                    lpips.append(lpips_model(gt_c, gen_c, lpips_order).cpu().numpy())
+                if "ws_lpips" in names:
+                    ws_lpips.append(lpips_model(gt_c, gen_c, lpips_order, row_weights=latitude_weights(gt_c.shape[1])).cpu().numpy())
+                if fvd_model is not None:
+                    if gt.shape[0] < 10:
+                        raise ValueError(f"episode {ep}: FVD compares clips of 10 frames and more, the folders hold {gt.shape[0]}")
+                    for feats, clip in zip(fvd_feats, (gt_c, gen_c)):            # ground truth first, as the reference's main
+                        for L, v in fvd_mod.clip_features(fvd_model, clip, fvd_order).items():
+                            feats.setdefault(L, []).append(v)
+                if latent_model is not None:                                     # one pass per clip serves both metrics
+                    for feats, clip in zip(latent_feats, (gt_c, gen_c)):
+                        feats.append(latent_model.features(clip, latent_order).cpu().numpy())
+            n_videos += len(clips)
             t_device += time.perf_counter() - t1
             t_decode += t1 - t0
-            psnr.append(p)
-            ssim.append(s)
     T, H, W, C = shape
+    if projection == "cube":
+        H = W = int(viewport_size) if viewport_size else W // 4
     setting = torch.Size([T, C, H, W])
     result = {}
     if fvd_model is not None:
         from .ops import streamk_check
         streamk_check()                            # results leave here
         result["fvd"] = fvd_mod.fvd_result(*({L: np.stack(v) for L, v in f.items()} for f in fvd_feats),
-                                           torch.Size([len(episodes), C, T, H, W]))
+                                           torch.Size([n_videos, C, T, H, W]))
     if "ssim" in names:
         result["ssim"] = aggregate(ssim, setting)
     if "psnr" in names:
         result["psnr"] = aggregate(psnr, setting)
-    if lpips_model is not None:
+    if "lpips" in names:
         result["lpips"] = aggregate(lpips, setting)
     if latent_model is not None:
         f_gt, f_gen = (np.stack(f) for f in latent_feats)                        # [B,T,1536], ground truth first as the reference's main
         side = latent_mod.SIDE
         if "latent_mse" in names:
-            result["latent_mse"] = latent_mod.latent_mse_result(f_gt, f_gen, torch.Size([len(episodes) * T, C, side, side]))
+            result["latent_mse"] = latent_mod.latent_mse_result(f_gt, f_gen, torch.Size([n_videos * T, C, side, side]))
         if "loop_closure_latent_mse" in names:                                   # video[:, -1:]: does the last frame come back to the start?
             result["loop_closure_latent_mse"] = latent_mod.latent_mse_result(f_gt[:, -1:], f_gen[:, -1:],
-                                                                             torch.Size([len(episodes), C, side, side]))
-    computed = {"lpips": lpips_model is not None, "fvd": fvd_model is not None, **{m: m in result for m in LATENT_METRICS}}
+                                                                             torch.Size([n_videos, C, side, side]))
+    for name, rows in (("ws_psnr", ws_psnr), ("ws_ssim", ws_ssim), ("ws_lpips", ws_lpips)):
+        if name in names:
+            result[name] = aggregate(rows, setting)
+    if projection == "cube":
+        result["projection"], result["viewport_size"] = "cube", H
+    computed = {"lpips": "lpips" in result, "fvd": fvd_model is not None, **{m: m in result for m in LATENT_METRICS}}
     result["not_computed"] = {k: v for k, v in NOT_COMPUTED.items() if not computed.get(k, False)}
     return result, {"episodes": len(episodes), "frames": len(episodes) * T, "decode_s": t_decode, "device_s": t_device}
 

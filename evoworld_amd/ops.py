@@ -4,6 +4,7 @@ Signatures, argument structs and enum values come from the header through _lib's
 `_call`, which passes the arguments positionally in the prototype's order with the current stream last."""
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -511,12 +512,8 @@ def pano_yaw_rotate(src, yaw_deg):
 METRIC_SSE, METRIC_SSIM = 1, 2
 
 
-def video_metrics(a, b, what=METRIC_SSE | METRIC_SSIM, sse=None, ssim=None):
-    """Per-frame PSNR / SSIM inputs of frame pairs (ew_video_metrics; calculate_psnr.py:6-15, calculate_ssim.py:6-40): a, b
-    uint8 [F,H,W,C] (a pixel is float32(k) / 255.0f) or fp32 [F,C,H,W], C = 1 or 3 -> (sse, ssim), fp64 [F] device tensors
-    (None where `what` does not ask for it): sse = the frame's sum of float32 (a - b)^2 in fp64, ssim = the reference's per-frame
-    SSIM (mean over the channels).  `sse` / `ssim` may be given as fp64 [F] device views to write into."""
-    lib = _lib.load()
+def _metric_frames(a, b):
+    """The frame pair of ew_video_metrics / ew_video_metrics_ws, validated -> (layout, F, C, H, W)."""
     if a.dtype == torch.uint8:
         layout = 0
         _req(a, torch.uint8, "a")
@@ -533,17 +530,63 @@ def video_metrics(a, b, what=METRIC_SSE | METRIC_SSIM, sse=None, ssim=None):
         F_, C, H, W = a.shape
     if b.shape != a.shape or b.device != a.device:
         raise ValueError(f"a {tuple(a.shape)} on {a.device} and b {tuple(b.shape)} on {b.device} differ")
+    return layout, F_, C, H, W
+
+
+def _metric_outputs(what, F_, device, given):
+    """fp64 [F] outputs for the bits of `what`: given = ((flag, tensor or None, name), ...) -> [tensor or None per flag]"""
     out = []
-    for flag, t, name in ((METRIC_SSE, sse, "sse"), (METRIC_SSIM, ssim, "ssim")):
+    for flag, t, name in given:
         if what & flag and t is None:
-            t = torch.empty(F_, dtype=torch.float64, device=a.device)
+            t = torch.empty(F_, dtype=torch.float64, device=device)
         if t is not None:
             _req(t, torch.float64, name)
             if t.numel() != F_:
                 raise ValueError(f"{name}: expected {F_} values, got {t.numel()}")
         out.append(t if what & flag else None)
+    return out
+
+
+def video_metrics(a, b, what=METRIC_SSE | METRIC_SSIM, sse=None, ssim=None):
+    """Per-frame PSNR / SSIM inputs of frame pairs (ew_video_metrics; calculate_psnr.py:6-15, calculate_ssim.py:6-40): a, b
+    uint8 [F,H,W,C] (a pixel is float32(k) / 255.0f) or fp32 [F,C,H,W], C = 1 or 3 -> (sse, ssim), fp64 [F] device tensors
+    (None where `what` does not ask for it): sse = the frame's sum of float32 (a - b)^2 in fp64, ssim = the reference's per-frame
+    SSIM (mean over the channels).  `sse` / `ssim` may be given as fp64 [F] device views to write into."""
+    lib = _lib.load()
+    layout, F_, C, H, W = _metric_frames(a, b)
+    out = _metric_outputs(what, F_, a.device, ((METRIC_SSE, sse, "sse"), (METRIC_SSIM, ssim, "ssim")))
     ws = torch.empty(max(1, lib.ew_video_metrics_workspace_bytes(F_, C, H, W)), dtype=torch.uint8, device=a.device)
     _call("ew_video_metrics", _ptr(a), _ptr(b), layout, F_, C, H, W, int(what), _ptr(out[0]), _ptr(out[1]), _ptr(ws))
+    return out[0], out[1]
+
+
+def check_row_weights(row_w, H, ssim=False):
+    """One weight per image row for ew_video_metrics_ws, validated on the host -> fp64 numpy [H]: finite, >= 0, a positive sum over all
+    rows, and with `ssim` over rows 5 .. H-6 too (the centre rows of the 11-row windows)."""
+    w = row_w.detach().cpu().numpy() if isinstance(row_w, torch.Tensor) else np.asarray(row_w)
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if w.shape != (H,):
+        raise ValueError(f"row_w: expected {H} weights (one per image row), got shape {w.shape}")
+    if not np.isfinite(w).all() or (w < 0).any():
+        raise ValueError("row_w: the weights must be finite and >= 0")
+    if not w.sum() > 0:
+        raise ValueError("row_w: the weights sum to zero")
+    if ssim and H >= 11 and not w[5:H - 5].sum() > 0:
+        raise ValueError(f"row_w: the weights of rows 5 .. {H - 6}, the centre rows of the SSIM windows, sum to zero")
+    return w
+
+
+def video_metrics_ws(a, b, row_w, what=METRIC_SSE | METRIC_SSIM, wsse=None, wssim=None):
+    """The row-weighted forms of video_metrics (ew_video_metrics_ws): a, b as there; row_w one weight per image row (H values: numpy,
+    a sequence or a tensor; metrics.latitude_weights(H) gives WS-PSNR / WS-SSIM of equirectangular frames) -> (wsse, wssim), fp64 [F]
+    device tensors (None where `what` does not ask for it): wsse = sum of row_w[y] * float32 (a - b)^2, not normalised; wssim = the SSIM
+    map averaged under the weights of its windows' centre rows, then over the channels."""
+    lib = _lib.load()
+    layout, F_, C, H, W = _metric_frames(a, b)
+    w = torch.from_numpy(check_row_weights(row_w, H, ssim=bool(what & METRIC_SSIM))).to(a.device)
+    out = _metric_outputs(what, F_, a.device, ((METRIC_SSE, wsse, "wsse"), (METRIC_SSIM, wssim, "wssim")))
+    ws = torch.empty(max(1, lib.ew_video_metrics_ws_workspace_bytes(F_, C, H, W)), dtype=torch.uint8, device=a.device)
+    _call("ew_video_metrics_ws", _ptr(a), _ptr(b), layout, F_, C, H, W, int(what), _ptr(w), _ptr(out[0]), _ptr(out[1]), _ptr(ws))
     return out[0], out[1]
 
 

@@ -27,7 +27,7 @@ typedef int ew_status;
 #define EW_ERR_UNSUPPORTED (-2)
 #define EW_ERR_HIP (-3)
 
-#define EW_ABI_VERSION 17
+#define EW_ABI_VERSION 18
 int ew_abi_version(void);
 const char* ew_last_error(void);
 
@@ -392,6 +392,22 @@ ew_status ew_pano_yaw_rotate(const void* src, int src_u8, const float* yaw_deg, 
 size_t ew_video_metrics_workspace_bytes(int F, int C, int H, int W);
 ew_status ew_video_metrics(const void* a, const void* b, int layout, int F, int C, int H, int W, int what, double* sse, double* ssim,
                            void* workspace, void* stream);
+
+/* The same two quantities under one weight per image row (ABI 18): WS-PSNR / WS-SSIM of equirectangular frames when row_w is the
+ * cosine of the row's latitude (evoworld_amd.metrics.latitude_weights); the kernel itself is projection-agnostic.  Nothing of this is
+ * in the reference.  a, b, layout, F, C, H, W, what: as ew_video_metrics.  row_w: fp64 [H] on the device, expected finite and >= 0
+ * (the Python wrapper checks; the library does not read it on the host).
+ * wsse [F]:  sum over c, y, x of row_w[y] * d2(c,y,x), d2 the float32 (a - b)^2 of ew_video_metrics widened to fp64 before the
+ *   multiplication; not normalised: the caller forms wmse = wsse / (C * W * sum_y row_w[y]).
+ * wssim [F]: (1/C) sum_c [ sum_{i<H-10, j<W-10} row_w[i+5] S_c(i,j) ] / [ (W-10) sum_{i<H-10} row_w[i+5] ] with S_c the SSIM map
+ *   of ew_video_metrics unchanged: a window counts with the weight of its CENTRE row.  A zero sum of the centre rows' weights gives
+ *   a non-finite value.  Needs H, W >= 11.
+ * Fixed-order partial sums, no atomics: two calls are bit-identical; with row_w == 1 both outputs are ew_video_metrics' values.
+ * workspace: ew_video_metrics_ws_workspace_bytes(F, C, H, W) bytes (8-byte aligned).  Refused: what ew_video_metrics refuses, and a
+ * NULL row_w. */
+size_t ew_video_metrics_ws_workspace_bytes(int F, int C, int H, int W);
+ew_status ew_video_metrics_ws(const void* a, const void* b, int layout, int F, int C, int H, int W, int what, const double* row_w,
+                              double* wsse, double* wssim, void* workspace, void* stream);
 
 /* The 8-bit ground-truth frame of the episode-mode dumps predictions_gt_{seg}/NNN.png (unified_loop_consistency.py:87-93,437-439):
  * the resized uint8 frame k -> ToTensor (k / 255) -> x*2 - 1 -> (x*0.5 + 0.5).clamp(0, 1).mul(255).byte(), every step a float32

@@ -20,6 +20,9 @@
                                                            evoworld_amd.latent_mse: ms for the features of both clips (50 frames: what the
                                                            CLI spends per episode for latent_mse and loop_closure_latent_mse together),
                                                            host clock around synchronised calls
+  python tools/bench_metrics.py --ws [--iters N]           ew_video_metrics_ws (latitude weights) and ew_video_metrics on the same 25 uint8
+                                                           pairs in one process, event-timed as `kernel` is; writes both to
+                                                           profiles/ws_metrics_bench.json.  No speed gate
 Each mode prints one JSON line."""
 import argparse
 import json
@@ -68,6 +71,39 @@ def bench_kernel(iters):
     return {"mode": "kernel", "frames": F, "shape": [H, W, 3], "us_per_call": round(us, 1), "us_per_frame": round(us / F, 2),
             "input_GBps": round(nbytes / us / 1e3, 1), "hbm_fraction": round(nbytes / us / 1e6 / HBM_TBS, 4), "iters": iters,
             "note": "event-timed call (both kernels + the workspace allocation); kernel time: rocprofv3 --kernel-trace --stats"}
+
+
+def bench_ws(iters):
+    from evoworld_amd import metrics as M, ops
+    gt, gen = seeded_pair(0)
+    w = M.latitude_weights(H)
+    out = [torch.empty(F, dtype=torch.float64, device="cuda") for _ in range(2)]
+
+    def timed(fn):
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / iters
+    us = {}
+    for rnd in range(2):                                                       # planar, weighted, planar, weighted: the second round is reported
+        us["planar"] = timed(lambda: ops.video_metrics(gt, gen, sse=out[0], ssim=out[1]))
+        us["weighted"] = timed(lambda: ops.video_metrics_ws(gt, gen, w, wsse=out[0], wssim=out[1]))
+    rec = {"mode": "ws", "frames": F, "shape": [H, W, 3], "iters": iters,
+           "ew_video_metrics_us_per_call": round(us["planar"], 1), "ew_video_metrics_ws_us_per_call": round(us["weighted"], 1),
+           "ratio": round(us["weighted"] / us["planar"], 3),
+           "note": "event-timed calls through ops (both kernels + the workspace allocation; the weighted call also validates its 576 "
+                   "weights on the host and uploads them, per call)"}
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "ws_metrics_bench.json"), "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    return rec
 
 
 def bench_lpips(iters, cpu_baseline):
@@ -200,15 +236,18 @@ def main():
     p.add_argument("--lpips", action="store_true", help="time LPIPS (random weights) on a 25-pair 576x1024 clip")
     p.add_argument("--fvd", action="store_true", help="time FVD's I3D (random weights) on a 25-frame 576x1024 clip")
     p.add_argument("--latent_mse", action="store_true", help="time the latent MSE's Inception-v4 (random weights) on a 25-pair 576x1024 clip")
+    p.add_argument("--ws", action="store_true", help="time ew_video_metrics_ws against ew_video_metrics on a 25-pair 576x1024 clip")
     p.add_argument("--cpu_baseline", action="store_true", help="with --lpips: also run the clip through tests/lpips_ref.py on the CPU")
-    p.add_argument("--iters", type=int, default=None, help="timed calls (default: 50 for kernel, 5 for --lpips, --fvd and --latent_mse)")
+    p.add_argument("--iters", type=int, default=None, help="timed calls (default: 50 for kernel and --ws, 5 for --lpips, --fvd and --latent_mse)")
     p.add_argument("--root", help="directory the cli / episode modes write their PNG trees to")
     p.add_argument("--episodes", type=int, default=20)
     p.add_argument("--poses", type=int, default=80)
     a = p.parse_args()
-    if (a.lpips + a.fvd + a.latent_mse + (a.mode is not None)) != 1:
-        p.error("give one of kernel / cli / episode, or --lpips, or --fvd, or --latent_mse")
-    if a.latent_mse:
+    if (a.lpips + a.fvd + a.latent_mse + a.ws + (a.mode is not None)) != 1:
+        p.error("give one of kernel / cli / episode, or --lpips, or --fvd, or --latent_mse, or --ws")
+    if a.ws:
+        rec = bench_ws(a.iters or 50)
+    elif a.latent_mse:
         rec = bench_latent_mse(a.iters or 5)
     elif a.fvd:
         rec = bench_fvd(a.iters or 5)
