@@ -299,7 +299,7 @@ class UnifiedLoopConsistencyPipeline:
         return pers, yaws / np.pi * 180.0
 
     def process_episode(self, start_image, camera_params, image_latents_fn=None, save_dir=None, pos_scale=0.1,
-                        save_segment_frames=False, episode_path=None, **pipe_kw):
+                        save_segment_frames=False, episode_path=None, export_memory=False, memory_voxel_size=None, **pipe_kw):
         """start_image float [3,H,W] in [-1,1]; camera_params [P,6] numpy: the UNSCALED RDF poses of camera_poses.txt
         (unified_loop_consistency.py:370-395), used as they are for the target yaws and the reprojection alignment; the
         Navigator / Plücker path gets the copy with xyz * pos_scale that the dataset hands out as batch['cam_traj']
@@ -322,7 +322,10 @@ class UnifiedLoopConsistencyPipeline:
         counts follow the runs' lengths); ValueError when the path or the episode cannot carry num_segments segments.
         With save_segment_frames and an `episode_path` whose panorama/NNN.png exist, predictions_gt_{seg}/NNN.png is written too
         (:437-439): the window's ground-truth panoramas (ids start_idx+1 .. end_idx of calculate_segment_indices), Pillow-exact
-        resized and passed through the reference's tensor_to_pil round trip (ops.gt_dump_map_u8), numbered like predictions_{seg}."""
+        resized and passed through the reference's tensor_to_pil round trip (ops.gt_dump_map_u8), numbered like predictions_{seg}.
+        With export_memory and a save_dir, every hand-off also writes its 3D memory as glbscene_{seg}.glb (memory.SceneMemory: the very
+        cloud the panoramas are rendered from, with the depth network's cameras; reproject_vggt_open3d.py:245-265).  memory_voxel_size
+        (opt-in) thins that cloud by a voxel-grid downsample before the splat (and the export); None leaves the path as it is."""
         from . import ops
         dev = start_image.device
         camera_params = np.asarray(camera_params, dtype=np.float64)
@@ -379,9 +382,14 @@ class UnifiedLoopConsistencyPipeline:
                 preds = self.depth_model(pers)
                 poses = xyz_euler_to_four_by_four_matrix_batch(torch.tensor(temp_cam, dtype=torch.float32), relative=True)
                 outdir = os.path.join(save_dir or "", f"rendered_panorama_vggt_open3d_{seg}")
+                glb = None
+                if export_memory and save_dir:
+                    os.makedirs(save_dir, exist_ok=True)
+                    glb = os.path.join(save_dir, f"glbscene_{seg}.glb")
                 panos = RP.predictions_to_target_view(preds, poses.numpy(), conf_thres=50.0, prediction_mode="depth_unproject",
                                                       num_target_view=24, outdir=outdir, cubemap_renderer=_Sized(self.renderer, self.pano_size),
-                                                      return_device_tensor=True, save_png=bool(save_dir))
+                                                      return_device_tensor=True, save_png=bool(save_dir), voxel_size=memory_voxel_size,
+                                                      export_glb=glb)
                 mem24 = RP.memory_to_pixel_values(panos, self.height, self.width)           # [24,3,H,W]
                 memory = torch.cat([start_image[None], mem24], dim=0)                      # [episode frame 1] + 24 reprojected (:277-279)
         self.last_frames_u8 = all_u8

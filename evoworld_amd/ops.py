@@ -448,6 +448,83 @@ def splat_cubemap(xyz, rgb, w2c, res, fx, fy, cx, cy, z_near, face_channels=3):
     return faces, zbuf
 
 
+def points_bounds(xyz):
+    """xyz fp32 [n,3] on the device -> (min fp32 [3], max fp32 [3], n_finite) on the host: the per-axis bounds over the points whose
+    three coordinates are all finite, and their count (ew_points_bounds); +inf / -inf and 0 when there is none.  Synchronises."""
+    lib = _lib.load()
+    xyz = _aligned(xyz)
+    _req(xyz, torch.float32, "xyz")
+    n = xyz.shape[0]
+    if xyz.ndim != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"xyz must be [n,3], got {tuple(xyz.shape)}")
+    ws = torch.empty(lib.ew_points_bounds_workspace_bytes(n) // 8 + 1, dtype=torch.int64, device=xyz.device)
+    out6 = torch.empty(6, dtype=torch.float32, device=xyz.device)
+    cnt = torch.empty(1, dtype=torch.int64, device=xyz.device)
+    _call("ew_points_bounds", _ptr(xyz), n, _ptr(ws), _ptr(out6), _ptr(cnt))
+    b = out6.cpu().numpy()
+    return b[:3].copy(), b[3:].copy(), int(cnt.item())
+
+
+VOXEL_GRID_BITS = 21            # bits per axis of a voxel key (ew_voxel_keys)
+
+
+def voxel_downsample(xyz, rgbx, voxel_size):
+    """Voxel-grid downsample on the device, Open3D's voxel_down_sample convention: xyz fp32 [n,3], rgbx uint8 [n,4] (the RGBX words
+    of filter_compact; a [n,3] tensor is widened) -> (xyz [m,3] fp32 = the mean of each occupied voxel's points, rgba [m,4] uint8 =
+    the per-channel mean rounded half to even with alpha 255, count [m] int32), voxels in ascending key order (x major).  Non-finite
+    points are dropped.  ew_points_bounds -> ew_voxel_keys -> torch.sort(stable) -> ew_voxel_reduce; deterministic (no atomics).
+    ValueError: voxel_size not a positive finite number, or a cloud that spans more than 2^21 voxels along an axis."""
+    try:
+        v = float(voxel_size)
+    except (TypeError, ValueError):
+        raise ValueError(f"voxel_size must be a positive finite number, got {voxel_size!r}") from None
+    v32 = np.float32(v)
+    if not (np.isfinite(v32) and v32 > 0):
+        raise ValueError(f"voxel_size must be a positive finite number (in float32), got {voxel_size!r}")
+    if rgbx.dtype != torch.uint8 or rgbx.device.type != "cuda":
+        raise TypeError("rgbx must be a uint8 device tensor")
+    if xyz.ndim != 2 or xyz.shape[1] != 3 or rgbx.ndim != 2 or rgbx.shape[0] != xyz.shape[0] or rgbx.shape[1] not in (3, 4):
+        raise ValueError(f"xyz must be [n,3] and rgbx [n,3|4], got {tuple(xyz.shape)} and {tuple(rgbx.shape)}")
+    dev = xyz.device
+
+    def empty():
+        return (torch.empty(0, 3, dtype=torch.float32, device=dev), torch.empty(0, 4, dtype=torch.uint8, device=dev),
+                torch.empty(0, dtype=torch.int32, device=dev))
+
+    n = xyz.shape[0]
+    if n == 0:
+        return empty()
+    lib = _lib.load()
+    xyz = _aligned(xyz)
+    _req(xyz, torch.float32, "xyz")
+    if rgbx.shape[1] == 3:
+        rgbx = torch.cat([rgbx, torch.zeros(n, 1, dtype=torch.uint8, device=dev)], dim=1)
+    rgbx = _aligned(rgbx)
+    lo, hi, n_finite = points_bounds(xyz)
+    if n_finite == 0:
+        return empty()
+    origin = (lo - np.float32(0.5) * v32).astype(np.float32)          # float32 arithmetic, as the kernel's index expects
+    origin_d = torch.from_numpy(origin).to(dev)
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+    _call("ew_voxel_keys", _ptr(xyz), n, _ptr(origin_d), float(v32), _ptr(keys), _ptr(overflow))
+    if int(overflow.item()):
+        extent = float(np.max(hi.astype(np.float64) - lo.astype(np.float64)))
+        raise ValueError(f"voxel_size {v:g} is too small for a cloud of extent {extent:g}: a voxel key has {VOXEL_GRID_BITS} bits per "
+                         f"axis, so the smallest voxel size this cloud admits is about {extent / 2 ** VOXEL_GRID_BITS:g} "
+                         f"(extent / 2^{VOXEL_GRID_BITS})")
+    skeys, perm = torch.sort(keys, stable=True)                          # plumbing: the sort is torch's (DESIGN.md)
+    out_xyz = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    out_rgba = torch.empty(n, 4, dtype=torch.uint8, device=dev)
+    out_cnt = torch.empty(n, dtype=torch.int32, device=dev)
+    ws = torch.empty(lib.ew_voxel_reduce_workspace_bytes(n) // 16 + 1, 2, dtype=torch.int64, device=dev)
+    m_d = torch.empty(1, dtype=torch.int64, device=dev)
+    _call("ew_voxel_reduce", _ptr(skeys), _ptr(perm), n, _ptr(xyz), _ptr(rgbx), _ptr(out_xyz), _ptr(out_rgba), _ptr(out_cnt), _ptr(ws),
+          _ptr(m_d))
+    m = int(m_d.item())
+    return out_xyz[:m], out_rgba[:m], out_cnt[:m]
+
+
 def equi2pers(equi, rot, Hp, Wp, fov_x):
     _req(equi, torch.uint8, "equi"); _req(rot, torch.float32, "rot")
     F_, He, We, _ = equi.shape

@@ -259,9 +259,13 @@ def predictions_to_target_view(predictions, camera_pose, conf_thres=50.0, filter
                                scene_builder=None, cubemap_renderer=None, mask_black_bg=False, mask_white_bg=False,
                                show_cam=True, mask_sky=False, target_dir=None, image_subdir=None,
                                prediction_mode="Predicted Pointmap", num_target_view=24, outdir="demo_pyrender_render",
-                               only_render_last_24_frame=False, return_device_tensor=False, save_png=True):
+                               only_render_last_24_frame=False, return_device_tensor=False, save_png=True, voxel_size=None,
+                               export_glb=None):
     """VGGT predictions -> 24 reprojected panoramas uint8 [24,1000,2000,3] (:1216-1282).  `outdir`'s `_{segment}` suffix
-    selects the target poses, as in the reference (:487-492)."""
+    selects the target poses, as in the reference (:487-492).
+    voxel_size (opt-in): the filtered cloud is thinned by ops.voxel_downsample between the filter and the splat (one averaged point
+    per occupied voxel).  export_glb (opt-in): a path; the cloud that is rendered -- after the downsample, when there is one -- is
+    also written there as a GLB with the predictions' cameras (memory.SceneMemory; show_cam as given), without a second filter pass."""
     if not isinstance(predictions, dict):
         raise ValueError("predictions must be a dictionary")
     pp = point_processor or PointCloudProcessor()
@@ -273,6 +277,11 @@ def predictions_to_target_view(predictions, camera_pose, conf_thres=50.0, filter
                                                                        predictions["intrinsic"])
     v, c, _scale = pp.filter_predictions(predictions, conf_thres, filter_by_frames, mask_black_bg, mask_white_bg, mask_sky,
                                          target_dir, image_subdir, prediction_mode, only_render_last_24_frame)
+    if voxel_size is not None:
+        v, rgba, _ = ops.voxel_downsample(v, c, voxel_size)
+        c = rgba[:, :3]                                                          # view of the RGBA words, as after the filter
+    if export_glb is not None:
+        SceneMemory.from_cloud(v, c, predictions["extrinsic"], show_cam).to_glb(export_glb)
     target = sb.align_extrinsics(camera_pose, predictions["extrinsic"], num_target_view, outdir, only_render_last_24_frame)
     panos = cr.render_cubemaps_to_panoramas(v, c, target, num_target_view, outdir if save_png else None)
     return panos if return_device_tensor else panos.cpu().numpy()
@@ -527,3 +536,7 @@ def memory_to_pixel_values(panos_u8, height=576, width=1024):
     cv = tuple(t.to(dev) for t in resample_coeffs(Hi, height))
     small = ops.resize_aa_u8(panos_u8.contiguous(), ch, cv, height, width) if (Hi, Wi) != (height, width) else panos_u8.contiguous()
     return ops.u8_hwc_to_f32_chw(small)
+
+
+# ------------------------------------------------------------------ the memory as an object: GLB / PLY export (:713-766)
+from .memory import SceneMemory, predictions_to_glb  # noqa: E402,F401  (memory.py imports this module lazily, inside its functions)

@@ -27,7 +27,7 @@ typedef int ew_status;
 #define EW_ERR_UNSUPPORTED (-2)
 #define EW_ERR_HIP (-3)
 
-#define EW_ABI_VERSION 18
+#define EW_ABI_VERSION 19
 int ew_abi_version(void);
 const char* ew_last_error(void);
 
@@ -351,6 +351,29 @@ ew_status ew_splat_cubemap(const float* xyz, size_t npts, const float* w2c, unsi
                            float fx, float fy, float cx, float cy, float z_near, void* stream);
 ew_status ew_splat_resolve(const unsigned long long* zbuf, const uint8_t* rgb, int rgb_stride, uint8_t* faces,
                            int face_channels, int V, int res, void* stream);
+
+/* The 3D memory as a point cloud to take away (ABI 19; csrc/pointcloud.hip).  The reference exports the filtered cloud through
+ * predictions_to_glb -> SceneBuilder.build_scene (reproject_vggt_open3d_utils.py:713-766, 349-455) and save_point_cloud_to_ply
+ * (utils/plucker_embedding.py:334); the voxel-grid downsample in front of the export (and, opt-in, in front of the splat) follows
+ * Open3D's voxel_down_sample convention.  n < 2^31 everywhere.
+ * ew_points_bounds: out6 (device) = min x, y, z, max x, y, z over the points whose three coordinates are all finite, *n_finite (device)
+ *   their count; n == 0 or no finite point: +inf x3, -inf x3 and 0.  ws: ew_points_bounds_workspace_bytes(n), 8-byte aligned.
+ * ew_voxel_keys: for a finite point, per axis i = (long long)floorf((p - origin) / voxel) in float32 (a subtraction, an IEEE division,
+ *   a floor; origin3 on the device, by convention min - 0.5f * voxel computed in float32), key = ix << 42 | iy << 21 | iz.  A non-finite
+ *   point gets 2^63 - 1 (sorts last, dropped by ew_voxel_reduce).  An index outside [0, 2^21) stores 1 to *overflow (device; the caller
+ *   zeroes it beforehand and discards the keys when it is set).
+ * ew_voxel_reduce: sorted_keys ascending with perm the permutation that sorted them (key i belongs to point perm[i]; the sort is the
+ *   caller's); one output per run of equal keys, in ascending key order: out_xyz = the mean of the run's points (fp64 sums, divided by the
+ *   count in fp64, rounded to float32), out_rgba = per channel round-half-to-even of sum / count in integer arithmetic with alpha 255
+ *   (rgbx: the RGBX words of ew_filter_compact, X ignored), out_count = the run's length; *n_voxels (device) = the number of runs.  The
+ *   outputs hold n entries.  Work per run is bounded by log-depth segmented scans whatever its length.  No atomics: two calls are
+ *   bit-identical.  ws: ew_voxel_reduce_workspace_bytes(n), 16-byte aligned. */
+size_t ew_points_bounds_workspace_bytes(size_t n);
+ew_status ew_points_bounds(const float* xyz, size_t n, void* ws, float* out6, unsigned long long* n_finite, void* stream);
+ew_status ew_voxel_keys(const float* xyz, size_t n, const float* origin3, float voxel, long long* keys, int* overflow, void* stream);
+size_t ew_voxel_reduce_workspace_bytes(size_t n);
+ew_status ew_voxel_reduce(const long long* sorted_keys, const long long* perm, size_t n, const float* xyz, const uint8_t* rgbx,
+                          float* out_xyz, uint8_t* out_rgba, int* out_count, void* ws, unsigned long long* n_voxels, void* stream);
 
 /* Equirect -> perspective bilinear gather (pyequilib Equi2Pers restatement; unified_loop_consistency.py:299-334).
  * equi uint8 [F,He,We,3]; rot [F,3,3] f32 (camera->pano rotation); out uint8 [F,Hp,Wp,3]. */

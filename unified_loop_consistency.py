@@ -43,6 +43,10 @@ def parse_arguments(argv=None):
     p.add_argument("--height", type=int, default=576)
     p.add_argument("--width", type=int, default=1024)
     p.add_argument("--qkv_fp8", action="store_true", help="fp8 (e4m3) q/k/v projections in the U-Net self-attention (opt-in; default fp16)")
+    p.add_argument("--export_glb", action="store_true",
+                   help="write every hand-off's 3D memory as glbscene_{seg}.glb under the episode's output directory (with its memory panoramas)")
+    p.add_argument("--memory_voxel_size", type=float, default=None,
+                   help="voxel-grid downsample of the 3D memory before the splat and the export (opt-in; scene units)")
     return p.parse_args(argv)
 
 
@@ -151,8 +155,9 @@ def run_episode(args, ep, pipe, unet, dev, out_dir, synthetic):
     # the unscaled poses go in; process_episode derives the pos-scaled Navigator / Plücker path itself (pos_scale = 0.1);
     # --save_frames also writes the reference's per-segment dumps predictions_{seg}/ and perspective_look_at_center_{seg}/
     # ... and, for an episode folder with panoramas, the ground-truth windows predictions_gt_{seg}/ (:437-439)
-    frames = loop.process_episode(start, cam, save_dir=out_dir if args.save_frames else None,
-                                  save_segment_frames=args.save_frames, episode_path=None if synthetic else ep)
+    frames = loop.process_episode(start, cam, save_dir=out_dir if args.save_frames or args.export_glb else None,
+                                  save_segment_frames=args.save_frames, episode_path=None if synthetic else ep,
+                                  export_memory=args.export_glb, memory_voxel_size=args.memory_voxel_size)
     torch.cuda.synchronize()
     dt = time.time() - t0
     if args.save_frames:
