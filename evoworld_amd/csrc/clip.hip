@@ -44,6 +44,15 @@ __device__ __forceinline__ void cubic_coeffs(float t, float (&c)[4]) {
     c[3] = ((A * x4 - 5.0f * A) * x4 + 8.0f * A) * x4 - 4.0f * A;
 }
 
+// torch's fp32 source index (align_corners=True): r = s * o rounded to fp32, i = floor(r), t = r - i.  Contracted, t = fma(s, o, -i) comes from the
+// exact product while i comes from the rounded one: up to half an ulp of r (3e-5 at r ~ 1000) away from torch's t, and so is the output.
+__device__ __forceinline__ void src_index(float s, int o, int& i, float& t) {
+#pragma clang fp contract(off)
+    const float r = s * (float)o;
+    i = (int)floorf(r);
+    t = r - (float)i;
+}
+
 // F.interpolate(mode='bicubic', align_corners=True) + per-channel affine: out = v * scale[c] + shift[c]
 __global__ __launch_bounds__(256) void bicubic_kernel(const float* __restrict__ x, float* __restrict__ out, long long planes,
                                                       int C, int H, int W, int Ho, int Wo, const float* __restrict__ scale,
@@ -55,11 +64,12 @@ __global__ __launch_bounds__(256) void bicubic_kernel(const float* __restrict__ 
         const long long t = i / Wo;
         const int oy = (int)(t % Ho);
         const long long pl = t / Ho;
-        const float ry = sy * (float)oy, rx = sx * (float)ox;
-        const int iy = (int)floorf(ry), ix = (int)floorf(rx);
-        float cy[4], cx[4];
-        cubic_coeffs(ry - (float)iy, cy);
-        cubic_coeffs(rx - (float)ix, cx);
+        int iy, ix;
+        float ty, tx, cy[4], cx[4];
+        src_index(sy, oy, iy, ty);
+        src_index(sx, ox, ix, tx);
+        cubic_coeffs(ty, cy);
+        cubic_coeffs(tx, cx);
         const float* base = x + pl * H * W;
         float acc = 0.f;
 #pragma unroll

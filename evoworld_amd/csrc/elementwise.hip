@@ -19,7 +19,11 @@ __global__ void nchw_to_nhwc_kernel(const float* __restrict__ x, f16* __restrict
         const float* xp = x + n * C * (long long)HW + p;
         f16* yp = y + i * ldc + c_off;
         for (int c = 0; c < C; ++c) {
-            const float v = scale * xp[(long long)c * HW];
+            float v = scale * xp[(long long)c * HW];
+            // hi is the fp16 rounding of the fp32 product v, like torch's (scale * x).half().  Left to itself the backend selects product and
+            // conversion as one v_fma_mixlo_f16 with a +0 addend (whatever -ffp-contract says): the exact product rounded once -- another fp16
+            // value in about 1 element in 10^4 when scale is no power of two -- and -0 turned into +0.  The empty asm keeps v a value of its own.
+            asm volatile("" : "+v"(v));
             const f16 hi = (f16)v;
             yp[c] = hi;
             if (lo_off > 0) {
