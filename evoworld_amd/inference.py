@@ -7,6 +7,7 @@
                                          <- evoworld/inference/navigator_evoworld.py:276-301,335-392,466-512  (C2, non-curve mode)
   Navigator.convert_panorama_to_cubemap / precompute_rotation_matrix / cubemap_to_equirectangular
                                          <- evoworld/inference/navigator_evoworld.py:514-705,707-743,745-864  (C2, skybox export)
+  Navigator.save_video / save_gif        <- evoworld/inference/navigator_evoworld.py:233-274               (C2, clip export)
   UnifiedLoopConsistencyPipeline.process_episode / convert_pano_to_pers
                                          <- unified_loop_consistency.py:299-334,398-492               (C3, N-segment loop)
 
@@ -16,6 +17,7 @@ mask_mem, per-window generator re-seeded with torch.manual_seed(-1)).  Differenc
 depth network (VGGT-1B, out of scope) is a duck-typed callable `depth_model(perspective_frames_u8) -> predictions dict`.
 File output (PNG dumps) is optional and off the hot path.
 """
+import logging
 import os
 from types import SimpleNamespace
 
@@ -25,6 +27,8 @@ import torch
 from . import reprojection as RP
 from .geometry import UNITY_TO_OPENCV, xyz_euler_to_four_by_four_matrix_batch, xyz_euler_to_three_by_four_matrix_batch
 from .plucker import equirectangular_to_ray, ray_c2w_to_plucker
+
+logger = logging.getLogger(__name__)
 
 
 # ------------------------------------------------------------------ C1: single clip
@@ -119,6 +123,56 @@ class Navigator:
             return (torch.from_numpy(arr.copy()).permute(2, 0, 1).float() / 255.0 * 2 - 1).cuda()
         raise NotImplementedError("chaining windows needs decoded frames (output_type='pil'); with output_type='latent' "
                                   "run one window per call (infer_segment=True), as process_episode does")
+
+    def generated_frames_u8(self):
+        """The frames save_video / save_gif export: of every window in self.generations its first n frames (the poses the window was
+        asked for), as uint8 [N,H,W,3] on the device, resized to the navigator's image size with Pillow's BICUBIC
+        (navigator_evoworld.py:241, :263) -- on the device through reprojection.resize_u8, skipped when the size already matches.
+        A window is a PIL clip list (output_type='pil'), a uint8 array [B,T,H,W,3] ('np') or a tensor [B,T,3,H,W] in [0,1] ('pt').
+        None when there is no generation."""
+        parts = []
+        for frames, n in self.generations:
+            if isinstance(frames, list):
+                arr = np.stack([np.asarray(f.convert("RGB")) for f in frames[0][:n]])
+                u8 = torch.from_numpy(arr).cuda()
+            elif isinstance(frames, np.ndarray) and frames.dtype == np.uint8 and frames.ndim == 5:
+                u8 = torch.from_numpy(np.ascontiguousarray(frames[0][:n])).cuda()
+            elif isinstance(frames, torch.Tensor) and frames.ndim == 5 and frames.shape[2] == 3:
+                u8 = (frames[0, :n].float().clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous().cuda()
+            elif isinstance(frames, torch.Tensor):
+                raise NotImplementedError(f"a generation of shape {tuple(frames.shape)} holds latents (output_type='latent'), not images: "
+                                          "decode them first (pipe.decode_latents, or process_episode(save_video=True), which "
+                                          "writes the decoded episode)")
+            else:
+                raise TypeError(f"cannot export a generation of type {type(frames).__name__}")
+            if len(u8):
+                parts.append(RP.resize_u8(u8, self.model_height, self.model_width, filter="pillow_bicubic"))
+        return torch.cat(parts, dim=0) if parts else None
+
+    def save_video(self, save_path, fps=10):
+        """The generated windows as one video file (navigator_evoworld.py:233-257).  The reference hands the frames to imageio /
+        ffmpeg; here they are encoded on the device as Motion-JPEG and wrapped in an AVI (evoworld_amd.video.write_video: quality
+        90, 4:2:0), so save_path must end in .avi.  Nothing is written (and that is logged) when there is no generation."""
+        from .video import write_video
+        frames = self.generated_frames_u8()
+        if frames is None:
+            logger.info("No Movement to Export.")
+            return
+        write_video(save_path, frames, fps=fps)
+        logger.info("Video saved as %s", save_path)
+
+    def save_gif(self, save_path, fps=10):
+        """The generated windows as an animated GIF (navigator_evoworld.py:259-274): Pillow on the host, save_all with
+        duration = int(1000 / fps) ms and loop = 0, exactly as the reference does.  GIF is an LZW-coded palette format of
+        thumbnail-sized use; it is not worth a kernel, only the BICUBIC resize in front of it runs on the device."""
+        from PIL import Image
+        frames = self.generated_frames_u8()
+        if frames is None:
+            logger.info("No Movement to Export.")
+            return
+        imgs = [Image.fromarray(f) for f in frames.cpu().numpy()]
+        imgs[0].save(save_path, save_all=True, append_images=imgs[1:], duration=int(1000 / fps), loop=0)
+        logger.info("GIF saved as %s", save_path)
 
     @staticmethod
     def split_path_into_segments(path):
@@ -299,7 +353,8 @@ class UnifiedLoopConsistencyPipeline:
         return pers, yaws / np.pi * 180.0
 
     def process_episode(self, start_image, camera_params, image_latents_fn=None, save_dir=None, pos_scale=0.1,
-                        save_segment_frames=False, episode_path=None, export_memory=False, memory_voxel_size=None, **pipe_kw):
+                        save_segment_frames=False, episode_path=None, export_memory=False, memory_voxel_size=None,
+                        save_video=False, video_fps=10, video_quality=90, **pipe_kw):
         """start_image float [3,H,W] in [-1,1]; camera_params [P,6] numpy: the UNSCALED RDF poses of camera_poses.txt
         (unified_loop_consistency.py:370-395), used as they are for the target yaws and the reprojection alignment; the
         Navigator / Plücker path gets the copy with xyz * pos_scale that the dataset hands out as batch['cam_traj']
@@ -325,7 +380,11 @@ class UnifiedLoopConsistencyPipeline:
         resized and passed through the reference's tensor_to_pil round trip (ops.gt_dump_map_u8), numbered like predictions_{seg}.
         With export_memory and a save_dir, every hand-off also writes its 3D memory as glbscene_{seg}.glb (memory.SceneMemory: the very
         cloud the panoramas are rendered from, with the depth network's cameras; reproject_vggt_open3d.py:245-265).  memory_voxel_size
-        (opt-in) thins that cloud by a voxel-grid downsample before the splat (and the export); None leaves the path as it is."""
+        (opt-in) thins that cloud by a voxel-grid downsample before the splat (and the export); None leaves the path as it is.
+        With save_video and a save_dir, navigated.avi holds all generated frames -- the very uint8 tensor that is returned -- as
+        Motion-JPEG encoded on the device (evoworld_amd.video; video_fps, video_quality), and, for an `episode_path` with ground-truth
+        panoramas, original.avi holds the frames load_gt_window_u8 yields for the same poses (panorama ids 1 .. N, frame for frame
+        beside navigated.avi): the pair calculate_scores.py loads per episode (there as .mp4).  The returned frames do not depend on it."""
         from . import ops
         dev = start_image.device
         camera_params = np.asarray(camera_params, dtype=np.float64)
@@ -393,6 +452,15 @@ class UnifiedLoopConsistencyPipeline:
                 mem24 = RP.memory_to_pixel_values(panos, self.height, self.width)           # [24,3,H,W]
                 memory = torch.cat([start_image[None], mem24], dim=0)                      # [episode frame 1] + 24 reprojected (:277-279)
         self.last_frames_u8 = all_u8
+        if save_video and save_dir:
+            from .video import write_video
+            os.makedirs(save_dir, exist_ok=True)
+            write_video(os.path.join(save_dir, "navigated.avi"), all_u8, fps=video_fps, quality=video_quality)
+            if episode_path is not None:
+                from .dataset import load_gt_window_u8
+                gt = load_gt_window_u8(episode_path, 0, all_u8.shape[0], self.height, self.width, dev, len(camera_params))
+                if gt is not None:
+                    write_video(os.path.join(save_dir, "original.avi"), gt, fps=video_fps, quality=video_quality)
         return ops.u8_hwc_to_f32_chw(all_u8)
 
 

@@ -525,6 +525,70 @@ def voxel_downsample(xyz, rgbx, voxel_size):
     return out_xyz[:m], out_rgba[:m], out_cnt[:m]
 
 
+JPEG_SAMPLING = {"4:2:0": (_lib.EW_JPEG_420, 16, 6), "4:4:4": (_lib.EW_JPEG_444, 8, 3)}      # name -> (ABI value, MCU size, blocks per MCU)
+
+
+def jpeg_dct_quant(frames_u8, quality, subsampling="4:2:0", out=None):
+    """frames uint8 [V,H,W,3] on the device -> the quantised DCT coefficients of their baseline JPEGs, int16
+    [V, mcu_rows, mcu_cols, blocks_per_mcu, 64] in scan and zigzag order (ew_jpeg_dct_quant).  quality 1..100,
+    subsampling "4:2:0" | "4:4:4".  `out`: a contiguous, 16-byte aligned int16 tensor of that shape to write into."""
+    _req(frames_u8, torch.uint8, "frames_u8")
+    if frames_u8.ndim != 4 or frames_u8.shape[3] != 3:
+        raise ValueError(f"frames_u8 must be [V,H,W,3], got {tuple(frames_u8.shape)}")
+    if subsampling not in JPEG_SAMPLING:
+        raise ValueError(f"subsampling must be one of {sorted(JPEG_SAMPLING)}, got {subsampling!r}")
+    if not (isinstance(quality, int) and 1 <= quality <= 100):
+        raise ValueError(f"quality must be an integer 1..100, got {quality!r}")
+    V, H, W, _ = frames_u8.shape
+    if not (1 <= V <= 65535 and 1 <= H <= 65535 and 1 <= W <= 65535):
+        raise ValueError(f"V, H and W must be 1..65535, got {V}, {H}, {W}")
+    mode, mcu, bpm = JPEG_SAMPLING[subsampling]
+    shape = (V, -(-H // mcu), -(-W // mcu), bpm, 64)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int16, device=frames_u8.device)
+    elif tuple(out.shape) != shape:
+        raise ValueError(f"out must be {shape}, got {tuple(out.shape)}")
+    _req(out, torch.int16, "out")
+    _call("ew_jpeg_dct_quant", _ptr(frames_u8), _ptr(out), V, H, W, quality, mode)
+    return out
+
+
+def jpeg_entropy(coef):
+    """coef int16 [V, mcu_rows, mcu_cols, 6 | 3, 64] (jpeg_dct_quant) -> (slots uint8 [V * mcu_rows, slot_bytes], seg_bytes int32
+    [V * mcu_rows]) on the device: the Huffman-coded, byte-stuffed restart segment of every MCU row and its length
+    (ew_jpeg_entropy).  Slots hold the provable worst case, 416 bytes per block."""
+    _req(coef, torch.int16, "coef")
+    if coef.ndim != 5 or coef.shape[3] not in (3, 6) or coef.shape[4] != 64 or coef.numel() == 0:
+        raise ValueError(f"coef must be [V, mcu_rows, mcu_cols, 6 | 3, 64], got {tuple(coef.shape)}")
+    V, mr, mc, bpm, _ = coef.shape
+    coef = _aligned(coef)
+    slot = _lib.load().ew_jpeg_segment_slot_bytes(mc, bpm)
+    slots = torch.empty(V * mr, slot, dtype=torch.uint8, device=coef.device)
+    seg_bytes = torch.empty(V * mr, dtype=torch.int32, device=coef.device)
+    _call("ew_jpeg_entropy", _ptr(coef), _ptr(slots), _ptr(seg_bytes), V * mr, mc, bpm, slot)
+    return slots, seg_bytes
+
+
+def jpeg_pack(slots, seg_bytes, mcu_rows):
+    """The segments of jpeg_entropy -> (stream uint8 [total] on the device, frame_bytes int64 [V] on the host): every frame's scan
+    data, contiguous, with the RSTm markers between its MCU rows (ew_jpeg_pack).  The offsets are torch.cumsum of the byte counts
+    (plumbing).  Synchronises once, for the stream's length."""
+    _req(slots, torch.uint8, "slots"); _req(seg_bytes, torch.int32, "seg_bytes")
+    n = seg_bytes.shape[0]
+    if slots.ndim != 2 or slots.shape[0] != n or n == 0 or mcu_rows < 1 or n % mcu_rows:
+        raise ValueError(f"slots must be [n, slot_bytes] and seg_bytes [n] with n a positive multiple of mcu_rows = {mcu_rows}, "
+                         f"got {tuple(slots.shape)} and {tuple(seg_bytes.shape)}")
+    sizes = seg_bytes.to(torch.int64).view(-1, mcu_rows) + 2
+    sizes[:, -1] -= 2                                                   # no marker behind a frame's last row
+    ends = torch.cumsum(sizes.view(-1), 0)
+    offsets = (ends - sizes.view(-1)).contiguous()
+    frame_bytes = sizes.sum(dim=1).cpu()
+    total = int(frame_bytes.sum())
+    stream = torch.empty(total, dtype=torch.uint8, device=slots.device)
+    _call("ew_jpeg_pack", _ptr(slots), _ptr(seg_bytes), _ptr(offsets), _ptr(stream), n, mcu_rows, slots.shape[1], total)
+    return stream, frame_bytes
+
+
 def equi2pers(equi, rot, Hp, Wp, fov_x):
     _req(equi, torch.uint8, "equi"); _req(rot, torch.float32, "rot")
     F_, He, We, _ = equi.shape

@@ -384,15 +384,28 @@ def _lanczos_filter(x):
     return _sinc(x) * _sinc(x / 3) if -3.0 <= x < 3.0 else 0.0
 
 
-RESAMPLE_FILTERS = {"bilinear": (_bilinear_filter, 1.0), "lanczos": (_lanczos_filter, 3.0)}     # name -> (weight, support)
+def _bicubic_filter(x):
+    """Pillow's bicubic_filter: the Keys kernel with a = -0.5, support 2"""
+    a = -0.5
+    x = abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+RESAMPLE_FILTERS = {"bilinear": (_bilinear_filter, 1.0), "lanczos": (_lanczos_filter, 3.0),
+                    "pillow_bicubic": (_bicubic_filter, 2.0)}                                # name -> (weight, support)
 
 
 def resample_coeffs(in_size, out_size, filter="bilinear"):
-    """Pillow's precompute_coeffs + normalize_coeffs_8bpc over the full box for the BILINEAR (support 1.0, the default) or
-    LANCZOS (support 3.0) filter: returns (kk int32 [out, ksize], bounds int32 [out, 2] = (xmin, count)), 22 fractional bits.
+    """Pillow's precompute_coeffs + normalize_coeffs_8bpc over the full box for the BILINEAR (support 1.0, the default),
+    LANCZOS (support 3.0) or BICUBIC ("pillow_bicubic": a = -0.5, support 2.0) filter: returns (kk int32 [out, ksize], bounds int32 [out, 2] = (xmin, count)), 22 fractional bits.
     Bilinear is what torchvision.transforms.Resize((576,1024)) does to the 1000x2000 PIL memory panoramas
     (dataset/CameraTrajDataset.py:586-619, unified_loop_consistency.py:422); LANCZOS is what the cubemap conversions bracket their
-    transform with (evoworld/inference/navigator_evoworld.py:527-530, :701-703, :858-860).  Verified bit-exact against PIL itself."""
+    transform with (evoworld/inference/navigator_evoworld.py:527-530, :701-703, :858-860); BICUBIC is what Navigator.save_video /
+    save_gif resize their frames with (:241, :263).  Verified bit-exact against PIL itself."""
     key = (in_size, out_size) if filter == "bilinear" else (in_size, out_size, filter)
     if key in _coeff_cache:
         return _coeff_cache[key]
@@ -426,7 +439,7 @@ def resample_coeffs(in_size, out_size, filter="bilinear"):
 
 
 def resize_u8(frames_u8, height, width, filter="bilinear"):
-    """PIL.Image.resize((width, height), BILINEAR | LANCZOS) of uint8 [V,Hi,Wi,3] frames on the device, bit for bit; the frames
+    """PIL.Image.resize((width, height), BILINEAR | LANCZOS | BICUBIC) of uint8 [V,Hi,Wi,3] frames on the device, bit for bit; the frames
     themselves when the size does not change (Pillow returns a copy then)."""
     V, Hi, Wi, _ = frames_u8.shape
     if (Hi, Wi) == (height, width):

@@ -375,6 +375,31 @@ size_t ew_voxel_reduce_workspace_bytes(size_t n);
 ew_status ew_voxel_reduce(const long long* sorted_keys, const long long* perm, size_t n, const float* xyz, const uint8_t* rgbx,
                           float* out_xyz, uint8_t* out_rgba, int* out_count, void* ws, unsigned long long* n_voxels, void* stream);
 
+/* Motion-JPEG frames encoded on the device (csrc/video.hip; added to ABI 19 without a bump: new symbols only).  The
+ * reference's Navigator.save_video / save_gif (evoworld/inference/navigator_evoworld.py:233-274) hand the frames to imageio / ffmpeg;
+ * here each frame becomes a baseline JPEG (ITU-T T.81: SOF0, 8 bit, JFIF YCbCr full range, Annex K Huffman tables, Annex K.1 / K.2
+ * quantisation tables under libjpeg's quality rule, restart interval = one MCU row) that evoworld_amd/video.py wraps in an AVI.
+ * subsampling: EW_JPEG_420 (MCU 16x16 = Y00 Y01 Y10 Y11 Cb Cr, chroma = the mean of 2x2 converted samples) or EW_JPEG_444 (MCU 8x8 =
+ * Y Cb Cr).  mcu_rows = ceil(H / mcu), mcu_cols = ceil(W / mcu); partial MCUs replicate the last column and row.
+ * ew_jpeg_dct_quant: frames uint8 [V,H,W,3] -> coef int16 [V, mcu_rows, mcu_cols, blocks_per_mcu, 64] (16-byte aligned), each block in
+ *   zigzag order: float32 colour transform, orthonormal 8x8 DCT-II (rows, then columns), round-half-even of the IEEE quotient c / t,
+ *   AC clamped to +-1023 and DC to [-1024, 1023].  quality 1 .. 100; V, H, W 1 .. 65535.
+ * ew_jpeg_entropy: one restart segment per MCU row of a frame (n_segments = V * mcu_rows, below 2^31): the Huffman-coded, byte-stuffed
+ *   bytes of segment s, padded with 1-bits, go to slots + s * slot_bytes and their count to seg_bytes[s] (device).  DC predictors start
+ *   at 0 in every segment.  slot_bytes >= ew_jpeg_segment_slot_bytes(mcu_cols, blocks_per_mcu), the provable worst case of 416 bytes
+ *   per block (26 bits per coefficient, doubled by stuffing); values outside what the tables hold are clamped, never overrun.
+ * ew_jpeg_pack: out[seg_offsets[s] ...] = segment s, followed by the marker RSTm (FF D0+m, m = row mod 8) unless s is its frame's last
+ *   row; seg_offsets int64 (device) is the caller's exclusive scan of seg_bytes + 2 (+ 0 for a last row); a segment that would leave
+ *   out_bytes is skipped.  No atomics anywhere: two calls return identical bytes. */
+#define EW_JPEG_420 420
+#define EW_JPEG_444 444
+size_t ew_jpeg_segment_slot_bytes(int mcu_cols, int blocks_per_mcu);
+ew_status ew_jpeg_dct_quant(const uint8_t* frames, int16_t* coef, int V, int H, int W, int quality, int subsampling, void* stream);
+ew_status ew_jpeg_entropy(const int16_t* coef, uint8_t* slots, int* seg_bytes, long long n_segments, int mcu_cols, int blocks_per_mcu,
+                          size_t slot_bytes, void* stream);
+ew_status ew_jpeg_pack(const uint8_t* slots, const int* seg_bytes, const long long* seg_offsets, uint8_t* out, long long n_segments,
+                       int mcu_rows, size_t slot_bytes, long long out_bytes, void* stream);
+
 /* Equirect -> perspective bilinear gather (pyequilib Equi2Pers restatement; unified_loop_consistency.py:299-334).
  * equi uint8 [F,He,We,3]; rot [F,3,3] f32 (camera->pano rotation); out uint8 [F,Hp,Wp,3]. */
 ew_status ew_equi2pers(const uint8_t* equi, const float* rot, uint8_t* out, int F, int He, int We, int Hp, int Wp,

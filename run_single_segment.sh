@@ -27,6 +27,9 @@ CMD="unified_loop_consistency.py --unet_path $CKPT --svd_path $CKPT --base_folde
 [ "$RANDOM_INIT" = true ] && CMD="$CMD --random_init"
 [ -n "$STAGES" ] && CMD="$CMD --stages $STAGES"
 [ "$QKV_FP8" = 1 ] && CMD="$CMD --qkv_fp8"      # opt-in fp8 (e4m3) q / k / v projections: BASELINE.json configs[4]
+[ "$SAVE_VIDEO" = 1 ] && CMD="$CMD --save_video"   # opt-in: navigated.avi + original.avi, Motion-JPEG encoded on the device
+[ -n "$VIDEO_FPS" ] && CMD="$CMD --video_fps $VIDEO_FPS"
+[ -n "$VIDEO_QUALITY" ] && CMD="$CMD --video_quality $VIDEO_QUALITY"
 
 if [ "$NUM_GPUS" -gt 1 ]; then
   python -m torch.distributed.run --nnodes=1 --nproc-per-node "$NUM_GPUS" --master-addr 127.0.0.1 --master-port ${MASTER_PORT:-29511} $CMD

@@ -29,6 +29,9 @@ CMD="unified_loop_consistency.py --unet_path $CKPT --svd_path $CKPT --base_folde
 [ "$QKV_FP8" = 1 ] && CMD="$CMD --qkv_fp8"      # opt-in fp8 (e4m3) q / k / v projections: BASELINE.json configs[4]
 [ "$EXPORT_GLB" = 1 ] && CMD="$CMD --export_glb"   # opt-in: glbscene_{seg}.glb of every hand-off's 3D memory
 [ -n "$MEMORY_VOXEL_SIZE" ] && CMD="$CMD --memory_voxel_size $MEMORY_VOXEL_SIZE"   # opt-in voxel-grid downsample of the memory
+[ "$SAVE_VIDEO" = 1 ] && CMD="$CMD --save_video"   # opt-in: navigated.avi (+ original.avi) per episode, Motion-JPEG encoded on the device
+[ -n "$VIDEO_FPS" ] && CMD="$CMD --video_fps $VIDEO_FPS"
+[ -n "$VIDEO_QUALITY" ] && CMD="$CMD --video_quality $VIDEO_QUALITY"
 
 if [ "$NUM_GPUS" -gt 1 ]; then
   python -m torch.distributed.run --nnodes=1 --nproc-per-node "$NUM_GPUS" --master-addr 127.0.0.1 --master-port ${MASTER_PORT:-29511} $CMD

@@ -8,6 +8,7 @@ Same flags as the reference.  Additions (all optional):
   --random_init              random U-Net weights of the full architecture instead of loading --unet_path
   --num_inference_steps N    (reference fixes 25)
   --height/--width           (reference fixes 576x1024)
+  --save_video               navigated.avi / original.avi per episode (Motion-JPEG, encoded on the device); --video_fps, --video_quality
   --qkv_fp8                  fp8 (e4m3) q / k / v projections in the U-Net's self-attention (BASELINE.json configs[4]); default off = fp16
 
 Launch on N GPUs:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 unified_loop_consistency.py ...
@@ -47,6 +48,10 @@ def parse_arguments(argv=None):
                    help="write every hand-off's 3D memory as glbscene_{seg}.glb under the episode's output directory (with its memory panoramas)")
     p.add_argument("--memory_voxel_size", type=float, default=None,
                    help="voxel-grid downsample of the 3D memory before the splat and the export (opt-in; scene units)")
+    p.add_argument("--save_video", action="store_true",
+                   help="write navigated.avi (and original.avi for an episode with panoramas): Motion-JPEG encoded on the device")
+    p.add_argument("--video_fps", type=float, default=10, help="frame rate of the --save_video files")
+    p.add_argument("--video_quality", type=int, default=90, help="JPEG quality (1..100) of the --save_video files")
     return p.parse_args(argv)
 
 
@@ -129,6 +134,10 @@ def run_single_segment(args, ep, pipe, unet, dev, out_dir, synthetic):
     if args.save_frames:
         _save_frames_u8(frames_u8, os.path.join(out_dir, "predictions"))                  # forward_evoworld.save_frames
         _save_frames_u8(ops.f32_chw_to_u8_hwc(batch["pixel_values"][0].float().contiguous()), os.path.join(out_dir, "predictions_gt"))
+    if args.save_video:                                                                   # the clip and its ground truth, as process_episode names them
+        from evoworld_amd.video import write_video
+        write_video(os.path.join(out_dir, "navigated.avi"), frames_u8, fps=args.video_fps, quality=args.video_quality)
+        write_video(os.path.join(out_dir, "original.avi"), batch["pixel_values"][0].float().to(dev), fps=args.video_fps, quality=args.video_quality)
     return {"episode": os.path.basename(ep), "frames": int(frames_u8.shape[0]), "seconds": round(dt, 3), "mode": "single_segment"}
 
 
@@ -155,9 +164,10 @@ def run_episode(args, ep, pipe, unet, dev, out_dir, synthetic):
     # the unscaled poses go in; process_episode derives the pos-scaled Navigator / Plücker path itself (pos_scale = 0.1);
     # --save_frames also writes the reference's per-segment dumps predictions_{seg}/ and perspective_look_at_center_{seg}/
     # ... and, for an episode folder with panoramas, the ground-truth windows predictions_gt_{seg}/ (:437-439)
-    frames = loop.process_episode(start, cam, save_dir=out_dir if args.save_frames or args.export_glb else None,
+    frames = loop.process_episode(start, cam, save_dir=out_dir if args.save_frames or args.export_glb or args.save_video else None,
                                   save_segment_frames=args.save_frames, episode_path=None if synthetic else ep,
-                                  export_memory=args.export_glb, memory_voxel_size=args.memory_voxel_size)
+                                  export_memory=args.export_glb, memory_voxel_size=args.memory_voxel_size,
+                                  save_video=args.save_video, video_fps=args.video_fps, video_quality=args.video_quality)
     torch.cuda.synchronize()
     dt = time.time() - t0
     if args.save_frames:
