@@ -91,7 +91,7 @@ __device__ __forceinline__ float ew_gelu(float x) { return 0.5f * x * (1.0f + ew
 // clamped at 64; beyond |g| = 8 the result is g or 0 to fp32 precision either way): max |gelu error| 2.6e-5 absolute (fp32
 // evaluation included), i.e. 1/19 of the fp16 ulp at 1.0 the result is rounded to -- measured effect on the forward's rel-L2
 // against the fp32 oracle: none (tests/test_gpu_unet.py).  13 issue slots per PAIR instead of the 31 of the A&S 7.1.26 erf form
-// used before (ew_vgelu2_erf, kept for A/B: -DEW_GEGLU_ERF): the GEGLU epilogue of the K = 320 feed-forward GEMMs was a third of
+// used before (ew_vgelu2_erf; ff_fused.hip still uses it: its output is the split stream, which resolves the 2.6e-5): the GEGLU epilogue of the K = 320 feed-forward GEMMs was a third of
 // their run time.
 __device__ __forceinline__ f32x2 ew_vgelu2_erf(f32x2 v, f32x2 g) {
     const f32x2 ag = {fabsf(g[0]), fabsf(g[1])};

@@ -981,19 +981,51 @@ def ff_pack(w1, b1, w2):
 
 def ff_geglu320(x, pack, b2, out, *, rowbias=None, rows_per_group=1, ld_rowbias=None, r1=None, r2=None, c_acc=1.0, c_r1=1.0, c_r2=1.0):
     """out = c_acc * (GEGLU(x W1^T + b1) W2^T + b2 + rowbias) + c_r1 * r1 + c_r2 * r2 for 320-channel tokens, one kernel
-    (ew_ff_geglu320_f16): x fp16 [M, 320] (the LayerNorm output), pack = ff_pack(...); r1 / r2 / out tensors or `Res`."""
+    (ew_ff_geglu320_f16): x fp16 [M, 320] (the LayerNorm output), pack = ff_pack(...); r1 / r2 / out tensors or `Res`, every plane
+    a contiguous [M, 320]; b2 fp16 [320]; rowbias fp16 [>= ceil(M / rows_per_group), >= 320] with row stride ld_rowbias."""
     _req(x, torch.float16, "x")
     a = _lib.FfArgs()
     r1h, r1l = _hl(r1)
     r2h, r2l = _hl(r2)
     oh, ol = _hl(out)
     w1p, b1p, w2p = pack
+    # the ABI carries no stride for r1 / r2 / out or their lo planes and no extent for b2 / rowbias: anything but dense [M, 320]
+    # planes would make the kernel read or write other memory, so it is refused here
+    if x.dim() != 2:
+        raise ValueError(f"x must be [M, 320] (got {tuple(x.shape)})")
+    M = x.shape[0]
+    if oh is None:
+        raise ValueError("out is required")
+    for t, dtype, name in ((oh, torch.float16, "out"), (ol, torch.int8, "out lo plane"), (r1h, torch.float16, "r1"), (r1l, torch.int8, "r1 lo plane"),
+                           (r2h, torch.float16, "r2"), (r2l, torch.int8, "r2 lo plane")):
+        if t is not None:
+            _req(t, dtype, name)
+            if tuple(t.shape) != (M, x.shape[1]):
+                raise ValueError(f"{name} must be [{M}, {x.shape[1]}] like x (got {tuple(t.shape)})")
+    _req(b2, torch.float16, "b2")
+    if tuple(b2.shape) != (x.shape[1],):
+        raise ValueError(f"b2 must be [{x.shape[1]}] (got {tuple(b2.shape)})")
+    if ld_rowbias is None:
+        ld_rowbias = x.shape[1]
+    if rowbias is not None:
+        if rowbias.device.type != "cuda":
+            raise _lib.EvoWorldHipError(f"rowbias must live on the GPU (got {rowbias.device}); evoworld_amd has no CPU path")
+        if rowbias.dtype != torch.float16:
+            raise TypeError(f"rowbias: expected {torch.float16}, got {rowbias.dtype}")
+        if rows_per_group < 1:
+            raise ValueError(f"rows_per_group must be >= 1 (got {rows_per_group})")
+        n_groups = (M + rows_per_group - 1) // rows_per_group
+        if rowbias.dim() != 2 or rowbias.shape[1] < x.shape[1] or rowbias.stride(1) != 1 or (rowbias.shape[0] > 1 and rowbias.stride(0) != ld_rowbias):
+            raise ValueError(f"rowbias must be [groups, >= {x.shape[1]}] with unit column stride and row stride ld_rowbias = {ld_rowbias} "
+                             f"(got shape {tuple(rowbias.shape)}, strides {tuple(rowbias.stride())})")
+        if rowbias.shape[0] < n_groups:
+            raise ValueError(f"rowbias has {rowbias.shape[0]} rows; {M} rows in groups of {rows_per_group} need {n_groups}")
     a.x, a.w1p, a.b1p, a.w2p, a.b2, a.rowbias = _ptr(x), _ptr(w1p), _ptr(b1p), _ptr(w2p), _ptr(b2), _ptr(rowbias)
     a.r1, a.r1_lo, a.r2, a.r2_lo, a.out, a.out_lo = _ptr(r1h), _ptr(r1l), _ptr(r2h), _ptr(r2l), _ptr(oh), _ptr(ol)
     a.zero_page = _ptr(zero_page(x.device))
     a.M, a.C, a.hidden = x.shape[0], x.shape[1], w2p.shape[0] * 32
     a.rows_per_group = rows_per_group
-    a.ld_rowbias = ld_rowbias if ld_rowbias is not None else x.shape[1]
+    a.ld_rowbias = ld_rowbias
     a.c_acc, a.c_r1, a.c_r2 = c_acc, c_r1, c_r2
     _call("ew_ff_geglu320_f16", ctypes.byref(a))
     return out
