@@ -8,15 +8,24 @@
 namespace {
 
 // ---------------------------------------------------------------------------------------------
-// GroupNorm statistics: deterministic and cancellation-safe.
+// GroupNorm statistics: deterministic and cancellation-safe, whatever any single row holds.
 //   stage 1 (gn_stats_kernel): grid = (row chunks, n_slabs); block = PL * VPP threads (VPP = C_src/8 vectors per row, PL
-//     row-lanes).  Every thread owns one fixed 8-channel vector and accumulates SHIFTED sums  s = sum(x - K_c),
-//     q = sum((x - K_c)^2)  with the pivot K_c = x[slab, row 0, c] (the same for every block of the slab, so partials add up;
-//     |mean_c - K_c| ~ std_c, which keeps q - s^2/n free of the E[x^2] - mean^2 cancellation).  The PL row-lanes of a block
-//     are combined through LDS in a FIXED order and the block writes one (s, q) pair per channel to
-//     part[slab][chunk][C_tot][2] -- no atomics anywhere.
-//   stage 2 (gn_finalize_kernel): one wave per (slab, group): lanes own channels, loop over the chunks in order, then a
-//     fixed shuffle tree: mean_g, var_g (two-level: per-channel mean / M2, then across the group's channels).
+//     row-lanes).  Every thread owns one fixed 8-channel vector and accumulates SHIFTED sums  s = sum(x - K),
+//     q = sum((x - K)^2)  over its rows r0 + pl, r0 + pl + PL, ... with a pivot of ITS OWN: K = the thread's first row.  After
+//     its loop it turns (n_t, s, q) into (n_t, mean_t = K + s/n_t, M2_t = q - s^2/n_t).  |mean_t - K| ~ std as long as the
+//     thread's first row is a typical one, which keeps q - s^2/n_t free of the E[x^2] - mean^2 cancellation; a first row that
+//     is far from the rest (row 0 of a slab is the corner pixel of a frame: zero padding, a saturated value) costs the
+//     cancellation over that one thread's n_t <= rows_per_block / PL rows, not over all rows of the slab.  (Until this form the
+//     pivot was x[slab, row 0, c] for every block, so that the partial sums could simply be added: one atypical row 0 put
+//     an error of ~2^-24 * rows * (K - mean)^2 / var on the variance, 1e-3 of rstd at 9216 rows.)
+//     The PL row-lanes of a block are combined through LDS in a FIXED order with Chan's formula, all items at once:
+//         n = sum n_k,  mean = ref + sum n_k (mean_k - ref) / n,  M2 = sum (M2_k + n_k (mean_k - mean)^2)
+//     (ref = the first item's mean, so that the sums run over differences of the size of std, not over the mean itself)
+//     and the block writes one (mean, M2) pair per channel to part[slab][chunk][C_tot][2]; the row counts follow from the
+//     launch geometry and are not stored.  No atomics anywhere.
+//   stage 2 (gn_finalize_kernel): one block per (slab, group): the chunks of a channel are combined the same way in a fixed
+//     order (pairwise, gn_chan, where a thread walks several chunks), then the group's channels through a fixed shuffle tree
+//     (per-channel mean / M2 -> mean_g, var_g).
 // The chunking depends on (rows, n_slabs) only, so the two sources of a virtual channel concat share one partial buffer.
 // x_lo (may be null): lo8 companion of a split residual stream (common.h: one byte per element, same element strides).
 // ---------------------------------------------------------------------------------------------
@@ -29,24 +38,41 @@ inline int gn_chunks(int n_slabs, int rows) {
     return want < 1 ? 1 : want;
 }
 
+// Chan's pairwise combine of the (n, mean, M2) of b into a; an empty b (nb == 0) leaves a as it is.  The weight nb / n through
+// the hardware reciprocal (1 ulp): a chain of these with an IEEE division per step showed in gn_finalize_kernel (6.4 -> 8.3 us
+// at the level-0 launch), which is also why the LDS combines take all their items at once instead
+__device__ __forceinline__ void gn_chan(float& na, float& ma, float& Ma, float nb, float mb, float Mb) {
+    if (nb > 0.f) {
+        const float n = na + nb, w = __fdividef(nb, n), d = mb - ma;
+        ma = fmaf(d, w, ma);
+        Ma = fmaf(d * d, na * w, Ma + Mb);
+        na = n;
+    }
+}
+
 __global__ void gn_stats_kernel(const f16* __restrict__ x, const int8_t* __restrict__ x_lo, float* __restrict__ part,
-                                float* __restrict__ pivot, int rows, int C_src, int c_off, int C_tot, int VPP, int PL,
-                                int rows_per_block) {
+                                int rows, int C_src, int c_off, int C_tot, int VPP, int PL, int rows_per_block) {
     extern __shared__ float lds[];  // [PL][2][C_src]
     const int tid = threadIdx.x;
     const int slab = blockIdx.y;
     const int v = tid % VPP, pl = tid / VPP;
     const int r0 = blockIdx.x * rows_per_block;
     const int r1 = min(rows, r0 + rows_per_block);
+    // rows of this block (none when the chunk starts past the last row) and of row-lane k: nb / PL, one more for k < nb % PL
+    const int nb = max(r1 - r0, 0), nlo = nb / PL, nrem = nb - nlo * PL;
+    const int nt = nlo + (pl < nrem ? 1 : 0);
     float s[8], q[8], piv[8];
     const size_t slab_off = ((size_t)slab * rows) * C_src + v * 8;
     const f16* base = x + slab_off;
     const int8_t* base_lo = x_lo ? x_lo + slab_off : nullptr;
-    {
-        const f16x8 p0 = *(const f16x8*)base;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { s[e] = 0.f; q[e] = 0.f; piv[e] = (float)p0[e]; }
-        if (base_lo) ew_split_dec8(p0, *(const u32x2*)base_lo, piv);
+    for (int e = 0; e < 8; ++e) { s[e] = 0.f; q[e] = 0.f; piv[e] = 0.f; }
+    if (nt > 0) {                                   // the pivot: this thread's first row
+        const size_t o = (size_t)(r0 + pl) * C_src;
+        const f16x8 p0 = *(const f16x8*)(base + o);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) piv[e] = (float)p0[e];
+        if (base_lo) ew_split_dec8(p0, *(const u32x2*)(base_lo + o), piv);
     }
     // eight independent 16-byte loads in flight per thread (one dependent load per iteration ran at 3.3 TB/s, four at 3.8)
     int r = r0 + pl;
@@ -107,32 +133,41 @@ __global__ void gn_stats_kernel(const f16* __restrict__ x, const int8_t* __restr
             }
         }
     }
+    // (n_t, s, q) -> (n_t, mean_t, M2_t); a thread without rows leaves (0, 0), which the combine skips
     float* mine = lds + (size_t)pl * 2 * C_src;
+    const float inv_n = 1.f / (float)max(nt, 1);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        mine[v * 8 + e] = s[e];
-        mine[C_src + v * 8 + e] = q[e];
+        const float d = s[e] * inv_n;
+        mine[v * 8 + e] = piv[e] + d;
+        mine[C_src + v * 8 + e] = fmaxf(q[e] - s[e] * d, 0.f);
     }
     __syncthreads();
     float* dst = part + (((size_t)slab * gridDim.x + blockIdx.x) * C_tot + c_off) * 2;
     for (int c = tid; c < C_src; c += blockDim.x) {
-        float ss = 0.f, qq = 0.f;
-        for (int k = 0; k < PL; ++k) { ss += lds[(size_t)k * 2 * C_src + c]; qq += lds[(size_t)k * 2 * C_src + C_src + c]; }
-        *(f32x2*)(dst + 2 * c) = (f32x2){ss, qq};
-    }
-    if (blockIdx.x == 0 && pl == 0) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) pivot[(size_t)slab * C_tot + c_off + v * 8 + e] = piv[e];
+        // All PL items at once, in order (no chain of dependent steps): d = sum(n_k d_k) / n, M2 = sum(M2_k + n_k (d_k - d)^2) with
+        // d_k = mean_k - ref, ref = row-lane 0's mean: the sums are then of the size of the differences between the lanes, not of
+        // the mean itself (summing the means themselves, rounded at ulp(mean) in every step, cost 5e-5 std at mean / std = 300)
+        const float ref = lds[c];
+        float sd = 0.f;
+        for (int k = 0; k < PL; ++k) sd += (float)(nlo + (k < nrem ? 1 : 0)) * (lds[(size_t)k * 2 * C_src + c] - ref);
+        const float dm = nb > 0 ? sd / (float)nb : 0.f;
+        float M2 = 0.f;
+        for (int k = 0; k < PL; ++k) {
+            const float dk = lds[(size_t)k * 2 * C_src + c] - ref - dm;
+            M2 += lds[(size_t)k * 2 * C_src + C_src + c] + (float)(nlo + (k < nrem ? 1 : 0)) * dk * dk;
+        }
+        *(f32x2*)(dst + 2 * c) = (f32x2){ref + dm, M2};     // an empty block writes (0, 0): finalize gives it no rows, but reads it
     }
 }
 
-// one 256-thread block per (slab, group): stats[slab][g] = (mean, biased variance).  Thread (kc, c) sums the chunks
-// kc, kc+KP, ... of channel c in order; the KP chunk-lanes of a channel are combined in order through LDS; the group's
-// channels go through a fixed shuffle tree.  (One wave per group looping over all chunks took 29 us per call.)
-__global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restrict__ part, const float* __restrict__ pivot,
-                                                          float* __restrict__ stats, int n_slabs, int rows, int C_tot,
-                                                          int groups, int chunks) {
-    __shared__ float red[2][256];
+// one 256-thread block per (slab, group): stats[slab][g] = (mean, biased variance).  Thread (kc, c) combines the chunks
+// kc, kc+KP, ... of channel c in order (gn_chan; chunk k holds min(rows - k * rpb, rpb) rows, none when that is <= 0); the KP
+// chunk-lanes of a channel are combined in order through LDS; the group's channels go through a fixed shuffle tree.
+// (One wave per group looping over all chunks took 29 us per call.)
+__global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restrict__ part, float* __restrict__ stats, int n_slabs,
+                                                          int rows, int C_tot, int groups, int chunks) {
+    __shared__ float red[3][256];
     __shared__ float chan[2][512];             // per-channel mean, M2 (gs <= 512)
     __shared__ float wsum[4];
     const int tid = threadIdx.x;
@@ -141,26 +176,33 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
     const float n = (float)rows;
     const int cw = gs < 256 ? gs : 256;        // channels handled per pass
     const int KP = 256 / cw;                   // chunk-lanes per channel
+    const int rpb = (rows + chunks - 1) / chunks;
     for (int c0 = 0; c0 < gs; c0 += cw) {
         const int c = c0 + tid % cw, kc = tid / cw;
-        float ss = 0.f, qq = 0.f;
+        float na = 0.f, ma = 0.f, Ma = 0.f, ref = 0.f;
         if (kc < KP && c < gs) {
             const float* p = part + (((size_t)slab * chunks) * C_tot + g * gs + c) * 2;
+            ref = p[0];                            // means relative to chunk 0's, as in the statistics kernel's combine
             for (int k = kc; k < chunks; k += KP) {
                 const f32x2 v = *(const f32x2*)(p + (size_t)k * C_tot * 2);
-                ss += v[0];
-                qq += v[1];
+                gn_chan(na, ma, Ma, (float)max(min(rows - k * rpb, rpb), 0), v[0] - ref, v[1]);
             }
         }
-        red[0][tid] = ss;
-        red[1][tid] = qq;
+        red[0][tid] = na;
+        red[1][tid] = ma;
+        red[2][tid] = Ma;
         __syncthreads();
-        if (tid < cw && c0 + tid < gs) {
-            float s2 = 0.f, q2 = 0.f;
-            for (int k = 0; k < KP; ++k) { s2 += red[0][k * cw + tid]; q2 += red[1][k * cw + tid]; }
-            const float d = s2 / n;
-            chan[0][c0 + tid] = pivot[(size_t)slab * C_tot + g * gs + c0 + tid] + d;     // channel mean
-            chan[1][c0 + tid] = fmaxf(q2 - s2 * d, 0.f);                                  // channel M2
+        if (tid < cw && c0 + tid < gs) {           // chunk-lane 0 of channel c0 + tid: ref is that channel's
+            const int lanes = min(KP, chunks);     // chunk-lanes past the last chunk hold nothing
+            float sd = 0.f, M = 0.f;               // all lanes at once, as in the statistics kernel (their rows add up to n)
+            for (int k = 0; k < lanes; ++k) sd += red[0][k * cw + tid] * red[1][k * cw + tid];
+            const float dm = sd / n;
+            for (int k = 0; k < lanes; ++k) {
+                const float dk = red[1][k * cw + tid] - dm;
+                M += red[2][k * cw + tid] + red[0][k * cw + tid] * dk * dk;
+            }
+            chan[0][c0 + tid] = ref + dm;                                                 // channel mean
+            chan[1][c0 + tid] = M;                                                        // channel M2
         }
         __syncthreads();
     }
@@ -373,18 +415,17 @@ __global__ __launch_bounds__(256) void ln_kernel(const f16* __restrict__ x, cons
 
 extern "C" size_t ew_groupnorm_workspace_floats(int n_slabs, int rows, int C_tot, int groups) {
     if (n_slabs <= 0 || rows <= 0 || C_tot <= 0 || groups <= 0) return 0;
-    // partials [n_slabs][chunks][C_tot][2] | pivots [n_slabs][C_tot] | stats [n_slabs][groups][2]
-    return (size_t)n_slabs * gn_chunks(n_slabs, rows) * C_tot * 2 + (size_t)n_slabs * C_tot + (size_t)n_slabs * groups * 2;
+    // partials [n_slabs][chunks][C_tot][2] | stats [n_slabs][groups][2]
+    return (size_t)n_slabs * gn_chunks(n_slabs, rows) * C_tot * 2 + (size_t)n_slabs * groups * 2;
 }
 
 namespace {
-struct GnWs { float* part; float* pivot; float* stats; int chunks; };
+struct GnWs { float* part; float* stats; int chunks; };
 inline GnWs gn_ws(float* ws, int n_slabs, int rows, int C_tot) {
     GnWs w;
     w.chunks = gn_chunks(n_slabs, rows);
     w.part = ws;
-    w.pivot = ws + (size_t)n_slabs * w.chunks * C_tot * 2;
-    w.stats = w.pivot + (size_t)n_slabs * C_tot;
+    w.stats = ws + (size_t)n_slabs * w.chunks * C_tot * 2;
     return w;
 }
 }  // namespace
@@ -399,12 +440,14 @@ extern "C" ew_status ew_groupnorm_stats_f16(const void* x, const void* x_lo, flo
     const int PL = VPP >= 256 ? 1 : 256 / VPP;
     const GnWs w = gn_ws(ws, n_slabs, rows, C_tot);
     const int rpb = ew_cdiv(rows, w.chunks);
-    // chunks whose first row is past the end would leave their partial slot unwritten: rpb*(chunks-1) < rows always holds
+    // rpb * (chunks - 1) < rows does NOT always hold (rows = 40000 in one slab: 512 chunks of 79 rows, and chunks 507..511 start past
+    // the last row).  Such a block reads no row and still writes its partial, (0, 0); finalize gives it no rows.  No partial slot
+    // is ever left unwritten (tests/test_gpu_groupnorm.py, "40000 rows").
     dim3 grid(w.chunks, n_slabs);
     const size_t lds = (size_t)PL * 2 * C_src * sizeof(float);
     EW_REQUIRE(lds <= 64 * 1024, "ew_groupnorm_stats_f16: C_src too large for the LDS combine");
     hipLaunchKernelGGL(gn_stats_kernel, grid, dim3(VPP * PL), lds, (hipStream_t)stream, (const f16*)x, (const int8_t*)x_lo,
-                       w.part, w.pivot, rows, C_src, c_off, C_tot, VPP, PL, rpb);
+                       w.part, rows, C_src, c_off, C_tot, VPP, PL, rpb);
     return ew_check_launch("ew_groupnorm_stats_f16");
 }
 
@@ -414,7 +457,7 @@ extern "C" ew_status ew_groupnorm_finalize(float* ws, int n_slabs, int rows, int
                "ew_groupnorm_finalize: bad shape");
     const GnWs w = gn_ws(ws, n_slabs, rows, C_tot);
     hipLaunchKernelGGL(gn_finalize_kernel, dim3(n_slabs * groups), dim3(256), 0, (hipStream_t)stream,
-                       w.part, w.pivot, w.stats, n_slabs, rows, C_tot, groups, w.chunks);
+                       w.part, w.stats, n_slabs, rows, C_tot, groups, w.chunks);
     return ew_check_launch("ew_groupnorm_finalize");
 }
 

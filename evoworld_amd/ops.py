@@ -170,7 +170,7 @@ def linear(x, w, bias=None, out=None, split_out=False, **kw):
 
 
 class WorkspacePool:
-    """fp32 scratch for the GroupNorm statistics of one forward (partials, pivots, stats: all written before they are read, so
+    """fp32 scratch for the GroupNorm statistics of one forward (partials, stats: all written before they are read, so
     nothing is zeroed).  `reset()` rewinds; `take(n)` hands out the next n floats."""
 
     def __init__(self, device, floats=8 << 20):

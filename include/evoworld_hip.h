@@ -165,10 +165,11 @@ ew_status ew_ff_geglu320_f16(const ew_ff_args* args, void* stream);
  * [c_off, c_off+C_src) that live in tensor `x` ([n_slabs*rows, C_src]); a skip-concat input is covered by
  * two calls (one per source) -- groups may straddle the seam.  x_lo (may be NULL) is the lo8 companion of a
  * split residual stream (int8, one byte per element, see ew_gemm_args).
- * Statistics are DETERMINISTIC and cancellation-safe (no atomics): ew_groupnorm_stats_f16 writes per-(slab, row chunk,
- * channel) sums of (x - K_c) and (x - K_c)^2 shifted by the pivot K_c = x[slab, row 0, c] into the workspace;
- * ew_groupnorm_finalize (one call per GroupNorm, after the stats calls of all its sources) reduces them in a fixed
- * order to (mean, biased variance) per (slab, group); ew_groupnorm_apply_f16 reads those.
+ * Statistics are DETERMINISTIC and cancellation-safe (no atomics), whatever a single row holds: ew_groupnorm_stats_f16
+ * writes a per-(slab, row chunk, channel) (mean, M2) pair into the workspace -- every thread sums (x - K) and (x - K)^2
+ * shifted by a pivot of its own, K = the first row it reads, and the threads of a chunk are combined with Chan's formula;
+ * ew_groupnorm_finalize (one call per GroupNorm, after the stats calls of all its sources) combines the chunks the same
+ * way in a fixed order to (mean, biased variance) per (slab, group); ew_groupnorm_apply_f16 reads those.
  * `ws`: ew_groupnorm_workspace_floats(n_slabs, rows, C_tot, groups) floats, uninitialised, private to this GroupNorm call.
  *        slab n = `rows` consecutive rows (rows = H*W for the per-frame GN of ResnetBlock2D / transformer
  *        norm / conv_norm_out; rows = T*H*W for TemporalResnetBlock's GN over [B,C,T,H,W]).
