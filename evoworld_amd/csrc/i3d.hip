@@ -1,28 +1,18 @@
-// i3d.hip -- the non-GEMM kernels of FVD's I3D network (Inception-v1 inflated to 3-D, 400 Kinetics classes) for the evaluation CLI (ABI 16).
-// Reference: evoworld/metrics/fvd/styleganv/fvd.py (preprocess_single, frechet_distance) and evoworld/metrics/fvd/videogpt/pytorch_i3d.py
-// (InceptionI3d).  The 57 BatchNorm-folded convolutions run on ew_gemm_f16 (dense mode, bias vector) over the patch rows
-// ew_im2col3d_f16 writes; conv outputs are stored PRE-ReLU and every reader below applies max(x, 0) itself (the GEMM has no ReLU
-// epilogue; ReLU commutes with max-pooling, and zero padding of a max pool over non-negative values equals skipping the taps).
+// i3d.hip -- the kernels only FVD's I3D network has (Inception-v1 inflated to 3-D, 400 Kinetics classes; ABI 16): the clip preprocessing and
+// the head.  Reference: evoworld/metrics/fvd/styleganv/fvd.py (preprocess_single, frechet_distance) and
+// evoworld/metrics/fvd/videogpt/pytorch_i3d.py (InceptionI3d).  The 57 BatchNorm-folded convolutions run on ew_gemm_f16 (dense mode, bias
+// vector) over the patch rows of ew_im2col3d_f16, the max pools on ew_maxpool3d_relu_f16 (convnet.hip); conv outputs are stored PRE-ReLU
+// and the head applies max(x, 0) itself.
 // Compiled with -ffp-contract=off: the resize's k / 255, source index, weights and blend are rounded where torch's CPU kernel rounds them.
 // preprocess_single runs on the host in the reference, and torch's x86 builds (AVX2 / AVX-512 code paths) contract the source index to
 // fma(scale, i + 0.5, -0.5) and each two-term blend t0 * w0 + t1 * w1 to fma(t0, w0, t1 * w1): the fmaf calls below are those, spelled out.
-#include "common.h"
+#include "convnet.h"
 #include <math.h>
 
 namespace {
 
-constexpr int NT = 256;
 constexpr int SIDE = 224;                                  // I3D's input resolution
 constexpr int HEAD_C = 1024, HEAD_HW = 49, HEAD_N = 400;   // Mixed_5c channels, its 7 x 7 pixels, Kinetics classes
-
-struct Dim3 { int t, h, w; };
-
-__device__ __forceinline__ uint4 relu8(uint4 raw) {
-    f16x8 v = *reinterpret_cast<f16x8*>(&raw);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = v[e] > (f16)0 ? v[e] : (f16)0;
-    return *reinterpret_cast<uint4*>(&v);
-}
 
 // torch's bilinear source index (align_corners=False) in float32: i -> (i0, i1, lambda); equal sizes copy (lambda = 0 either way)
 __device__ __forceinline__ void src_index(int i, float scale, int n_in, int& i0, int& i1, float& l1) {
@@ -72,66 +62,6 @@ __global__ __launch_bounds__(NT) void video_preprocess_kernel(const void* __rest
             v[c] = (f16)((val - 0.5f) * 2.0f);
         }
         *reinterpret_cast<f16x8*>(out + i * 8) = v;
-    }
-}
-
-// fp16 [T,H,W,C] source, C % 8 == 0: one thread per 8 output columns (one 16-byte load and store; a vector never straddles a tap)
-template <bool RELU>
-__global__ __launch_bounds__(NT) void im2col3d_kernel(const f16* __restrict__ src, f16* __restrict__ out, long long total_vec, Dim3 in, int C,
-                                                      Dim3 k, Dim3 s, Dim3 p, Dim3 o, int ldk8, int kC) {
-    for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < total_vec; i += (long long)gridDim.x * NT) {
-        const int col8 = (int)(i % ldk8);
-        long long row = i / ldk8;
-        const int kk = col8 * 8;
-        uint4 v = make_uint4(0u, 0u, 0u, 0u);
-        if (kk < kC) {
-            int tap = kk / C;
-            const int c = kk - tap * C;
-            const int dx = tap % k.w;
-            tap /= k.w;
-            const int dy = tap % k.h, dt = tap / k.h;
-            const int ox = (int)(row % o.w);
-            row /= o.w;
-            const int oy = (int)(row % o.h), ot = (int)(row / o.h);
-            const int it = ot * s.t + dt - p.t, iy = oy * s.h + dy - p.h, ix = ox * s.w + dx - p.w;
-            if (it >= 0 && it < in.t && iy >= 0 && iy < in.h && ix >= 0 && ix < in.w) {
-                v = *reinterpret_cast<const uint4*>(src + (((long long)it * in.h + iy) * in.w + ix) * C + c);
-                if (RELU) v = relu8(v);
-            }
-        }
-        *reinterpret_cast<uint4*>(out + i * 8) = v;
-    }
-}
-
-// max over the window's taps inside the input of max(x, 0); 8 channels per thread
-__global__ __launch_bounds__(NT) void maxpool3d_relu_kernel(const f16* __restrict__ src, f16* __restrict__ out, long long total_vec, Dim3 in, int C8,
-                                                            Dim3 k, Dim3 s, Dim3 p, Dim3 o) {
-    for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < total_vec; i += (long long)gridDim.x * NT) {
-        const int c8 = (int)(i % C8);
-        long long r = i / C8;
-        const int ox = (int)(r % o.w);
-        r /= o.w;
-        const int oy = (int)(r % o.h), ot = (int)(r / o.h);
-        f16x8 m;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) m[e] = (f16)0;
-        for (int dt = 0; dt < k.t; ++dt) {
-            const int it = ot * s.t + dt - p.t;
-            if (it < 0 || it >= in.t) continue;
-            for (int dy = 0; dy < k.h; ++dy) {
-                const int iy = oy * s.h + dy - p.h;
-                if (iy < 0 || iy >= in.h) continue;
-                for (int dx = 0; dx < k.w; ++dx) {
-                    const int ix = ox * s.w + dx - p.w;
-                    if (ix < 0 || ix >= in.w) continue;
-                    const uint4 raw = *reinterpret_cast<const uint4*>(src + ((((long long)it * in.h + iy) * in.w + ix) * C8 + c8) * 8);
-                    const f16x8 v = *reinterpret_cast<const f16x8*>(&raw);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) m[e] = v[e] > m[e] ? v[e] : m[e];
-                }
-            }
-        }
-        *reinterpret_cast<f16x8*>(out + i * 8) = m;
     }
 }
 
@@ -186,11 +116,6 @@ __global__ __launch_bounds__(NT) void i3d_head_logits_kernel(const float* __rest
     if (lane == 0) out[n] = s + b[n];
 }
 
-inline int grid_for(long long total) {
-    long long b = (total + NT - 1) / NT;
-    return (int)(b < 8192 ? b : 8192);
-}
-
 }  // namespace
 
 extern "C" ew_status ew_video_preprocess_f16(const void* src, int src_kind, void* out, int T, int H, int W, int h_resized, int w_resized, int y0,
@@ -211,48 +136,6 @@ extern "C" ew_status ew_video_preprocess_f16(const void* src, int src_kind, void
     else
         hipLaunchKernelGGL(video_preprocess_kernel<2>, dim3(grid_for(total)), dim3(NT), 0, st, src, (f16*)out, total, H, W, sh, sw, y0, x0, swap_rb ? 1 : 0);
     return ew_check_launch("video_preprocess_kernel");
-}
-
-// shared geometry checks of the two window kernels: every window starts inside the padded input and overlaps the input itself
-#define EW_REQUIRE_WINDOWS(name)                                                                                                              \
-    EW_REQUIRE(t_in > 0 && h_in > 0 && w_in > 0 && C > 0 && C % 8 == 0, name ": needs T, H, W > 0 and C %% 8 == 0 (%d x %d x %d x %d)", t_in, \
-               h_in, w_in, C);                                                                                                                \
-    EW_REQUIRE(kt > 0 && kh > 0 && kw > 0 && st > 0 && sh > 0 && sw > 0, name ": kernel (%d,%d,%d) / stride (%d,%d,%d) must be positive", kt, \
-               kh, kw, st, sh, sw);                                                                                                           \
-    EW_REQUIRE(pt >= 0 && pt < kt && ph >= 0 && ph < kh && pw >= 0 && pw < kw, name ": front pads (%d,%d,%d) must lie in [0, kernel)", pt, ph, \
-               pw);                                                                                                                           \
-    EW_REQUIRE(t_out > 0 && h_out > 0 && w_out > 0 && (long long)(t_out - 1) * st - pt < t_in && (long long)(h_out - 1) * sh - ph < h_in &&   \
-                   (long long)(w_out - 1) * sw - pw < w_in,                                                                                   \
-               name ": an output of %d x %d x %d has windows that miss the %d x %d x %d input", t_out, h_out, w_out, t_in, h_in, w_in);      \
-    EW_REQUIRE((long long)t_in * h_in * w_in < (1LL << 31) && (long long)t_out * h_out * w_out < (1LL << 31), name ": clip too large");     \
-    EW_REQUIRE((uintptr_t)src % 16 == 0 && (uintptr_t)out % 16 == 0, name ": pointers must be 16-byte aligned")
-
-extern "C" ew_status ew_im2col3d_f16(const void* src, void* out, int t_in, int h_in, int w_in, int C, int kt, int kh, int kw, int st, int sh,
-                                     int sw, int pt, int ph, int pw, int t_out, int h_out, int w_out, int ldk, int relu, void* stream) {
-    EW_REQUIRE(src && out, "ew_im2col3d_f16: NULL pointer");
-    EW_REQUIRE_WINDOWS("ew_im2col3d_f16");
-    const long long kC = (long long)kt * kh * kw * C;
-    EW_REQUIRE(kC <= ldk && ldk % 8 == 0, "ew_im2col3d_f16: ldk = %d must be a multiple of 8 and >= kt*kh*kw*C = %lld", ldk, kC);
-    const long long total_vec = (long long)t_out * h_out * w_out * (ldk / 8);
-    const Dim3 in{t_in, h_in, w_in}, k{kt, kh, kw}, s{st, sh, sw}, p{pt, ph, pw}, o{t_out, h_out, w_out};
-    if (relu)
-        hipLaunchKernelGGL(im2col3d_kernel<true>, dim3(grid_for(total_vec)), dim3(NT), 0, (hipStream_t)stream, (const f16*)src, (f16*)out, total_vec,
-                           in, C, k, s, p, o, ldk / 8, (int)kC);
-    else
-        hipLaunchKernelGGL(im2col3d_kernel<false>, dim3(grid_for(total_vec)), dim3(NT), 0, (hipStream_t)stream, (const f16*)src, (f16*)out, total_vec,
-                           in, C, k, s, p, o, ldk / 8, (int)kC);
-    return ew_check_launch("im2col3d_kernel");
-}
-
-extern "C" ew_status ew_maxpool3d_relu_f16(const void* src, void* out, int t_in, int h_in, int w_in, int C, int kt, int kh, int kw, int st, int sh,
-                                           int sw, int pt, int ph, int pw, int t_out, int h_out, int w_out, void* stream) {
-    EW_REQUIRE(src && out, "ew_maxpool3d_relu_f16: NULL pointer");
-    EW_REQUIRE_WINDOWS("ew_maxpool3d_relu_f16");
-    const long long total_vec = (long long)t_out * h_out * w_out * (C / 8);
-    const Dim3 in{t_in, h_in, w_in}, k{kt, kh, kw}, s{st, sh, sw}, p{pt, ph, pw}, o{t_out, h_out, w_out};
-    hipLaunchKernelGGL(maxpool3d_relu_kernel, dim3(grid_for(total_vec)), dim3(NT), 0, (hipStream_t)stream, (const f16*)src, (f16*)out, total_vec, in,
-                       C / 8, k, s, p, o);
-    return ew_check_launch("maxpool3d_relu_kernel");
 }
 
 extern "C" size_t ew_i3d_head_workspace_bytes(void) { return HEAD_C * sizeof(float); }

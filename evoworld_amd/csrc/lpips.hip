@@ -1,56 +1,20 @@
-// lpips.hip -- the non-GEMM kernels of LPIPS (AlexNet backbone) for the evaluation CLI (ABI 14).
+// lpips.hip -- the kernels only LPIPS (AlexNet backbone) has (ABI 14): the first layer's patch gather from the frames and the head.
 // Reference: evoworld/metrics/other_metrics/calculate_lpips.py and calculate_all_metrics.py:195-221, i.e. lpips.LPIPS(net='alex',
 // spatial=True).forward(img1, img2).mean() per frame pair.  The five convolutions run on ew_gemm_f16 (dense mode, bias vector) over
-// the patch rows ew_im2col_f16 writes; conv outputs are stored PRE-ReLU and every reader below applies max(x, 0) itself (the GEMM
-// has no ReLU epilogue; ReLU commutes with max-pooling).
+// the patch rows ew_im2col_frames_f16 (first layer) and ew_im2col3d_f16 with kt = 1 (convnet.hip) write, the max pools on
+// ew_maxpool3d_relu_f16 (convnet.hip); conv outputs are stored PRE-ReLU and the head applies max(x, 0) itself.
 // Compiled with -ffp-contract=off: the first layer's k / 255 -> 2x - 1 -> (x - shift) / scale are the reference's separate float32
 // roundings.
-#include "common.h"
+#include "convnet.h"
 #include <math.h>
 
 namespace {
-
-constexpr int NT = 256;
 
 struct FirstAffine { float shift[3], scale[3]; };
 
 __device__ __forceinline__ float first_value(float x01, int c, const FirstAffine& fa) {
     const float x = x01 * 2.0f - 1.0f;                     // calculate_lpips.py: frames in [0,1] -> [-1,1]
     return (x - fa.shift[c]) / fa.scale[c];                // lpips ScalingLayer
-}
-
-__device__ __forceinline__ uint4 relu8(uint4 raw) {
-    f16x8 v = *reinterpret_cast<f16x8*>(&raw);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = v[e] > (f16)0 ? v[e] : (f16)0;
-    return *reinterpret_cast<uint4*>(&v);
-}
-
-// fp16 NHWC source, C % 8 == 0: one thread per 8 output columns (one 16-byte load and store; a vector never straddles a tap)
-template <bool RELU>
-__global__ __launch_bounds__(NT) void im2col_f16_kernel(const f16* __restrict__ src, f16* __restrict__ out, long long total_vec,
-                                                        int h_in, int w_in, int C, int k, int stride, int pad, int h_out, int w_out,
-                                                        int ldk8, int kkC) {
-    for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < total_vec; i += (long long)gridDim.x * NT) {
-        const int col8 = (int)(i % ldk8);
-        const long long row = i / ldk8;
-        const int kk = col8 * 8;
-        uint4 v = make_uint4(0u, 0u, 0u, 0u);
-        if (kk < kkC) {
-            const int tap = kk / C, c = kk - tap * C;
-            const int ky = tap / k, kx = tap - ky * k;
-            const int ox = (int)(row % w_out);
-            const long long t = row / w_out;
-            const int oy = (int)(t % h_out);
-            const long long img = t / h_out;
-            const int iy = oy * stride + ky - pad, ix = ox * stride + kx - pad;
-            if (iy >= 0 && iy < h_in && ix >= 0 && ix < w_in) {
-                v = *reinterpret_cast<const uint4*>(src + ((img * h_in + iy) * w_in + ix) * C + c);
-                if (RELU) v = relu8(v);
-            }
-        }
-        *reinterpret_cast<uint4*>(out + i * 8) = v;
-    }
 }
 
 // first layer: uint8 [n,h,w,3] (KIND 1) or fp32 [n,3,h,w] (KIND 2) frames in [0,1]; column = (ky*k + kx)*3 + c, where network
@@ -92,32 +56,6 @@ __global__ __launch_bounds__(NT) void im2col_first_kernel(const void* __restrict
             v[e] = r;
         }
         *reinterpret_cast<f16x8*>(out + i * 8) = v;
-    }
-}
-
-// max over the 3x3 window at stride 2 (no padding, floor output size) of max(x, 0); 8 channels per thread
-__global__ __launch_bounds__(NT) void maxpool3s2_relu_kernel(const f16* __restrict__ src, f16* __restrict__ out, long long total_vec,
-                                                             int h_in, int w_in, int C8, int h_out, int w_out) {
-    for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < total_vec; i += (long long)gridDim.x * NT) {
-        const int c8 = (int)(i % C8);
-        long long t = i / C8;
-        const int ox = (int)(t % w_out);
-        t /= w_out;
-        const int oy = (int)(t % h_out);
-        const long long img = t / h_out;
-        f16x8 m;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) m[e] = (f16)0;
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < 3; ++dx) {
-                const uint4 raw = *reinterpret_cast<const uint4*>(src + (((img * h_in + 2 * oy + dy) * w_in + 2 * ox + dx) * C8 + c8) * 8);
-                const f16x8 v = *reinterpret_cast<const f16x8*>(&raw);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) m[e] = v[e] > m[e] ? v[e] : m[e];
-            }
-        *reinterpret_cast<f16x8*>(out + i * 8) = m;
     }
 }
 
@@ -217,46 +155,30 @@ __global__ __launch_bounds__(HEAD_MAX_BLOCKS) void lpips_head_reduce_kernel(cons
     if (t == 0) acc[f] += s_red[0] / n_out;
 }
 
-inline int grid_for(long long total_vec) {
-    long long b = (total_vec + NT - 1) / NT;
-    return (int)(b < 8192 ? b : 8192);
-}
-
 }  // namespace
 
-extern "C" ew_status ew_im2col_f16(const void* src, int src_kind, void* out, int n_img, int h_in, int w_in, int C, int k, int stride,
-                                   int pad, int h_out, int w_out, int ldk, int relu, int swap_rb, const float* first_affine, void* stream) {
-    EW_REQUIRE(src && out, "ew_im2col_f16: NULL pointer");
-    EW_REQUIRE(src_kind >= 0 && src_kind <= 2, "ew_im2col_f16: src_kind %d (0: fp16 NHWC, 1: uint8 NHWC frames, 2: fp32 NCHW frames)", src_kind);
-    EW_REQUIRE(n_img > 0 && h_in > 0 && w_in > 0 && C > 0 && k > 0 && stride > 0 && pad >= 0 && pad < k,
-               "ew_im2col_f16: bad geometry (n %d, %d x %d x %d, k %d, stride %d, pad %d)", n_img, h_in, w_in, C, k, stride, pad);
+extern "C" ew_status ew_im2col_frames_f16(const void* src, int src_kind, void* out, int n_img, int h_in, int w_in, int k, int stride, int pad,
+                                          int h_out, int w_out, int ldk, int swap_rb, const float* first_affine, void* stream) {
+    EW_REQUIRE(src && out, "ew_im2col_frames_f16: NULL pointer");
+    EW_REQUIRE(src_kind == 1 || src_kind == 2, "ew_im2col_frames_f16: src_kind %d (1: uint8 NHWC frames, 2: fp32 NCHW frames)", src_kind);
+    EW_REQUIRE(n_img > 0 && h_in > 0 && w_in > 0 && k > 0 && stride > 0 && pad >= 0 && pad < k,
+               "ew_im2col_frames_f16: bad geometry (n %d, %d x %d x 3, k %d, stride %d, pad %d)", n_img, h_in, w_in, k, stride, pad);
     EW_REQUIRE(h_in + 2 * pad >= k && w_in + 2 * pad >= k && h_out == (h_in + 2 * pad - k) / stride + 1 && w_out == (w_in + 2 * pad - k) / stride + 1,
-               "ew_im2col_f16: output %d x %d is not floor((%d x %d + 2*%d - %d) / %d) + 1", h_out, w_out, h_in, w_in, pad, k, stride);
-    EW_REQUIRE((long long)k * k * C <= ldk && ldk % 8 == 0, "ew_im2col_f16: ldk = %d must be a multiple of 8 and >= k*k*C = %lld", ldk,
-               (long long)k * k * C);
-    EW_REQUIRE((uintptr_t)out % 16 == 0, "ew_im2col_f16: out must be 16-byte aligned");
-    EW_REQUIRE((long long)h_in * w_in * C < (1LL << 31) && (long long)h_out * w_out < (1LL << 31), "ew_im2col_f16: image too large");
-    const long long total_vec = (long long)n_img * h_out * w_out * (ldk / 8);
-    hipStream_t st = (hipStream_t)stream;
-    if (src_kind == 0) {
-        EW_REQUIRE(C % 8 == 0 && (uintptr_t)src % 16 == 0, "ew_im2col_f16: fp16 source needs C %% 8 == 0 (got %d) and a 16-byte aligned pointer", C);
-        EW_REQUIRE(!swap_rb && !first_affine, "ew_im2col_f16: swap_rb / first_affine belong to the frame sources (src_kind 1, 2)");
-        if (relu)
-            hipLaunchKernelGGL(im2col_f16_kernel<true>, dim3(grid_for(total_vec)), dim3(NT), 0, st, (const f16*)src, (f16*)out, total_vec, h_in,
-                               w_in, C, k, stride, pad, h_out, w_out, ldk / 8, k * k * C);
-        else
-            hipLaunchKernelGGL(im2col_f16_kernel<false>, dim3(grid_for(total_vec)), dim3(NT), 0, st, (const f16*)src, (f16*)out, total_vec, h_in,
-                               w_in, C, k, stride, pad, h_out, w_out, ldk / 8, k * k * C);
-        return ew_check_launch("im2col_f16_kernel");
-    }
-    EW_REQUIRE(C == 3 && first_affine && !relu, "ew_im2col_f16: frame sources take C = 3, the six scaling constants and no ReLU");
-    EW_REQUIRE(src_kind == 1 || (uintptr_t)src % 4 == 0, "ew_im2col_f16: fp32 source must be 4-byte aligned");
+               "ew_im2col_frames_f16: output %d x %d is not floor((%d x %d + 2*%d - %d) / %d) + 1", h_out, w_out, h_in, w_in, pad, k, stride);
+    EW_REQUIRE((long long)k * k * 3 <= ldk && ldk % 8 == 0, "ew_im2col_frames_f16: ldk = %d must be a multiple of 8 and >= k*k*C = %lld", ldk,
+               (long long)k * k * 3);
+    EW_REQUIRE((uintptr_t)out % 16 == 0, "ew_im2col_frames_f16: out must be 16-byte aligned");
+    EW_REQUIRE((long long)h_in * w_in * 3 < (1LL << 31) && (long long)h_out * w_out < (1LL << 31), "ew_im2col_frames_f16: image too large");
+    EW_REQUIRE(first_affine, "ew_im2col_frames_f16: frame sources take the six scaling constants");
+    EW_REQUIRE(src_kind == 1 || (uintptr_t)src % 4 == 0, "ew_im2col_frames_f16: fp32 source must be 4-byte aligned");
     FirstAffine fa;
     for (int c = 0; c < 3; ++c) {
         fa.shift[c] = first_affine[c];
         fa.scale[c] = first_affine[3 + c];
-        EW_REQUIRE(fa.scale[c] != 0.0f, "ew_im2col_f16: scale[%d] is zero", c);
+        EW_REQUIRE(fa.scale[c] != 0.0f, "ew_im2col_frames_f16: scale[%d] is zero", c);
     }
+    const long long total_vec = (long long)n_img * h_out * w_out * (ldk / 8);
+    hipStream_t st = (hipStream_t)stream;
     if (src_kind == 1)
         hipLaunchKernelGGL(im2col_first_kernel<1>, dim3(grid_for(total_vec)), dim3(NT), 0, st, src, (f16*)out, total_vec, h_in, w_in, k, stride,
                            pad, h_out, w_out, ldk / 8, k * k * 3, swap_rb ? 1 : 0, fa);
@@ -264,20 +186,6 @@ extern "C" ew_status ew_im2col_f16(const void* src, int src_kind, void* out, int
         hipLaunchKernelGGL(im2col_first_kernel<2>, dim3(grid_for(total_vec)), dim3(NT), 0, st, src, (f16*)out, total_vec, h_in, w_in, k, stride,
                            pad, h_out, w_out, ldk / 8, k * k * 3, swap_rb ? 1 : 0, fa);
     return ew_check_launch("im2col_first_kernel");
-}
-
-extern "C" ew_status ew_maxpool3s2_relu_f16(const void* src, void* out, int n_img, int h_in, int w_in, int C, int h_out, int w_out,
-                                            void* stream) {
-    EW_REQUIRE(src && out, "ew_maxpool3s2_relu_f16: NULL pointer");
-    EW_REQUIRE(n_img > 0 && h_in >= 3 && w_in >= 3 && C > 0 && C % 8 == 0, "ew_maxpool3s2_relu_f16: needs n > 0, H, W >= 3, C %% 8 == 0 (n %d, %d x %d x %d)",
-               n_img, h_in, w_in, C);
-    EW_REQUIRE(h_out == (h_in - 3) / 2 + 1 && w_out == (w_in - 3) / 2 + 1, "ew_maxpool3s2_relu_f16: output %d x %d is not floor((%d x %d - 3) / 2) + 1",
-               h_out, w_out, h_in, w_in);
-    EW_REQUIRE((uintptr_t)src % 16 == 0 && (uintptr_t)out % 16 == 0, "ew_maxpool3s2_relu_f16: pointers must be 16-byte aligned");
-    const long long total_vec = (long long)n_img * h_out * w_out * (C / 8);
-    hipLaunchKernelGGL(maxpool3s2_relu_kernel, dim3(grid_for(total_vec)), dim3(NT), 0, (hipStream_t)stream, (const f16*)src, (f16*)out, total_vec,
-                       h_in, w_in, C / 8, h_out, w_out);
-    return ew_check_launch("maxpool3s2_relu_kernel");
 }
 
 extern "C" size_t ew_lpips_head_workspace_bytes(int F, int h, int w, int C) {

@@ -4,9 +4,9 @@ frechet_distance), over the network evoworld/metrics/fvd/videogpt/pytorch_i3d.py
 inflated to 3-D, whose 400 Kinetics logits are the features.
 
 ops.video_preprocess resizes, crops and maps a clip to [-1,1]; the 57 BatchNorm-folded convolutions run on ops.gemm (dense mode, bias
-vector, writing straight into their module's concat) over the patch rows of ops.im2col3d; ops.maxpool3d_relu and ops.i3d_head do the rest
-(csrc/i3d.hip).  Conv outputs stay pre-ReLU in memory: every reader applies max(x, 0) itself.  One clip goes through the network per call, so
-its logits do not depend on what else is evaluated.  Patch rows are written in slabs of output frames of at most WORKSPACE_BYTES.
+vector, writing straight into their module's concat) over the patch rows of ops.im2col3d; ops.maxpool3d_relu (csrc/convnet.hip) and
+ops.i3d_head (csrc/i3d.hip) do the rest; the loader, packer and constructors are _convnet's.  Conv outputs stay pre-ReLU in memory: every
+reader applies max(x, 0) itself.  One clip goes through the network per call, so its logits do not depend on what else is evaluated.  Patch rows are written in slabs of output frames of at most WORKSPACE_BYTES.
 The Frechet distance is the reference's float64 numpy / scipy arithmetic on the host.  This project ships no weights.
 """
 import math
@@ -15,10 +15,10 @@ import zipfile
 import numpy as np
 import torch
 
-from .lpips import load_state_files as _load_state_files
+from ._convnet import K_ALIGN, ConvNet, fold_batchnorm, pack_conv, random_conv_bn, validate  # noqa: F401 (K_ALIGN: this module's name too)
+from ._convnet import load_state_files as _load_state_files
 
 SIDE = 224                                             # preprocess_single's resolution
-K_ALIGN = 64                                           # ew_gemm_f16 takes K in multiples of 64
 WORKSPACE_BYTES = 256 << 20                            # cap on the patch rows alive at once (the stem's at T = 25 would be 0.9 GB)
 MIN_FRAMES = 9                                         # fewer frames leave Mixed_5c a single frame: the (2,7,7) average pool has no window
 BN_EPS = 1e-5
@@ -84,18 +84,10 @@ def _spec():
 
 
 def canonical_state_dict(sd):
-    """An InceptionI3d state dict -> {key: fp32 CPU tensor} over exactly the keys the network has, validated.  A leading `module.` is
-    stripped, num_batches_tracked and anything else is ignored.  KeyError lists the first missing keys; ValueError names a key of the
-    wrong shape."""
-    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
-    spec = _spec()
-    missing = [k for k in spec if k not in sd]
-    if missing:
-        raise KeyError(f"I3D state dict is missing {len(missing)} keys, e.g. {missing[:3]}; expected {ACCEPTED}")
-    for k, shape in spec.items():
-        if tuple(sd[k].shape) != shape:
-            raise ValueError(f"{k}: expected shape {shape}, got {tuple(sd[k].shape)}")
-    return {k: sd[k].detach().to("cpu", torch.float32) for k in spec}
+    """An InceptionI3d state dict -> {key: fp32 CPU tensor} over exactly the keys the network has, validated (_convnet.validate).  A leading
+    `module.` is stripped, num_batches_tracked and anything else is ignored.  KeyError lists the first missing keys; ValueError names a
+    key of the wrong shape."""
+    return validate(sd, _spec(), "I3D", ACCEPTED)
 
 
 def pack_state_dict(sd):
@@ -104,17 +96,10 @@ def pack_state_dict(sd):
     writes its columns (the stem's 3 input channels padded to 8), `{name}.b` fp16 [C_out]; logits.w fp32 [400,1024], logits.b fp32 [400]."""
     c = canonical_state_dict(sd)
     packed = {}
-    for name, ci, co, k in units():
-        s = c[f"{name}.bn.weight"].double() / (c[f"{name}.bn.running_var"].double() + BN_EPS).sqrt()
-        w = c[f"{name}.conv3d.weight"].double() * s.view(co, 1, 1, 1, 1)
-        cp = -(-ci // 8) * 8
-        K = k ** 3 * cp
-        rows = torch.zeros(co, k, k, k, cp, dtype=torch.float64)
-        rows[..., :ci] = w.permute(0, 2, 3, 4, 1)
-        wk = torch.zeros(co, -(-K // K_ALIGN) * K_ALIGN, dtype=torch.float16)
-        wk[:, :K] = rows.reshape(co, K).half()
-        packed[f"{name}.w"] = wk
-        packed[f"{name}.b"] = (c[f"{name}.bn.bias"].double() - c[f"{name}.bn.running_mean"].double() * s).half().contiguous()
+    for name, ci, _, _ in units():
+        w, b = fold_batchnorm(c, name, "conv3d", BN_EPS)
+        packed[f"{name}.w"] = pack_conv(w, -(-ci // 8) * 8)
+        packed[f"{name}.b"] = b.half().contiguous()
     packed["logits.w"] = c["logits.conv3d.weight"].reshape(N_CLASSES, 1024).contiguous()
     packed["logits.b"] = c["logits.conv3d.bias"].contiguous()
     return packed
@@ -132,7 +117,7 @@ def is_torchscript_archive(path):
 
 
 def load_state_files(paths):
-    """One or more weight files merged into one state dict (lpips.load_state_files); a TorchScript archive is refused."""
+    """One or more weight files merged into one state dict (_convnet.load_state_files); a TorchScript archive is refused."""
     if isinstance(paths, (str, bytes)) or hasattr(paths, "__fspath__"):
         paths = [paths]
     for p in paths:
@@ -143,42 +128,26 @@ def load_state_files(paths):
 
 
 def random_state_dict(seed=0):
-    """A seeded InceptionI3d-layout state dict (timing and tests; the values mean nothing): conv weights N(0, 2 / fan-in), gamma uniform in
-    [0.8, 1.2], beta and running mean N(0, 0.1^2), running variance uniform in [0.7, 1.3], logits bias N(0, 0.1^2).  Activations stay O(1)."""
+    """A seeded InceptionI3d-layout state dict (timing and tests; the values mean nothing): every unit as _convnet.random_conv_bn draws it,
+    logits weight N(0, 2 / 1024), logits bias N(0, 0.1^2).  Activations stay O(1)."""
     g = torch.Generator().manual_seed(seed)
     sd = {}
     for name, ci, co, k in units():
-        sd[f"{name}.conv3d.weight"] = torch.randn(co, ci, k, k, k, generator=g) * (2.0 / (ci * k ** 3)) ** 0.5
-        sd[f"{name}.bn.weight"] = 0.8 + 0.4 * torch.rand(co, generator=g)
-        sd[f"{name}.bn.bias"] = 0.1 * torch.randn(co, generator=g)
-        sd[f"{name}.bn.running_mean"] = 0.1 * torch.randn(co, generator=g)
-        sd[f"{name}.bn.running_var"] = 0.7 + 0.6 * torch.rand(co, generator=g)
+        random_conv_bn(g, sd, name, "conv3d", (co, ci, k, k, k))
     sd["logits.conv3d.weight"] = torch.randn(N_CLASSES, 1024, 1, 1, 1, generator=g) * (2.0 / 1024) ** 0.5
     sd["logits.conv3d.bias"] = 0.1 * torch.randn(N_CLASSES, generator=g)
     return sd
 
 
-class I3D:
+class I3D(ConvNet):
     """InceptionI3d(400) in eval mode behind styleganv's preprocess_single, one clip per call, on the device.
     workspace_bytes caps the patch rows alive at once; every slab of output frames is one GEMM call, so the cap decides the GEMM shapes and
     is part of the result's definition: logits are bit-for-bit reproducible for a fixed cap, and equal up to summation order across caps."""
+    pack_state_dict, load_state_files, random_state_dict = map(staticmethod, (pack_state_dict, load_state_files, random_state_dict))
 
     def __init__(self, packed, device, workspace_bytes=WORKSPACE_BYTES):
-        self.device = torch.device(device)
+        super().__init__(packed, device)
         self.workspace_bytes = int(workspace_bytes)
-        self.p = {k: v.to(self.device) for k, v in packed.items()}
-
-    @classmethod
-    def from_state_dict(cls, sd, device="cuda", **kw):
-        return cls(pack_state_dict(sd), device, **kw)
-
-    @classmethod
-    def from_files(cls, paths, device="cuda", **kw):
-        return cls.from_state_dict(load_state_files(paths), device, **kw)
-
-    @classmethod
-    def from_random(cls, seed=0, device="cuda", **kw):
-        return cls.from_state_dict(random_state_dict(seed), device, **kw)
 
     # ---- layers
     def _conv(self, x, targets, k, s, relu=True):
@@ -195,11 +164,7 @@ class I3D:
             first = o0 * s - pt                                                # input frame of the slab's first tap (negative: padding)
             lo, hi = max(0, first), min(T, (o1 - 1) * s - pt + k)
             rows = ops.im2col3d(x[lo:hi], (k, k, k), (s, s, s), (lo - first, ph, pw), (o1 - o0, Ho, Wo), ldk, relu)
-            for name, out, c_off in targets:
-                w = self.p[f"{name}.w"]
-                ld = out.shape[-1]
-                ops.gemm(rows, w, out.view(-1, ld)[o0 * per_frame:, c_off:], M=(o1 - o0) * per_frame, N=w.shape[0], c1=ldk, lda=ldk,
-                         bias=self.p[f"{name}.b"], ld_out=ld)
+            self.conv_into(rows.view(1, -1, ldk), [(self.p[f"{name}.w"], self.p[f"{name}.b"], out[o0:o1], c_off) for name, out, c_off in targets])
         return To, Ho, Wo
 
     def _unit(self, x, name, co, k, s, relu=True):
@@ -231,12 +196,8 @@ class I3D:
         """clip uint8 [T,H,W,3] or fp32 [T,3,H,W] in [0,1] on the device (channels R, G, B) -> fp16 [T,224,224,8]: preprocess_single.
         channel_order 'bgr' hands the network B, G, R planes, as the reference's cv2.imread frames reach it."""
         from . import ops
-        if channel_order not in ("rgb", "bgr"):
-            raise ValueError(f"channel_order {channel_order!r}: expected 'rgb' or 'bgr'")
-        if clip.ndim != 4 or clip.dtype not in (torch.uint8, torch.float32):
-            raise ValueError(f"clip: expected uint8 [T,H,W,3] or fp32 [T,3,H,W], got {clip.dtype} {tuple(clip.shape)}")
-        H, W = (clip.shape[1], clip.shape[2]) if clip.dtype == torch.uint8 else (clip.shape[2], clip.shape[3])
-        return ops.video_preprocess(clip, *preprocess_geometry(H, W), swap_rb=channel_order == "bgr")
+        swap = self.check_channel_order(channel_order)
+        return ops.video_preprocess(clip, *preprocess_geometry(*self.frames_hw(clip, "clip", "T")), swap_rb=swap)
 
     def forward(self, x, n_frames=None, endpoints=None):
         """x = preprocess(...) -> the 400 logits, fp32, of its first n_frames frames (all by default).  `endpoints`: a dict that receives

@@ -5,8 +5,8 @@ the ImageNet mean and std.  Despite the metric's name no VAE is involved.
 
 ops.frames_resize_aa_norm resizes and normalises; the 149 BatchNorm-folded convolutions run on ops.gemm (dense mode, bias vector, writing
 straight into their module's concat) over the patch rows of ops.im2col3d with kt = 1; ops.maxpool3d_relu, ops.avgpool3x3_relu and
-ops.global_avgpool_relu do the rest (csrc/i3d.hip, csrc/inception.hip).  Conv outputs stay pre-ReLU in memory: every reader applies max(x, 0)
-itself.  Every frame goes through the GEMMs on its own (M = one frame's pixels), so a frame's features depend on that frame alone:
+ops.global_avgpool_relu do the rest (csrc/convnet.hip, csrc/inception.hip); the loader, packer and constructors are _convnet's.  Conv
+outputs stay pre-ReLU in memory: every reader applies max(x, 0) itself.  Every frame goes through the GEMMs on its own (M = one frame's pixels), so a frame's features depend on that frame alone:
 identical frames give exactly 0, and the loop-closure value reuses the last frame's features of the same pass.  The aggregation is the
 reference's numpy arithmetic on the host, in float64.  This project ships no weights.
 """
@@ -15,11 +15,11 @@ import functools
 import numpy as np
 import torch
 
-from .lpips import load_state_files
+from ._convnet import K_ALIGN, ConvNet, load_state_files, pack_conv, random_conv_bn, validate  # noqa: F401 (K_ALIGN, load_state_files: this module's names too)
+from ._convnet import fold_batchnorm as _fold_batchnorm
 
 SIDE = 299                                             # Resize((299, 299))
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
-K_ALIGN = 64                                           # ew_gemm_f16 takes K in multiples of 64
 BN_EPS = 1e-3                                          # timm's inception_v4 BatchNorm
 N_FEATURES = 1536
 ACCEPTED = ("a state dict in timm inception_v4's key layout (features.0.conv.weight, features.0.bn.{weight,bias,running_mean,running_var}, "
@@ -130,25 +130,15 @@ def _spec():
 
 
 def canonical_state_dict(sd):
-    """A timm inception_v4 state dict -> {key: fp32 CPU tensor} over exactly the keys the feature network has, validated.  A leading
-    `module.` is stripped; num_batches_tracked, last_linear.* and anything else is ignored.  KeyError lists the first missing keys;
-    ValueError names a key of the wrong shape."""
-    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
-    spec = _spec()
-    missing = [k for k in spec if k not in sd]
-    if missing:
-        raise KeyError(f"Inception-v4 state dict is missing {len(missing)} keys, e.g. {missing[:3]}; expected {ACCEPTED}")
-    for k, shape in spec.items():
-        if tuple(sd[k].shape) != shape:
-            raise ValueError(f"{k}: expected shape {shape}, got {tuple(sd[k].shape)}")
-    return {k: sd[k].detach().to("cpu", torch.float32) for k in spec}
+    """A timm inception_v4 state dict -> {key: fp32 CPU tensor} over exactly the keys the feature network has, validated
+    (_convnet.validate).  A leading `module.` is stripped; num_batches_tracked, last_linear.* and anything else is ignored.  KeyError lists
+    the first missing keys; ValueError names a key of the wrong shape."""
+    return validate(sd, _spec(), "Inception-v4", ACCEPTED)
 
 
 def fold_batchnorm(c, name):
-    """(weight [C_out, C_in, kh, kw], bias [C_out]) in fp64 of unit `name` with its eval-mode BatchNorm folded in: s = gamma / sqrt(var +
-    1e-3); w * s; beta - mean * s"""
-    s = c[f"{name}.bn.weight"].double() / (c[f"{name}.bn.running_var"].double() + BN_EPS).sqrt()
-    return c[f"{name}.conv.weight"].double() * s.view(-1, 1, 1, 1), c[f"{name}.bn.bias"].double() - c[f"{name}.bn.running_mean"].double() * s
+    """(weight [C_out, C_in, kh, kw], bias [C_out]) in fp64 of unit `name` with its eval-mode BatchNorm (eps 1e-3) folded in"""
+    return _fold_batchnorm(c, name, "conv", BN_EPS)
 
 
 def pack_state_dict(sd):
@@ -157,31 +147,20 @@ def pack_state_dict(sd):
     `{name}.b` fp16 [C_out]."""
     c = canonical_state_dict(sd)
     packed = {}
-    for name, ci, co, (kh, kw), _, _ in units():
+    for name, ci, *_rest in units():
         w, b = fold_batchnorm(c, name)
-        cp = -(-ci // 8) * 8
-        K = kh * kw * cp
-        rows = torch.zeros(co, kh, kw, cp, dtype=torch.float64)
-        rows[..., :ci] = w.permute(0, 2, 3, 1)
-        wk = torch.zeros(co, -(-K // K_ALIGN) * K_ALIGN, dtype=torch.float16)
-        wk[:, :K] = rows.reshape(co, K).half()
-        packed[f"{name}.w"] = wk
+        packed[f"{name}.w"] = pack_conv(w, -(-ci // 8) * 8)
         packed[f"{name}.b"] = b.half().contiguous()
     return packed
 
 
 def random_state_dict(seed=0):
-    """A seeded inception_v4-layout state dict (timing and tests; the values mean nothing): conv weights N(0, 2 / fan-in), gamma uniform in
-    [0.8, 1.2], beta and running mean N(0, 0.1^2), running variance uniform in [0.7, 1.3]; num_batches_tracked as timm's file has it (the
-    loader ignores it).  Activations stay O(1)."""
+    """A seeded inception_v4-layout state dict (timing and tests; the values mean nothing): every unit as _convnet.random_conv_bn draws it,
+    plus num_batches_tracked as timm's file has it (the loader ignores it).  Activations stay O(1)."""
     g = torch.Generator().manual_seed(seed)
     sd = {}
     for name, ci, co, (kh, kw), _, _ in units():
-        sd[f"{name}.conv.weight"] = torch.randn(co, ci, kh, kw, generator=g) * (2.0 / (ci * kh * kw)) ** 0.5
-        sd[f"{name}.bn.weight"] = 0.8 + 0.4 * torch.rand(co, generator=g)
-        sd[f"{name}.bn.bias"] = 0.1 * torch.randn(co, generator=g)
-        sd[f"{name}.bn.running_mean"] = 0.1 * torch.randn(co, generator=g)
-        sd[f"{name}.bn.running_var"] = 0.7 + 0.6 * torch.rand(co, generator=g)
+        random_conv_bn(g, sd, name, "conv", (co, ci, kh, kw))
         sd[f"{name}.bn.num_batches_tracked"] = torch.tensor(0)
     return sd
 
@@ -236,27 +215,15 @@ def latent_mse_result(f1, f2, video_setting):
             "video_setting_name": "time, channel, heigth, width"}
 
 
-class InceptionV4:
+class InceptionV4(ConvNet):
     """timm's inception_v4 (num_classes=0, eval mode) behind Resize((299, 299)) + Normalize, on the device: frames -> 1536 features each.
     `chunk` frames share the gathers and pools of one pass; the GEMMs run frame by frame."""
+    pack_state_dict, load_state_files, random_state_dict = map(staticmethod, (pack_state_dict, load_state_files, random_state_dict))
 
     def __init__(self, packed, device, chunk=5):
-        self.device = torch.device(device)
+        super().__init__(packed, device)
         self.chunk = int(chunk)
-        self.p = {k: v.to(self.device) for k, v in packed.items()}
         self._tables = {}
-
-    @classmethod
-    def from_state_dict(cls, sd, device="cuda", **kw):
-        return cls(pack_state_dict(sd), device, **kw)
-
-    @classmethod
-    def from_files(cls, paths, device="cuda", **kw):
-        return cls.from_state_dict(load_state_files(paths), device, **kw)
-
-    @classmethod
-    def from_random(cls, seed=0, device="cuda", **kw):
-        return cls.from_state_dict(random_state_dict(seed), device, **kw)
 
     # ---- layers
     def _table(self, n_in, n_out):
@@ -294,18 +261,17 @@ class InceptionV4:
             group = [(k2, o2) for k2, s2, o2 in steps if s2 == src and o2[0] == "conv" and o2[3:] == op[3:] and k2 not in done]
             ldk = self.p[f"{_name(i, key)}.w"].shape[1]
             rows = ops.im2col3d(vals[src], (1, kh, kw), (1, s, s), (0, ph, pw), (n, h, w), ldk, relu).view(n, h * w, ldk)
+            targets = []
             for k2, o2 in group:
-                name, co = _name(i, k2), o2[2]
+                name = _name(i, k2)
                 if k2 in offset:
                     out, c_off = y, offset[k2]
                 else:
-                    out, c_off = torch.empty(n, h, w, co, dtype=torch.float16, device=x.device), 0
+                    out, c_off = torch.empty(n, h, w, o2[2], dtype=torch.float16, device=x.device), 0
                     vals[k2] = out
-                ld = out.shape[-1]
-                for j in range(n):                     # one frame per GEMM: its values do not depend on the rest of the batch
-                    ops.gemm(rows[j], self.p[f"{name}.w"], out.view(n, h * w, ld)[j, :, c_off:], M=h * w, N=co, c1=ldk, lda=ldk,
-                             bias=self.p[f"{name}.b"], ld_out=ld)
+                targets.append((self.p[f"{name}.w"], self.p[f"{name}.b"], out, c_off))
                 done.add(k2)
+            self.conv_into(rows, targets)              # one frame per GEMM: its values do not depend on the rest of the batch
         return y
 
     # ---- the network
@@ -314,12 +280,9 @@ class InceptionV4:
         transform.  channel_order 'bgr' hands the network B, G, R planes, as the reference's cv2.imread frames reach it; the ImageNet
         mean and std stay indexed by the network's channel."""
         from . import ops
-        if channel_order not in ("rgb", "bgr"):
-            raise ValueError(f"channel_order {channel_order!r}: expected 'rgb' or 'bgr'")
-        if frames.ndim != 4 or frames.dtype not in (torch.uint8, torch.float32):
-            raise ValueError(f"frames: expected uint8 [F,H,W,3] or fp32 [F,3,H,W], got {frames.dtype} {tuple(frames.shape)}")
-        H, W = (frames.shape[1], frames.shape[2]) if frames.dtype == torch.uint8 else (frames.shape[2], frames.shape[3])
-        return ops.frames_resize_aa_norm(frames, self._table(H, SIDE), self._table(W, SIDE), MEAN, STD, channel_order == "bgr")
+        swap = self.check_channel_order(channel_order)
+        H, W = self.frames_hw(frames)
+        return ops.frames_resize_aa_norm(frames, self._table(H, SIDE), self._table(W, SIDE), MEAN, STD, swap)
 
     def forward(self, x, endpoints=None):
         """x = preprocess(...) -> fp32 [F,1536].  `endpoints`: a dict that receives every features.{i} output, fp16 [F,h,w,C] (the

@@ -2,8 +2,9 @@
 evoworld/metrics/other_metrics/calculate_lpips.py (run by calculate_all_metrics.py:195-221), i.e. per frame pair
 lpips.LPIPS(net='alex', spatial=True).forward(img1, img2).mean() on frames mapped from [0,1] to [-1,1].
 
-The five convolutions run on ops.gemm (dense mode, bias vector) over the patch rows of ops.im2col; ops.maxpool3s2_relu and
-ops.lpips_head do the rest (csrc/lpips.hip).  Conv outputs stay pre-ReLU in memory: every reader applies max(x, 0) itself.  The mean
+The five convolutions run on ops.gemm (dense mode, bias vector) over the patch rows of ops.im2col_frames (the first, csrc/lpips.hip) and
+ops.im2col3d with kt = 1; ops.maxpool3d_relu (csrc/convnet.hip) and ops.lpips_head (csrc/lpips.hip) do the rest; the loader, packer and
+constructors are _convnet's.  Conv outputs stay pre-ReLU in memory: every reader applies max(x, 0) itself.  The mean
 over the bilinearly upsampled distance map is a weighted sum over the tap's own pixels (upsample_mean_weights), so no full-size map
 exists.  This project ships no weights: they come from a lpips.LPIPS state dict, or from torchvision's AlexNet plus the lpips
 package's alex.pth.
@@ -11,12 +12,13 @@ package's alex.pth.
 import numpy as np
 import torch
 
+from ._convnet import K_ALIGN, ConvNet, load_state_files, pack_conv, validate  # noqa: F401 (K_ALIGN, load_state_files: this module's names too)
+
 # (torchvision features index, out channels, in channels, kernel, stride, padding); a tap follows each convolution's ReLU
 CONVS = ((0, 64, 3, 11, 4, 2), (3, 192, 64, 5, 1, 2), (6, 384, 192, 3, 1, 1), (8, 256, 384, 3, 1, 1), (10, 256, 256, 3, 1, 1))
 POOL_AFTER = (True, True, False, False, False)         # MaxPool2d(3, 2) between conv1 / conv2 and conv2 / conv3
 SHIFT = (-.030, -.088, -.188)                          # lpips ScalingLayer
 SCALE = (.458, .448, .450)
-K_ALIGN = 64                                           # ew_gemm_f16 takes K in multiples of 64
 MIN_SIZE = 31                                          # smallest H, W that leave every tap at least 1 x 1
 
 
@@ -56,59 +58,38 @@ def tap_sizes(H, W):
     return out
 
 
-def _spec():
-    spec = {}
-    for i, (_, co, ci, k, _, _) in enumerate(CONVS):
-        spec[f"conv{i}.weight"] = (co, ci, k, k)
-        spec[f"conv{i}.bias"] = (co,)
-        spec[f"lin{i}"] = (1, co, 1, 1)
-    return spec
-
-
 def canonical_state_dict(sd):
     """Either accepted key layout -> {conv{i}.weight, conv{i}.bias, lin{i} (i = 0..4), optional shift / scale}, validated.
     Layouts: a full lpips.LPIPS.state_dict() (net.slice{i+1}.{idx}.weight|bias, lin{i}.model.1.weight, optional scaling_layer.shift|scale;
     the duplicate lins.* entries are ignored), or torchvision AlexNet's features.{idx}.weight|bias merged with the lpips package's
     alex.pth (lin{i}.model.1.weight).  KeyError lists the first missing keys; ValueError names a key of the wrong shape."""
-    out, missing = {}, []
-    for i, (idx, *_rest) in enumerate(CONVS):
-        for part in ("weight", "bias"):
+    source, spec = {}, {}                                  # canonical name -> the key it is read from (the alternatives where none is there)
+    for i, (idx, co, ci, k, _, _) in enumerate(CONVS):
+        for part, shape in (("weight", (co, ci, k, k)), ("bias", (co,))):
             names = (f"net.slice{i + 1}.{idx}.{part}", f"features.{idx}.{part}")
-            found = [n for n in names if n in sd]
-            if found:
-                out[f"conv{i}.{part}"] = (found[0], sd[found[0]])
-            else:
-                missing.append(" | ".join(names))
-        n = f"lin{i}.model.1.weight"
-        if n in sd:
-            out[f"lin{i}"] = (n, sd[n])
-        else:
-            missing.append(n)
-    if missing:
-        raise KeyError(f"LPIPS state dict is missing {len(missing)} keys, e.g. {missing[:3]}")
-    for k, shape in _spec().items():
-        name, t = out[k]
-        if tuple(t.shape) != shape:
-            raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
+            source[f"conv{i}.{part}"] = next((n for n in names if n in sd), " | ".join(names))
+            spec[source[f"conv{i}.{part}"]] = shape
+        source[f"lin{i}"] = f"lin{i}.model.1.weight"
+        spec[source[f"lin{i}"]] = (1, co, 1, 1)
+    c = validate(sd, spec, "LPIPS")
+    out = {k: c[n] for k, n in source.items()}
     for k in ("shift", "scale"):
         n = f"scaling_layer.{k}"
         if n in sd:
             if sd[n].numel() != 3:
                 raise ValueError(f"{n}: expected shape (1, 3, 1, 1), got {tuple(sd[n].shape)}")
-            out[k] = (n, sd[n])
-    return {k: t.detach().to("cpu", torch.float32) for k, (_, t) in out.items()}
+            out[k] = sd[n].detach().to("cpu", torch.float32)
+    return out
 
 
 def pack_state_dict(sd):
     """State dict (either layout) -> the tensors the kernels read, on the CPU: w{i} fp16 [C_out, K padded to 64] with K ordered
-    (ky, kx, c_in) as ops.im2col writes its columns, b{i} fp16 [C_out], lin{i} fp32 [C_out], shift / scale (tuples of 3 floats)."""
+    (ky, kx, c_in) as ops.im2col_frames / ops.im2col3d write their columns (the first layer's 3 channels are not padded: K = 363 -> 384),
+    b{i} fp16 [C_out], lin{i} fp32 [C_out], shift / scale (tuples of 3 floats)."""
     c = canonical_state_dict(sd)
     packed = {}
-    for i, (_, co, ci, k, _, _) in enumerate(CONVS):
-        K = k * k * ci
-        w = torch.zeros(co, -(-K // K_ALIGN) * K_ALIGN, dtype=torch.float16)
-        w[:, :K] = c[f"conv{i}.weight"].permute(0, 2, 3, 1).reshape(co, K).half()
-        packed[f"w{i}"] = w
+    for i, (_, co, *_rest) in enumerate(CONVS):
+        packed[f"w{i}"] = pack_conv(c[f"conv{i}.weight"])
         packed[f"b{i}"] = c[f"conv{i}.bias"].half().contiguous()
         packed[f"lin{i}"] = c[f"lin{i}"].reshape(co).contiguous()
     packed["shift"] = tuple(float(v) for v in c["shift"].reshape(3)) if "shift" in c else SHIFT
@@ -116,48 +97,28 @@ def pack_state_dict(sd):
     return packed
 
 
-def load_state_files(paths):
-    """One or more weight files (.safetensors, or anything torch.load(..., weights_only=True) reads) merged into one state dict."""
-    if isinstance(paths, (str, bytes)) or hasattr(paths, "__fspath__"):
-        paths = [paths]
+def random_state_dict(seed=0):
+    """A seeded lpips.LPIPS-layout state dict with AlexNet's shapes: conv weights scaled by 1 / sqrt(fan-in) so activations stay
+    O(1), biases N(0, 0.1^2), lin weights uniform in [0, 1) (non-negative, as the trained ones are)."""
+    g = torch.Generator().manual_seed(seed)
     sd = {}
-    for p in paths:
-        if str(p).endswith(".safetensors"):
-            from safetensors.torch import load_file
-            part = load_file(str(p))
-        else:
-            part = torch.load(p, map_location="cpu", weights_only=True)
-            if isinstance(part, dict) and "state_dict" in part and isinstance(part["state_dict"], dict):
-                part = part["state_dict"]
-        sd.update(part)
+    for i, (idx, co, ci, k, _, _) in enumerate(CONVS):
+        sd[f"net.slice{i + 1}.{idx}.weight"] = torch.randn(co, ci, k, k, generator=g) / float(ci * k * k) ** 0.5
+        sd[f"net.slice{i + 1}.{idx}.bias"] = 0.1 * torch.randn(co, generator=g)
+        sd[f"lin{i}.model.1.weight"] = torch.rand(1, co, 1, 1, generator=g)
     return sd
 
 
-class LPIPSAlex:
+class LPIPSAlex(ConvNet):
     """lpips.LPIPS(net='alex', spatial=True) followed by the mean over the map, per frame pair, on the device."""
+    pack_state_dict, load_state_files, random_state_dict = map(staticmethod, (pack_state_dict, load_state_files, random_state_dict))
 
     def __init__(self, packed, device, chunk=4):
-        self.device = torch.device(device)
+        super().__init__(packed, device)
         self.chunk = int(chunk)                    # frame pairs whose activations are alive at once
-        self.shift, self.scale = packed["shift"], packed["scale"]
-        self.w = [packed[f"w{i}"].to(self.device) for i in range(5)]
-        self.b = [packed[f"b{i}"].to(self.device) for i in range(5)]
-        self.lin = [packed[f"lin{i}"].to(self.device) for i in range(5)]
+        self.shift, self.scale = self.p["shift"], self.p["scale"]
+        self.w, self.b, self.lin = ([self.p[f"{k}{i}"] for i in range(5)] for k in ("w", "b", "lin"))
         self._mean_w = {}
-
-    @classmethod
-    def from_state_dict(cls, sd, device="cuda", chunk=4):
-        return cls(pack_state_dict(sd), device, chunk)
-
-    @classmethod
-    def from_files(cls, paths, device="cuda", chunk=4):
-        return cls.from_state_dict(load_state_files(paths), device, chunk)
-
-    @classmethod
-    def from_random(cls, seed=0, device="cuda", chunk=4):
-        """AlexNet-shaped random weights (timing and tests; the values mean nothing): conv weights N(0, 1 / fan-in), small biases,
-        non-negative lin weights."""
-        return cls.from_state_dict(random_state_dict(seed), device, chunk)
 
     def _weights_for(self, h, w, H, W):
         key = (h, w, H, W)
@@ -170,18 +131,19 @@ class LPIPSAlex:
         """frames uint8 [n,H,W,3] or fp32 [n,3,H,W] in [0,1] -> the five pre-ReLU conv outputs, fp16 [n,h,w,C] each.  Every image goes
         through ew_gemm_f16 on its own, so its features do not depend on what else is in the batch."""
         from . import ops
-        if channel_order not in ("rgb", "bgr"):
-            raise ValueError(f"channel_order {channel_order!r}: expected 'rgb' or 'bgr'")
+        swap = self.check_channel_order(channel_order)
+        n, sizes = frames.shape[0], tap_sizes(*self.frames_hw(frames))
         taps, x = [], frames
         for i, (_, co, ci, k, s, p) in enumerate(CONVS):
-            first = (self.shift, self.scale, channel_order == "bgr") if i == 0 else None
-            rows, ho, wo = ops.im2col(x, k, s, p, self.w[i].shape[1], relu=i >= 3, first=first)
-            n, ldk = rows.shape[0] // (ho * wo), rows.shape[1]
+            (ho, wo), ldk = sizes[i], self.w[i].shape[1]
+            if i == 0:
+                rows = ops.im2col_frames(x, k, s, p, ldk, self.shift, self.scale, swap)[0]
+            else:
+                rows = ops.im2col3d(x, (1, k, k), (1, s, s), (0, p, p), (n, ho, wo), ldk, relu=i >= 3)
             y = torch.empty(n, ho, wo, co, dtype=torch.float16, device=rows.device)
-            for j in range(n):
-                ops.gemm(rows[j * ho * wo:(j + 1) * ho * wo], self.w[i], y[j], M=ho * wo, N=co, c1=ldk, lda=ldk, bias=self.b[i])
+            self.conv_into(rows.view(n, ho * wo, ldk), [(self.w[i], self.b[i], y, 0)])
             taps.append(y)
-            x = ops.maxpool3s2_relu(y) if POOL_AFTER[i] else y
+            x = ops.maxpool3d_relu(y, (1, 3, 3), (1, 2, 2), (0, 0, 0), (n, (ho - 3) // 2 + 1, (wo - 3) // 2 + 1)) if POOL_AFTER[i] else y
         return taps
 
     def __call__(self, a, b, channel_order="rgb", chunk=None, row_weights=None):
@@ -192,10 +154,7 @@ class LPIPSAlex:
         from . import ops
         if a.shape != b.shape or a.dtype != b.dtype or a.device != b.device:
             raise ValueError(f"a {tuple(a.shape)} {a.dtype} on {a.device} and b {tuple(b.shape)} {b.dtype} on {b.device} differ")
-        if a.ndim != 4 or a.dtype not in (torch.uint8, torch.float32):
-            raise ValueError(f"frames: expected uint8 [F,H,W,3] or fp32 [F,3,H,W], got {a.dtype} {tuple(a.shape)}")
-        F_ = a.shape[0]
-        H, W = (a.shape[1], a.shape[2]) if a.dtype == torch.uint8 else (a.shape[2], a.shape[3])
+        F_, (H, W) = a.shape[0], self.frames_hw(a)
         sizes = tap_sizes(H, W)
         n_out = H * W
         if row_weights is not None:
@@ -214,15 +173,3 @@ class LPIPSAlex:
                 ops.lpips_head(t[:n], t[n:], self.lin[i], wy, wx, n_out, acc[f0:f0 + n])
         ops.streamk_check()                        # results leave here: a timed-out stream-K hand-over in a convolution must not pass silently
         return acc
-
-
-def random_state_dict(seed=0):
-    """A seeded lpips.LPIPS-layout state dict with AlexNet's shapes: conv weights scaled by 1 / sqrt(fan-in) so activations stay
-    O(1), biases N(0, 0.1^2), lin weights uniform in [0, 1) (non-negative, as the trained ones are)."""
-    g = torch.Generator().manual_seed(seed)
-    sd = {}
-    for i, (idx, co, ci, k, _, _) in enumerate(CONVS):
-        sd[f"net.slice{i + 1}.{idx}.weight"] = torch.randn(co, ci, k, k, generator=g) / float(ci * k * k) ** 0.5
-        sd[f"net.slice{i + 1}.{idx}.bias"] = 0.1 * torch.randn(co, generator=g)
-        sd[f"lin{i}.model.1.weight"] = torch.rand(1, co, 1, 1, generator=g)
-    return sd

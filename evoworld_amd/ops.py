@@ -744,49 +744,33 @@ def conv_out_size(n, k, stride, pad):
     return (n + 2 * pad - k) // stride + 1
 
 
-def im2col(src, k, stride, pad, ldk, relu=False, first=None):
-    """k x k / stride / zero-pad patch rows for a convolution on ew_gemm_f16 (ew_im2col_f16): src fp16 NHWC [n,h,w,C] (C % 8 == 0;
-    relu: read max(x, 0)) -> fp16 [n*h_out*w_out, ldk], column (ky*k + kx)*C + c, zero beyond k*k*C.  first = (shift[3], scale[3],
-    swap_rb): src is a batch of frames in [0,1], uint8 [n,h,w,3] or fp32 [n,3,h,w], mapped 2v - 1 -> (x - shift) / scale on the way
-    (network channel c reads frame channel 2 - c when swap_rb).  Returns (rows, h_out, w_out)."""
-    affine, swap = None, 0
-    if first is None:
-        _req(src, torch.float16, "src")
-        if src.ndim != 4:
-            raise ValueError(f"src: expected fp16 [n,h,w,C], got {tuple(src.shape)}")
-        kind = 0
-        n, h, w, C = src.shape
+def _frames_src(t, name, dims="n,H,W"):
+    """A batch of frames in [0,1], uint8 [n,H,W,3] or fp32 [n,3,H,W], validated -> (src_kind of the frame entry points, n, H, W);
+    `dims` names the three sizes in the message."""
+    kind = 1 if t.dtype == torch.uint8 else 2
+    _req(t, torch.uint8 if kind == 1 else torch.float32, name)
+    if kind == 1:
+        n, H, W, C = t.shape if t.ndim == 4 else (0, 0, 0, 0)
     else:
-        shift, scale, swap = first
-        affine = (ctypes.c_float * 6)(*[float(v) for v in shift], *[float(v) for v in scale])
-        if src.dtype == torch.uint8:
-            _req(src, torch.uint8, "src")
-            kind = 1
-            n, h, w, C = src.shape if src.ndim == 4 else (0, 0, 0, 0)
-        else:
-            _req(src, torch.float32, "src")
-            kind = 2
-            n, C, h, w = src.shape if src.ndim == 4 else (0, 0, 0, 0)
-        if C != 3:
-            raise ValueError(f"src: expected uint8 [n,h,w,3] or fp32 [n,3,h,w] frames, got {tuple(src.shape)}")
+        n, C, H, W = t.shape if t.ndim == 4 else (0, 0, 0, 0)
+    if C != 3:
+        raise ValueError(f"{name}: expected uint8 [{dims},3] or fp32 [{dims.replace(',', ',3,', 1)}] frames, got {tuple(t.shape)}")
+    return kind, n, H, W
+
+
+def im2col_frames(frames, k, stride, pad, ldk, shift, scale, swap_rb=False):
+    """k x k / stride / zero-pad patch rows of a network's first convolution on ew_gemm_f16, straight from the frames
+    (ew_im2col_frames_f16): frames in [0,1], uint8 [n,h,w,3] or fp32 [n,3,h,w], mapped 2v - 1 -> (x - shift[c]) / scale[c] on the way
+    (network channel c reads frame channel 2 - c when swap_rb) -> fp16 [n*h_out*w_out, ldk], column (ky*k + kx)*3 + c, zero beyond
+    k*k*3.  Returns (rows, h_out, w_out)."""
+    kind, n, h, w = _frames_src(frames, "src", "n,h,w")
     ho, wo = conv_out_size(h, k, stride, pad), conv_out_size(w, k, stride, pad)
     if ho < 1 or wo < 1:
         raise ValueError(f"im2col: a {k}x{k} window (pad {pad}) does not fit {h}x{w}")
-    out = torch.empty(n * ho * wo, ldk, dtype=torch.float16, device=src.device)
-    _call("ew_im2col_f16", _ptr(src), kind, _ptr(out), n, h, w, C, k, stride, pad, ho, wo, ldk, int(bool(relu)), int(bool(swap)), affine)
+    out = torch.empty(n * ho * wo, ldk, dtype=torch.float16, device=frames.device)
+    affine = (ctypes.c_float * 6)(*[float(v) for v in shift], *[float(v) for v in scale])
+    _call("ew_im2col_frames_f16", _ptr(frames), kind, _ptr(out), n, h, w, k, stride, pad, ho, wo, ldk, int(bool(swap_rb)), affine)
     return out, ho, wo
-
-
-def maxpool3s2_relu(x):
-    """MaxPool2d(3, 2) of max(x, 0) (ew_maxpool3s2_relu_f16): fp16 NHWC [n,h,w,C], C % 8 == 0 -> [n, (h-3)//2+1, (w-3)//2+1, C]."""
-    _req(x, torch.float16, "x")
-    if x.ndim != 4 or x.shape[1] < 3 or x.shape[2] < 3:
-        raise ValueError(f"x: expected fp16 [n,h,w,C] with h, w >= 3, got {tuple(x.shape)}")
-    n, h, w, C = x.shape
-    ho, wo = (h - 3) // 2 + 1, (w - 3) // 2 + 1
-    out = torch.empty(n, ho, wo, C, dtype=torch.float16, device=x.device)
-    _call("ew_maxpool3s2_relu_f16", _ptr(x), _ptr(out), n, h, w, C, ho, wo)
-    return out
 
 
 def lpips_head(fa, fb, lin, wy, wx, n_out, acc):
@@ -809,16 +793,7 @@ def lpips_head(fa, fb, lin, wy, wx, n_out, acc):
 def video_preprocess(clip, h_resized, w_resized, y0, x0, swap_rb=False):
     """styleganv preprocess_single of one clip (ew_video_preprocess_f16): uint8 [T,H,W,3] or fp32 [T,3,H,W] in [0,1] -> fp16
     [T,224,224,8] in [-1,1], channels 3..7 zero: bilinear resize to h_resized x w_resized, 224 x 224 crop at (y0, x0), (x - 0.5) * 2."""
-    if clip.dtype == torch.uint8:
-        _req(clip, torch.uint8, "clip")
-        kind = 1
-        T, H, W, C = clip.shape if clip.ndim == 4 else (0, 0, 0, 0)
-    else:
-        _req(clip, torch.float32, "clip")
-        kind = 2
-        T, C, H, W = clip.shape if clip.ndim == 4 else (0, 0, 0, 0)
-    if C != 3:
-        raise ValueError(f"clip: expected uint8 [T,H,W,3] or fp32 [T,3,H,W] frames, got {tuple(clip.shape)}")
+    kind, T, H, W = _frames_src(clip, "clip", "T,H,W")
     out = torch.empty(T, 224, 224, 8, dtype=torch.float16, device=clip.device)
     _call("ew_video_preprocess_f16", _ptr(clip), kind, _ptr(out), T, H, W, h_resized, w_resized, y0, x0, int(bool(swap_rb)))
     return out
@@ -878,16 +853,7 @@ def frames_resize_aa_norm(frames, table_h, table_w, mean, std, swap_rb=False):
     [F,out_h,out_w,8], channels 3..7 zero: the antialiased bilinear resize of torchvision's Resize on a float tensor, then (x - mean[c]) /
     std[c].  table_h / table_w = (first int32 [n_out], count int32 [n_out], weights fp32 [n_out, taps]) device tensors, as
     latent_mse.resize_table(H, out_h) / (W, out_w) gives them."""
-    if frames.dtype == torch.uint8:
-        _req(frames, torch.uint8, "frames")
-        kind = 1
-        F_, H, W, C = frames.shape if frames.ndim == 4 else (0, 0, 0, 0)
-    else:
-        _req(frames, torch.float32, "frames")
-        kind = 2
-        F_, C, H, W = frames.shape if frames.ndim == 4 else (0, 0, 0, 0)
-    if C != 3:
-        raise ValueError(f"frames: expected uint8 [F,H,W,3] or fp32 [F,3,H,W] frames, got {tuple(frames.shape)}")
+    kind, F_, H, W = _frames_src(frames, "frames", "F,H,W")
     args = []
     for name, (first, count, weights) in (("table_h", table_h), ("table_w", table_w)):
         _req(first, torch.int32, f"{name}[0]"); _req(count, torch.int32, f"{name}[1]"); _req(weights, torch.float32, f"{name}[2]")

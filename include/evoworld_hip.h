@@ -27,7 +27,7 @@ typedef int ew_status;
 #define EW_ERR_UNSUPPORTED (-2)
 #define EW_ERR_HIP (-3)
 
-#define EW_ABI_VERSION 19
+#define EW_ABI_VERSION 20
 int ew_abi_version(void);
 const char* ew_last_error(void);
 
@@ -473,19 +473,40 @@ ew_status ew_gt_dump_map_u8(const uint8_t* src, uint8_t* dst, size_t n, void* st
  * cross 4-byte aligned; one launch for all V panoramas. */
 ew_status ew_equi2cube_u8(const uint8_t* pano, uint8_t* cross, int V, int H, int W, int interpolation, void* stream);
 
-/* LPIPS with the AlexNet backbone (ABI 14; evoworld/metrics/other_metrics/calculate_lpips.py, calculate_all_metrics.py:195-221:
- * lpips.LPIPS(net='alex', spatial=True).forward(img1, img2).mean() per frame pair).  The five convolutions run on ew_gemm_f16 (dense
- * mode, bias vector) over the patch rows of ew_im2col_f16; their outputs are stored PRE-ReLU and the three kernels below apply
- * max(x, 0) where they read (ReLU commutes with max-pooling).  Weights come from the caller: the project ships none.
+/* The layer kernels the metric networks share (csrc/convnet.hip; ABI 20 gave them one home: LPIPS/AlexNet, FVD's I3D and the latent MSE's
+ * Inception-v4 below).  Every convolution of the three runs on ew_gemm_f16 (dense mode, bias vector) over the patch rows of
+ * ew_im2col3d_f16; a 2-D network passes kt = 1 with its image batch on the T axis.  Conv outputs are stored PRE-ReLU and the kernels apply
+ * max(x, 0) where they read (ReLU commutes with max-pooling).  All tensors are fp16 [T,H,W,C] (channels innermost, C % 8 == 0), 16-byte
+ * aligned; no atomics, fixed summation orders: two calls are bit-identical.
  *
- * ew_im2col_f16: k x k / stride / zero-pad patch gather -> out fp16 [n_img*h_out*w_out, ldk], column (ky*k + kx)*C + c, columns
- *   [k*k*C, ldk) zero (ldk % 8 == 0: pad K to the multiple of 64 ew_gemm_f16 wants).  h_out = floor((h_in + 2 pad - k) / stride) + 1.
- *   src_kind 0: src fp16 NHWC [n_img,h_in,w_in,C], C % 8 == 0, 16-byte aligned; relu = 1 reads max(x, 0).
- *   src_kind 1 / 2 (the first layer): src uint8 [n_img,h_in,w_in,3] (a pixel is float32(k) / 255.0f) or fp32 [n_img,3,h_in,w_in], frames in
- *   [0,1]: network channel c reads frame channel (swap_rb ? 2 - c : c), v -> 2v - 1 -> (x - shift[c]) / scale[c] (the [-1,1] map of
- *   calculate_lpips.py and lpips' ScalingLayer), each step one float32 rounding, then fp16.  first_affine: HOST pointer to
- *   {shift[3], scale[3]} (read during the call); NULL, swap_rb = 0 for src_kind 0.
- * ew_maxpool3s2_relu_f16: MaxPool2d(3, 2) of max(x, 0), fp16 NHWC, h_out = floor((h_in - 3) / 2) + 1, C % 8 == 0.
+ * ew_im2col3d_f16: (kt,kh,kw) / stride (st,sh,sw) patch gather with front pads (pt,ph,pw), 0 <= pad < kernel -> out [t_out*h_out*w_out, ldk],
+ *   column ((dt*kh + dy)*kw + dx)*C + c; taps outside the input and the columns [kt*kh*kw*C, ldk) are zero (ldk % 8 == 0: pad K to the
+ *   multiple of 64 ew_gemm_f16 wants).  The caller chooses the output size (TensorFlow "SAME": ceil(in / stride), front pad = total // 2,
+ *   evoworld_amd.fvd.same_pad; or torch's floor((in + 2 pad - k) / stride) + 1); every window must overlap the input.  relu = 1 reads max(x, 0).
+ * ew_maxpool3d_relu_f16: max over the window's taps inside the input of max(x, 0), same geometry arguments -> out [t_out,h_out,w_out,C].
+ *   Equals a zero-padded max pool of post-ReLU input (the reference's MaxPool3dSamePadding): every value is >= 0.
+ * ew_avgpool3x3_relu_f16: AvgPool2d(3, stride=1, padding=1, count_include_pad=False) of max(x, 0), fp16 [n_img,H,W,C] -> the same shape,
+ *   C % 8 == 0: the taps inside the image added in fp32 in (dy, dx) order, divided by their number (4, 6 or 9 when H, W >= 3).
+ * ew_global_avgpool_relu_f32: fp16 [n_img,h,w,C] -> fp32 [n_img,C], the mean over h * w of max(x, 0): per (image, channel) one fp32 sum
+ *   in row-major pixel order, divided by h * w.  C % 8 == 0, pointers 16-byte aligned. */
+ew_status ew_im2col3d_f16(const void* src, void* out, int t_in, int h_in, int w_in, int C, int kt, int kh, int kw, int st, int sh, int sw,
+                          int pt, int ph, int pw, int t_out, int h_out, int w_out, int ldk, int relu, void* stream);
+ew_status ew_maxpool3d_relu_f16(const void* src, void* out, int t_in, int h_in, int w_in, int C, int kt, int kh, int kw, int st, int sh, int sw,
+                                int pt, int ph, int pw, int t_out, int h_out, int w_out, void* stream);
+ew_status ew_avgpool3x3_relu_f16(const void* src, void* out, int n_img, int H, int W, int C, void* stream);
+ew_status ew_global_avgpool_relu_f32(const void* src, float* out, int n_img, int h, int w, int C, void* stream);
+
+/* LPIPS with the AlexNet backbone (ABI 14; evoworld/metrics/other_metrics/calculate_lpips.py, calculate_all_metrics.py:195-221:
+ * lpips.LPIPS(net='alex', spatial=True).forward(img1, img2).mean() per frame pair).  The first convolution's patch rows come from
+ * ew_im2col_frames_f16, the other four's from ew_im2col3d_f16 and the two max pools from ew_maxpool3d_relu_f16 (csrc/convnet.hip, kt = 1,
+ * the image batch on T); the two kernels below are in csrc/lpips.hip.  Weights come from the caller: the project ships none.
+ *
+ * ew_im2col_frames_f16 (ABI 20): the first layer's k x k / stride / zero-pad patch gather from a
+ *   batch of frames -> out fp16 [n_img*h_out*w_out, ldk], column (ky*k + kx)*3 + c, columns [k*k*3, ldk) zero (ldk % 8 == 0: pad K to the
+ *   multiple of 64 ew_gemm_f16 wants).  h_out = floor((h_in + 2 pad - k) / stride) + 1.  src_kind 1: src uint8 [n_img,h_in,w_in,3] (a pixel
+ *   is float32(k) / 255.0f); 2: fp32 [n_img,3,h_in,w_in]; frames in [0,1]: network channel c reads frame channel (swap_rb ? 2 - c : c),
+ *   v -> 2v - 1 -> (x - shift[c]) / scale[c] (the [-1,1] map of calculate_lpips.py and lpips' ScalingLayer), each step one float32
+ *   rounding, then fp16.  first_affine: HOST pointer to {shift[3], scale[3]} (read during the call).
  * ew_lpips_head, one tap of F frame pairs: fa, fb fp16 [F, h, w, C] pre-ReLU (C % 8 == 0, <= 512); per pixel
  *   d = sum_c lin[c] * (a_c / (|a| + 1e-10) - b_c / (|b| + 1e-10))^2 with |.| over channels, in fp32; then
  *   acc[f] += sum_yx d[y,x] * wy[y] * wx[x] / n_out in fp64 (acc fp64 [F], read and written: zero it before the first tap).
@@ -494,19 +515,17 @@ ew_status ew_equi2cube_u8(const uint8_t* pano, uint8_t* cross, int V, int H, int
  *   lin fp32 [C].  Two fixed-order reduction stages through `workspace` (ew_lpips_head_workspace_bytes(F, h, w, C) bytes, 8-byte aligned;
  *   the block count depends on (h, w, C) only), no atomics: two calls are bit-identical, f's value does not depend on F, swapping fa and
  *   fb gives the same bits, identical inputs give exactly 0. */
-enum { EW_IM2COL_F16_NHWC = 0, EW_IM2COL_U8_HWC = 1, EW_IM2COL_F32_CHW = 2 };
-ew_status ew_im2col_f16(const void* src, int src_kind, void* out, int n_img, int h_in, int w_in, int C, int k, int stride, int pad,
-                        int h_out, int w_out, int ldk, int relu, int swap_rb, const float* first_affine, void* stream);
-ew_status ew_maxpool3s2_relu_f16(const void* src, void* out, int n_img, int h_in, int w_in, int C, int h_out, int w_out, void* stream);
+enum { EW_IM2COL_U8_HWC = 1, EW_IM2COL_F32_CHW = 2 };
+ew_status ew_im2col_frames_f16(const void* src, int src_kind, void* out, int n_img, int h_in, int w_in, int k, int stride, int pad, int h_out,
+                               int w_out, int ldk, int swap_rb, const float* first_affine, void* stream);
 size_t ew_lpips_head_workspace_bytes(int F, int h, int w, int C);
 ew_status ew_lpips_head(const void* fa, const void* fb, const float* lin, const double* wy, const double* wx, int F, int h, int w, int C,
                         double n_out, double* acc, void* workspace, void* stream);
 
 /* FVD's I3D network (ABI 16; evoworld/metrics/fvd/styleganv/fvd.py preprocess_single and evoworld/metrics/fvd/videogpt/pytorch_i3d.py
  * InceptionI3d(400): Inception-v1 inflated to 3-D, one clip per call).  The 57 BatchNorm-folded convolutions run on ew_gemm_f16 (dense
- * mode, bias vector, ld_out = the module's concat width) over the patch rows of ew_im2col3d_f16; their outputs are stored PRE-ReLU and
- * the kernels below apply max(x, 0) where they read.  Weights come from the caller: the project ships none.  All tensors are fp16
- * [T,H,W,C] (channels innermost, C % 8 == 0), 16-byte aligned; no atomics, fixed summation orders: two calls are bit-identical.
+ * mode, bias vector, ld_out = the module's concat width) over the patch rows of ew_im2col3d_f16, the max pools on ew_maxpool3d_relu_f16
+ * (csrc/convnet.hip); the two kernels below are in csrc/i3d.hip.  Weights come from the caller: the project ships none.
  *
  * ew_video_preprocess_f16: preprocess_single of one clip.  src_kind 1: uint8 [T,H,W,3] (a pixel is float32(k) / 255.0f); 2: fp32 [T,3,H,W] in
  *   [0,1] -> out [T,224,224,8], channels 3..7 zero.  Bilinear resize (align_corners=False, no antialias) to h_resized x w_resized with torch's
@@ -514,22 +533,12 @@ ew_status ew_lpips_head(const void* fa, const void* fb, const float* lin, const 
  *   torch's CPU kernel rounds (fma(scale, i + 0.5, -0.5); each blend t0 * w0 + t1 * w1 as fma(t0, w0, t1 * w1)), the 224 x 224
  *   crop at (y0, x0) of the resized frame, then (x - 0.5) * 2.  Network channel c reads frame channel (swap_rb ? 2 - c : c).  The caller
  *   computes h_resized, w_resized, y0, x0 (evoworld_amd.fvd.preprocess_geometry); only the cropped pixels are evaluated.
- * ew_im2col3d_f16: (kt,kh,kw) / stride (st,sh,sw) patch gather with front pads (pt,ph,pw), 0 <= pad < kernel -> out [t_out*h_out*w_out, ldk],
- *   column ((dt*kh + dy)*kw + dx)*C + c; taps outside the input and the columns [kt*kh*kw*C, ldk) are zero (ldk % 8 == 0: pad K to the
- *   multiple of 64 ew_gemm_f16 wants).  The caller chooses the output size (TensorFlow "SAME": ceil(in / stride), front pad = total // 2;
- *   evoworld_amd.fvd.same_pad); every window must overlap the input.  relu = 1 reads max(x, 0).
- * ew_maxpool3d_relu_f16: max over the window's taps inside the input of max(x, 0), same geometry arguments -> out [t_out,h_out,w_out,C].
- *   Equals the reference's zero-padded MaxPool3dSamePadding of post-ReLU input: every value is >= 0.
  * ew_i3d_head: x = the pre-ReLU Mixed_5c output [t_in >= 2, 7, 7, 1024] (any other shape is refused) -> logits fp32 [400] =
  *   mean over time of logits(AvgPool3d((2,7,7), 1)(relu(x))) = W v + b with v[c] = sum_j cnt_j sum_yx max(x[j,y,x,c], 0) / (98 (t_in - 1)),
  *   cnt_j = the number of windows frame j lies in.  w fp32 [400,1024], b fp32 [400]; fp32 throughout; workspace: ew_i3d_head_workspace_bytes()
  *   bytes, 16-byte aligned. */
 ew_status ew_video_preprocess_f16(const void* src, int src_kind, void* out, int T, int H, int W, int h_resized, int w_resized, int y0, int x0,
                                   int swap_rb, void* stream);
-ew_status ew_im2col3d_f16(const void* src, void* out, int t_in, int h_in, int w_in, int C, int kt, int kh, int kw, int st, int sh, int sw,
-                          int pt, int ph, int pw, int t_out, int h_out, int w_out, int ldk, int relu, void* stream);
-ew_status ew_maxpool3d_relu_f16(const void* src, void* out, int t_in, int h_in, int w_in, int C, int kt, int kh, int kw, int st, int sh, int sw,
-                                int pt, int ph, int pw, int t_out, int h_out, int w_out, void* stream);
 size_t ew_i3d_head_workspace_bytes(void);
 ew_status ew_i3d_head(const void* x, int t_in, int h_in, int w_in, int C, const float* w, const float* b, float* logits, void* workspace,
                       void* stream);
@@ -537,9 +546,9 @@ ew_status ew_i3d_head(const void* x, int t_in, int h_in, int w_in, int C, const 
 /* The latent MSE's Inception-v4 network (ABI 17; evoworld/metrics/other_metrics/calculate_latent_mse.py:11-79, run by
  * evoworld/metrics/calculate_all_metrics.py:220-221: timm's `inception_v4` with the classifier removed, 1536 pooled features per frame,
  * behind torchvision's Resize((299, 299)) + Normalize(ImageNet mean, std)).  The 149 BatchNorm-folded convolutions run on ew_gemm_f16
- * (dense mode, bias vector, ld_out = the module's concat width) over the patch rows of ew_im2col3d_f16 with kt = 1, the max pools on
- * ew_maxpool3d_relu_f16; conv outputs are stored PRE-ReLU and the kernels below apply max(x, 0) where they read.  Weights come from the
- * caller: the project ships none.  No atomics, fixed summation orders: two calls are bit-identical.
+ * (dense mode, bias vector, ld_out = the module's concat width) over the patch rows of ew_im2col3d_f16 with kt = 1, the pools on
+ * ew_maxpool3d_relu_f16, ew_avgpool3x3_relu_f16 and ew_global_avgpool_relu_f32 (csrc/convnet.hip); the kernel below is in
+ * csrc/inception.hip.  Weights come from the caller: the project ships none.
  *
  * ew_frames_resize_aa_norm_f16: the first layer's input.  src_kind 1: uint8 [F,H,W,3] (a pixel is float32(k) / 255.0f); 2: fp32 [F,3,H,W] in
  *   [0,1] -> out fp16 [F,out_h,out_w,8], channels 3..7 zero.  The resize is F.interpolate(mode="bilinear", align_corners=False,
@@ -548,16 +557,10 @@ ew_status ew_i3d_head(const void* x, int t_in, int h_in, int w_in, int C, const 
  *   tables give the first source index (int [n_out]), the tap count (int [n_out]) and the weights (float [n_out, taps], rows padded), as evoworld_amd.latent_mse.resize_table computes them on the host; also an upscale
  *   goes through the table (with antialias it is not plain bilinear).  Indices are clamped to the frame and counts to `taps`.  Then
  *   (x - mean[c]) / std[c] in float32, then fp16.  Network channel c reads frame channel (swap_rb ? 2 - c : c); mean and std are indexed
- *   by the network channel.  mean_std: HOST pointer to {mean[3], std[3]} (read during the call), std > 0.
- * ew_avgpool3x3_relu_f16: AvgPool2d(3, stride=1, padding=1, count_include_pad=False) of max(x, 0), fp16 [n_img,H,W,C] -> the same shape,
- *   C % 8 == 0: the taps inside the image added in fp32 in (dy, dx) order, divided by their number (4, 6 or 9 when H, W >= 3).
- * ew_global_avgpool_relu_f32: fp16 [n_img,h,w,C] -> fp32 [n_img,C], the mean over h * w of max(x, 0): per (image, channel) one fp32 sum
- *   in row-major pixel order, divided by h * w.  C % 8 == 0, pointers 16-byte aligned. */
+ *   by the network channel.  mean_std: HOST pointer to {mean[3], std[3]} (read during the call), std > 0. */
 ew_status ew_frames_resize_aa_norm_f16(const void* src, int src_kind, void* out, int F, int H, int W, int out_h, int out_w, const int* y_first,
                                        const int* y_count, const float* y_weights, int y_taps, const int* x_first, const int* x_count,
                                        const float* x_weights, int x_taps, int swap_rb, const float* mean_std, void* stream);
-ew_status ew_avgpool3x3_relu_f16(const void* src, void* out, int n_img, int H, int W, int C, void* stream);
-ew_status ew_global_avgpool_relu_f32(const void* src, float* out, int n_img, int h, int w, int C, void* stream);
 
 #ifdef __cplusplus
 }

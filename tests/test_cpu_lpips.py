@@ -158,14 +158,14 @@ def test_shell_script_passes_the_weights_through():
 def test_abi_declares_the_lpips_entries():
     from evoworld_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "evoworld_hip.h")).read()
-    for s in ("ew_im2col_f16", "ew_maxpool3s2_relu_f16", "ew_lpips_head", "ew_lpips_head_workspace_bytes"):
+    for s in ("ew_im2col_frames_f16", "ew_im2col3d_f16", "ew_maxpool3d_relu_f16", "ew_lpips_head", "ew_lpips_head_workspace_bytes"):
         assert re.search(r"\b%s\s*\(" % s, hdr), s
         assert s in _lib.HEADER.functions, s
     version = int(re.search(r"#define EW_ABI_VERSION (\d+)", hdr).group(1))
     assert version == _lib.ABI_VERSION and version >= 14
     lib = _lib.load()
     assert lib.ew_abi_version() == version
-    for s in ("ew_im2col_f16", "ew_maxpool3s2_relu_f16", "ew_lpips_head", "ew_lpips_head_workspace_bytes"):
+    for s in ("ew_im2col_frames_f16", "ew_im2col3d_f16", "ew_maxpool3d_relu_f16", "ew_lpips_head", "ew_lpips_head_workspace_bytes"):
         assert (getattr(lib, s).restype, list(getattr(lib, s).argtypes)) == _lib.HEADER.signatures[s], s
     # the workspace of the head: 8 bytes per (frame, block), a block count that depends on the tap alone
     one = lib.ew_lpips_head_workspace_bytes(1, 143, 255, 64)
@@ -177,8 +177,10 @@ def test_ops_refuse_cpu_tensors():
     from evoworld_amd import ops
     from evoworld_amd._lib import EvoWorldHipError
     with pytest.raises(EvoWorldHipError):
-        ops.maxpool3s2_relu(torch.zeros(1, 8, 8, 8, dtype=torch.float16))
+        ops.maxpool3d_relu(torch.zeros(1, 8, 8, 8, dtype=torch.float16), (1, 3, 3), (1, 2, 2), (0, 0, 0), (1, 3, 3))
     with pytest.raises(EvoWorldHipError):
-        ops.im2col(torch.zeros(1, 8, 8, 8, dtype=torch.float16), 3, 1, 1, 128)
+        ops.im2col3d(torch.zeros(1, 8, 8, 8, dtype=torch.float16), (1, 3, 3), (1, 1, 1), (0, 1, 1), (1, 8, 8), 128)
+    with pytest.raises(EvoWorldHipError):
+        ops.im2col_frames(torch.zeros(1, 8, 8, 3, dtype=torch.uint8), 3, 1, 1, 64, L.SHIFT, L.SCALE)
     with pytest.raises(EvoWorldHipError):
         L.LPIPSAlex.from_random(0, device="cpu")(torch.zeros(1, 64, 64, 3, dtype=torch.uint8), torch.zeros(1, 64, 64, 3, dtype=torch.uint8))

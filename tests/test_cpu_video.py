@@ -182,7 +182,7 @@ def test_cli_flags_signatures_and_prototypes():
     x = video.parse_arguments(["extract", "--input", "x.avi", "--output", "d"])
     assert x.command == "extract"
     H = _lib.HEADER
-    assert H.constants["EW_ABI_VERSION"] == 19 and H.constants["EW_JPEG_420"] == 420 and H.constants["EW_JPEG_444"] == 444
+    assert H.constants["EW_ABI_VERSION"] >= 19 and H.constants["EW_JPEG_420"] == 420 and H.constants["EW_JPEG_444"] == 444
     assert H.functions["ew_jpeg_segment_slot_bytes"] == ("size_t", ["int", "int"])
     assert H.functions["ew_jpeg_dct_quant"] == ("ew_status", ["const uint8_t*", "int16_t*", "int", "int", "int", "int", "int", "void*"])
     assert H.functions["ew_jpeg_entropy"] == ("ew_status", ["const int16_t*", "uint8_t*", "int*", "long long", "int", "int", "size_t", "void*"])

@@ -1,5 +1,5 @@
-"""-m gpu: LPIPS (AlexNet backbone, user-supplied weights) on the device -- evoworld_amd.lpips over ew_im2col_f16, ew_gemm_f16,
-ew_maxpool3s2_relu_f16 and ew_lpips_head (csrc/lpips.hip) -- against the fp32 PyTorch restatement tests/lpips_ref.py run on the host
+"""-m gpu: LPIPS (AlexNet backbone, user-supplied weights) on the device -- evoworld_amd.lpips over ew_im2col_frames_f16 and ew_lpips_head
+(csrc/lpips.hip), ew_im2col3d_f16 and ew_maxpool3d_relu_f16 with kt = 1 (csrc/convnet.hip) and ew_gemm_f16 -- against the fp32 PyTorch restatement tests/lpips_ref.py run on the host
 with seeded random weights (no LPIPS weights or package exist here: this row is not pinned by the reference's own run).
 
 Parity bound.  REL_BOUND is a relative error per frame pair: twice the worst value measured on the MI355X over every case of
@@ -172,12 +172,17 @@ def _unfold_rows(x_nhwc, k, stride, pad, ldk):
 
 
 def _run_im2col(src, kind, n, h, w, C, k, stride, pad, ldk, relu, swap, affine):
+    """kind 1 / 2: the frames' entry; kind 0: the fp16 gather, the 3-D entry with kt = 1 and the image batch on T"""
     from evoworld_amd import _lib
     lib = _lib.load()
     ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
 
     def run(view, prefill):
-        _lib.check(lib.ew_im2col_f16(P(src), kind, P(view), n, h, w, C, k, stride, pad, ho, wo, ldk, relu, swap, affine, None), "ew_im2col_f16")
+        if kind:
+            _lib.check(lib.ew_im2col_frames_f16(P(src), kind, P(view), n, h, w, k, stride, pad, ho, wo, ldk, swap, affine, None), "ew_im2col_frames_f16")
+        else:
+            _lib.check(lib.ew_im2col3d_f16(P(src), P(view), n, h, w, C, 1, k, k, 1, stride, stride, 0, pad, pad, n, ho, wo, ldk, relu, None),
+                       "ew_im2col3d_f16")
     return KC.two_prefills(run, (n * ho * wo, ldk, torch.float16, {"ld": ldk}))[0].view
 
 
@@ -201,6 +206,7 @@ def test_im2col_first_layer_is_exact():
 
 
 def test_im2col_f16_is_exact():
+    from evoworld_amd import ops
     g = torch.Generator().manual_seed(4)
     for (h, w, C), k, pad, relu in (((71, 127, 64), 5, 2, 0), ((35, 63, 192), 3, 1, 0), ((35, 63, 384), 3, 1, 1), ((35, 63, 256), 3, 1, 1),
                                     ((143, 255, 64), 3, 1, 1)):
@@ -209,6 +215,7 @@ def test_im2col_f16_is_exact():
         want = _unfold_rows(x.clamp_min(0) if relu else x, k, 1, pad, ldk)
         got = _run_im2col(x, 0, 2, h, w, C, k, 1, pad, ldk, relu, 0, None)
         assert torch.equal(got, want), (h, w, C, k)
+        assert torch.equal(ops.im2col3d(x, (1, k, k), (1, 1, 1), (0, pad, pad), (2, h, w), ldk, relu), want)
 
 
 def test_maxpool3s2_relu_is_exact():
@@ -222,12 +229,12 @@ def test_maxpool3s2_relu_is_exact():
         assert want.shape == (2, ho, wo, C)
 
         def run(view, prefill):
-            _lib.check(lib.ew_maxpool3s2_relu_f16(P(x), P(view), 2, h, w, C, ho, wo, None), "ew_maxpool3s2_relu_f16")
+            _lib.check(lib.ew_maxpool3d_relu_f16(P(x), P(view), 2, h, w, C, 1, 3, 3, 1, 2, 2, 0, 0, 0, 2, ho, wo, None), "ew_maxpool3d_relu_f16")
         got = KC.two_prefills(run, (2 * ho * wo, C, torch.float16, {"ld": C}))[0].view
         assert torch.equal(got.view(2, ho, wo, C), want), (h, w, C)
-        assert torch.equal(ops.maxpool3s2_relu(x), want)
+        assert torch.equal(ops.maxpool3d_relu(x, (1, 3, 3), (1, 2, 2), (0, 0, 0), (2, ho, wo)), want)
     neg = -torch.rand(1, 7, 7, 8, generator=g).half().to(DEV)                            # all negative: the ReLU gives zeros
-    assert not ops.maxpool3s2_relu(neg).any()
+    assert not ops.maxpool3d_relu(neg, (1, 3, 3), (1, 2, 2), (0, 0, 0), (1, 3, 3)).any()
 
 
 def test_lpips_head_against_fp64():
@@ -269,20 +276,25 @@ def test_kernel_entries_refuse_bad_arguments():
     out = torch.zeros(1 << 16, dtype=torch.float16, device=DEV)
     d = torch.zeros(64, dtype=torch.float64, device=DEV)
     f = torch.zeros(64, dtype=torch.float32, device=DEV)
-    cases = [(lambda: lib.ew_im2col_f16(P(x), 0, P(out), 1, 8, 8, 8, 3, 1, 1, 7, 8, 128, 0, 0, None, None), "is not floor"),
-             (lambda: lib.ew_im2col_f16(P(x), 0, P(out), 1, 8, 8, 8, 3, 1, 1, 8, 8, 64, 0, 0, None, None), "ldk = 64"),
-             (lambda: lib.ew_im2col_f16(P(x), 0, P(out), 1, 8, 8, 4, 3, 1, 1, 8, 8, 64, 0, 0, None, None), "C % 8"),
-             (lambda: lib.ew_im2col_f16(P(x), 1, P(out), 1, 8, 8, 3, 3, 1, 1, 8, 8, 64, 0, 0, None, None), "six scaling constants"),
-             (lambda: lib.ew_im2col_f16(P(x), 3, P(out), 1, 8, 8, 8, 3, 1, 1, 8, 8, 128, 0, 0, None, None), "src_kind 3"),
-             (lambda: lib.ew_maxpool3s2_relu_f16(P(x), P(out), 1, 8, 8, 8, 4, 3, None), "is not floor"),
-             (lambda: lib.ew_maxpool3s2_relu_f16(P(x), P(out), 1, 2, 8, 8, 0, 3, None), "H, W >= 3"),
+    affine = (ctypes.c_float * 6)(0, 0, 0, 1, 1, 1)
+    # the fp16 gather and the pool are the 3-D entries with kt = 1: they take the caller's output size and refuse one whose windows leave the
+    # input (an 11th output row of an 8-row image; a 5th pooled row; no pooled row at all), not one that merely differs from floor(...)
+    cases = [(lambda: lib.ew_im2col3d_f16(P(x), P(out), 1, 8, 8, 8, 1, 3, 3, 1, 1, 1, 0, 1, 1, 1, 11, 8, 128, 0, None), "has windows that miss"),
+             (lambda: lib.ew_im2col3d_f16(P(x), P(out), 1, 8, 8, 8, 1, 3, 3, 1, 1, 1, 0, 1, 1, 1, 8, 8, 64, 0, None), "ldk = 64"),
+             (lambda: lib.ew_im2col3d_f16(P(x), P(out), 1, 8, 8, 4, 1, 3, 3, 1, 1, 1, 0, 1, 1, 1, 8, 8, 64, 0, None), "C % 8"),
+             (lambda: lib.ew_im2col_frames_f16(P(x), 1, P(out), 1, 8, 8, 3, 1, 1, 7, 8, 64, 0, affine, None), "is not floor"),
+             (lambda: lib.ew_im2col_frames_f16(P(x), 1, P(out), 1, 8, 8, 3, 1, 1, 8, 8, 64, 0, None, None), "six scaling constants"),
+             (lambda: lib.ew_im2col_frames_f16(P(x), 3, P(out), 1, 8, 8, 3, 1, 1, 8, 8, 128, 0, affine, None), "src_kind 3"),
+             (lambda: lib.ew_im2col_frames_f16(P(x), 0, P(out), 1, 8, 8, 3, 1, 1, 8, 8, 128, 0, affine, None), "src_kind 0"),
+             (lambda: lib.ew_maxpool3d_relu_f16(P(x), P(out), 1, 8, 8, 8, 1, 3, 3, 1, 2, 2, 0, 0, 0, 1, 5, 3, None), "has windows that miss"),
+             (lambda: lib.ew_maxpool3d_relu_f16(P(x), P(out), 1, 2, 8, 8, 1, 3, 3, 1, 2, 2, 0, 0, 0, 1, 0, 3, None), "has windows that miss"),
              (lambda: lib.ew_lpips_head(P(x), P(x), P(f), P(d), P(d), 1, 8, 8, 12, 64.0, P(d), P(d), None), "C = 12"),
              (lambda: lib.ew_lpips_head(P(x), P(x), P(f), P(d), P(d), 1, 8, 8, 8, 0.0, P(d), P(d), None), "n_out"),
              (lambda: lib.ew_lpips_head(P(x), P(x), None, P(d), P(d), 1, 8, 8, 8, 64.0, P(d), P(d), None), "NULL")]
     for call, msg in cases:
         assert call() != 0 and msg in lib.ew_last_error().decode(), (msg, lib.ew_last_error())
     with pytest.raises(TypeError):
-        ops.maxpool3s2_relu(x.float())
+        ops.maxpool3d_relu(x.float(), (1, 3, 3), (1, 2, 2), (0, 0, 0), (1, 3, 3))
     with pytest.raises(ValueError):
         ops.lpips_head(x, x, f[:8], d[:8], d[:7], 64, d[:1])
 
