@@ -2,7 +2,7 @@
 kernel_checks.  It states the kernel's NUMERICS, not its layout: fp16 q / k / v, fp32 scores, keys in blocks of 32 with a running maximum m,
 P = exp2((s - m) * scale * log2 e) rounded to fp16, the normaliser l summing the same rounded values, fp32 accumulators for l and O, both
 multiplied by alpha = exp2((m_old - m_new) * scale * log2 e) in every block, one division and one rounding to fp16 at the end.
-tests/test_cpu_attn_stream_ref.py holds it against fp64 SDPA."""
+tests/test_cpu_attn_stream_ref.py holds it against fp64 SDPA (the forced-rescale inputs, spike_case, live in tests/attn_cases.py)."""
 import math
 
 import torch
@@ -28,22 +28,3 @@ def attn_stream(q, k, v, scale=0.125, block=32):
         m = m_new
     return (acc / l[..., None]).half()
 
-
-def spike_case(pattern, B=1, T=97, S=6, heads=1, seed=3):
-    """fp16 q, k, v [B, T, S, heads, 64] that force the rescale: every query gets +16 u (u a unit vector); `first`: only key 3 gets +16 u (the
-    maximum is set in the first block and never displaced); `last`: only key T-1 (the maximum jumps by ~40 logits in the final, one-key block of
-    T = 97); `rising`: key t gets +(16 t / (T-1)) u (the maximum rises in every block)."""
-    g = torch.Generator().manual_seed(seed)
-    q, k, v = (torch.randn(B, T, S, heads, 64, generator=g) for _ in range(3))
-    u = torch.randn(64, generator=g)
-    u = u / u.norm()
-    q = q + 16.0 * u
-    if pattern == "first":
-        k[:, 3] += 16.0 * u
-    elif pattern == "last":
-        k[:, T - 1] += 16.0 * u
-    elif pattern == "rising":
-        k = k + (16.0 * torch.arange(T, dtype=torch.float32) / (T - 1))[None, :, None, None, None] * u
-    else:
-        raise ValueError(pattern)
-    return q.half(), k.half(), v.half()

@@ -7,6 +7,12 @@
 - two_prefills: the same call into two sets of guarded buffers prefilled with different patterns must give bit-identical
   results -- catches elements that are never written and kernels that read their own output.
 
+- Haloed: the input-side mirror of Guarded -- an operand view inside one larger allocation whose surround (rows before and after,
+  columns between the width and the row stride) holds a fill pattern; same_under_halos runs the same call under every fill of
+  HALO_FILLS and requires bit-identical outputs: NaN and inf catch 0 * halo, the largest finite value catches a halo element that is
+  weighted, zero is what torch.zeros operands give (and must equal the plain, un-haloed call).  The halo is ordinary memory of the
+  operand's own allocation: nothing outside it is read.
+
 Everything runs on the device of the tensors it is given (some GPU buffers are several GB).
 tests/test_cpu_kernel_checks.py shows on the CPU that each check catches what it claims."""
 import torch
@@ -109,6 +115,54 @@ def assert_same_bits(a, b, what="output"):
         idx = tuple(int(v) for v in diff.nonzero()[0])
         raise AssertionError(f"{what}: {int(diff.sum())} elements differ between the two prefills, first at {idx} "
                              f"({a[idx].item()} vs {b[idx].item()}): never written, or the kernel reads its own output")
+
+
+# fp16 bit patterns of an operand's surround: zero, the NaN payload of _PATTERNS, +inf, the largest finite value
+HALO_FILLS = {"zero": 0x0000, "nan": _PATTERNS[torch.float16][0], "inf": 0x7C00, "max": 0x7BFF}
+
+
+class Haloed:
+    """`data` (fp16 [rows, width], any device) copied into a view with row stride `ld` of one allocation of
+    (pad_before + rows + pad_after) * ld elements; every other element of it holds HALO_FILLS[fill].  `view` goes to the kernel
+    (pass `ld` as its row stride); ld and pad_before * ld are multiples of 8 so that the view is 16-byte aligned."""
+
+    def __init__(self, data, *, ld=None, pad_cols=16, pad_before=3, pad_after=5, fill="zero", device=None):
+        assert data.dtype == torch.float16 and data.ndim == 2
+        rows, width = data.shape
+        self.ld = width + pad_cols if ld is None else ld
+        assert self.ld >= width and self.ld % 8 == 0, (self.ld, width)
+        self.fill = fill
+        self.buf = torch.empty((pad_before + rows + pad_after) * self.ld, dtype=torch.float16, device=device or data.device)
+        self.buf.view(torch.int16).fill_(_signed(HALO_FILLS[fill], torch.int16))
+        self.view = self.buf[pad_before * self.ld: (pad_before + rows) * self.ld].view(rows, self.ld)[:, :width]
+        self.view.copy_(data)
+
+
+def same_under_halos(run, operands, plain=None, fills=tuple(HALO_FILLS), device=None):
+    """operands: (fp16 [rows, width] data, kwargs-for-Haloed) per input.  Calls run(*haloed) -- each argument a Haloed, whose .view and
+    .ld go to the kernel -- once per fill; run returns the output tensor.  Every output must equal the first fill's bit for bit, and
+    `plain` (the output of the un-haloed call) when given.  Returns the first output."""
+    first = None
+    for fill in fills:
+        out = run(*[Haloed(d, fill=fill, device=device, **kw) for d, kw in operands])
+        if out.is_cuda:
+            torch.cuda.synchronize()
+        out = out.clone()
+        if first is None:
+            first, first_fill = out, fill
+            if plain is not None:
+                _assert_halo_bits(plain, out, f"the un-haloed call vs the '{fill}' halo")
+        else:
+            _assert_halo_bits(first, out, f"halo fill '{first_fill}' vs '{fill}'")
+    return first
+
+
+def _assert_halo_bits(a, b, what):
+    diff = a.view(_INT[a.dtype]) != b.view(_INT[b.dtype])
+    if bool(diff.any()):
+        idx = tuple(int(v) for v in diff.nonzero()[0])
+        raise AssertionError(f"halo: {what}: {int(diff.sum())} output elements differ, first at {idx} ({a[idx].item()} vs {b[idx].item()}): "
+                             f"an element outside the operand reached the result")
 
 
 def two_prefills(run, *specs, device="cuda"):

@@ -5,7 +5,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from attn_stream_ref import attn_stream, spike_case
+from attn_cases import spike_case
+from attn_stream_ref import attn_stream
 from kernel_checks import rel_l2, worst_row
 
 

@@ -3,7 +3,7 @@ import pytest
 import torch
 
 from conftest import rel_l2
-from kernel_checks import Guarded, fill_pattern, two_prefills, worst_row
+from kernel_checks import HALO_FILLS, Guarded, Haloed, fill_pattern, same_under_halos, two_prefills, worst_row
 
 
 def test_worst_row_flags_one_row_that_rel_l2_misses():
@@ -79,6 +79,58 @@ def test_two_prefills_flags_a_kernel_that_reads_its_output():
         o += 1.0                                          # reads what is there: NaN under one prefill, 203.25 under the other
     with pytest.raises(AssertionError, match="differ"):
         two_prefills(accumulates, (8, 8, torch.float16, dict(pad_rows=1)), device="cpu")
+
+
+def _emulated(reach):
+    """a row-sum 'kernel' over a Haloed [rows, width] operand that also touches one element outside it"""
+    def run(x):
+        rows, width = x.view.shape
+        off = x.view.storage_offset()
+        wide = x.buf.as_strided((rows + 2, x.ld), (x.ld, 1), off - x.ld).float()      # the view with one row before and one after
+        out = wide[1:-1, :width].sum(dim=1)
+        if reach == "column":
+            out = out + wide[1:-1, width]                 # the column just past the width
+        elif reach == "row_after_x0":
+            out[-1] = out[-1] + 0.0 * wide[-1, 0]         # the row after the last, weight zero ("never consumed")
+        elif reach == "row_before":
+            out[0] = out[0] + wide[0, 2]
+        return out
+    return run
+
+
+def test_halo_fills_and_layout():
+    data = torch.arange(5 * 24, dtype=torch.float32).reshape(5, 24).half()
+    for fill, bits in HALO_FILLS.items():
+        h = Haloed(data, pad_cols=8, pad_before=2, pad_after=3, fill=fill)
+        assert h.ld == 32 and h.view.data_ptr() % 16 == h.buf.data_ptr() % 16 and torch.equal(h.view, data)
+        surround = torch.ones(10, 32, dtype=torch.bool)
+        surround[2:7, :24] = False
+        assert (h.buf.view(torch.int16).view(10, 32)[surround] == (bits if bits < 0x8000 else bits - 0x10000)).all()
+    assert torch.isnan(Haloed(data, fill="nan").buf[0]) and torch.isinf(Haloed(data, fill="inf").buf[0])
+    assert Haloed(data, fill="max").buf[0] == 65504.0
+
+
+def test_same_under_halos_catches_reads_outside_the_operand():
+    data = torch.randn(9, 24, generator=torch.Generator().manual_seed(0)).half()
+    ops = [(data, dict(pad_cols=8))]
+    plain = data.float().sum(dim=1)
+    assert torch.equal(same_under_halos(_emulated("none"), ops, plain=plain), plain)
+    with pytest.raises(AssertionError, match="halo"):
+        same_under_halos(_emulated("column"), ops)
+    with pytest.raises(AssertionError, match="halo"):
+        same_under_halos(_emulated("row_before"), ops)
+    # weight zero: 0 * NaN and 0 * inf are NaN, 0 * 65504 is 0 -- the finite fill alone does not see it
+    same_under_halos(_emulated("row_after_x0"), ops, plain=plain, fills=("zero", "max"))
+    with pytest.raises(AssertionError, match="'zero' vs 'nan'"):
+        same_under_halos(_emulated("row_after_x0"), ops, plain=plain, fills=("zero", "nan"))
+    with pytest.raises(AssertionError, match="'zero' vs 'inf'"):
+        same_under_halos(_emulated("row_after_x0"), ops, plain=plain, fills=("zero", "inf"))
+    # ... and a weighted element is seen by the finite fill alone, too
+    with pytest.raises(AssertionError, match="'zero' vs 'max'"):
+        same_under_halos(_emulated("column"), ops, fills=("zero", "max"))
+    # the result under the zero halo is held to the plain, un-haloed call
+    with pytest.raises(AssertionError, match="un-haloed"):
+        same_under_halos(_emulated("none"), ops, plain=plain + 1.0, fills=("zero",))
 
 
 def test_fill_pattern_workspace():

@@ -7,7 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from attn_stream_ref import spike_case
+from attn_cases import spike_case
 from kernel_checks import rel_l2, report, two_prefills
 
 pytestmark = pytest.mark.gpu

@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from attn_cases import LAZY_PATTERNS, SHIFT_CASES, lazy_max_case, shift_case
 from conftest import rel_l2
 from kernel_checks import fill_pattern, report, two_prefills
 
@@ -52,6 +53,20 @@ WORST_ROW = {
     'softmax_rows 77x1024 ld+40 split': (0.00087, 0.000436),  # measured worst row; rel-L2 0.00022 row 31
     'softmax_rows 300x136 ld+40 hi': (0.00091, 0.000458),  # measured worst row; rel-L2 0.000192 row 19
     'softmax_rows 9x2048 ld+40 split': (0.00063, 0.000319),  # measured worst row; rel-L2 0.000178 row 5
+    'attn_spatial_log2 shift 2x512x2 0': (0.0009, 0.00045),  # measured worst row; rel-L2 0.000248 row 51
+    'attn_spatial_log2 shift 1x1000x1 0': (0.001, 0.000532),  # measured worst row; rel-L2 0.000247 row 761
+    'attn_spatial_log2 shift 3x136x5 0': (0.00079, 0.000399),  # measured worst row; rel-L2 0.000288 row 120
+    'attn_spatial_log2 shift 1x2304x1 -60': (0.001, 0.000511),  # measured worst row; rel-L2 0.00025 row 654
+    'attn_spatial_log2 shift 1x640x2 40': (0.001, 0.000517),  # measured worst row; rel-L2 0.000245 row 48
+    'attn_spatial_log2 shift 1x128x1 -60': (0.00092, 0.000462),  # measured worst row; rel-L2 0.000242 row 31
+    'attn_spatial_log2 shift 2x72x2 40': (0.00078, 0.000393),  # measured worst row; rel-L2 0.000269 row 74
+    'attn_spatial_log2 lazy max ramp': (0.001, 0.000537),  # measured worst row; rel-L2 0.000289 row 1656
+    'attn_spatial_log2 lazy max jumps': (0.00097, 0.000488),  # measured worst row; rel-L2 0.000287 row 1987
+    'attn_spatial_log2 lazy max overflow': (0.001, 0.000543),  # measured worst row; rel-L2 0.000295 row 942
+    'attn_spatial_log2 lazy max flat_below': (0.00093, 0.000469),  # measured worst row; rel-L2 0.000296 row 314
+    'attn_spatial_log2 lazy max flat_above': (0.00097, 0.000489),  # measured worst row; rel-L2 0.000297 row 1587
+    'attn_spatial_log2 lazy max late_spike': (0.00092, 0.000464),  # measured worst row; rel-L2 0.000289 row 1656
+    'attn_spatial_log2 lazy max ragged_spike': (0.00091, 0.000457),  # measured worst row; rel-L2 0.00026 row 1910
 }
 
 
@@ -417,55 +432,39 @@ def _attn_spatial_case(ops, n_seq, S, heads, log2):
     report(case, o, ref, _wr(case), 2e-3)
 
 
-@pytest.mark.parametrize("n_seq,S,heads,shift", [(2, 512, 2, 0.0), (1, 1000, 1, 0.0), (3, 136, 5, 0.0), (1, 2304, 1, -60.0), (1, 640, 2, 40.0),
-                                                 (1, 128, 1, -60.0), (2, 72, 2, 40.0)])        # ... and on the two-tile path
+@pytest.mark.parametrize("n_seq,S,heads,shift", SHIFT_CASES)        # (the last two: on the two-tile path)
 def test_attn_spatial_log2(ops, n_seq, S, heads, shift):
     """ew_attn_spatial_log2_f16: q, k pre-scaled by sqrt(scale * log2 e) (what the projection epilogue writes); the MFMA's C operand
     subtracts the running max.  `shift` moves every score of a head by a constant (one extra q / k channel pair): strongly negative
-    first-tile maxima (the max must be SET on the first tile, not only raised) and large positive ones (deferred-max raises)."""
+    first-tile maxima (the max must be SET on the first tile, not only raised) and large positive ones (deferred-max raises).
+    (attn_cases.shift_case builds the operands; test_gpu_attention.py runs them on the scale-and-shift form.)"""
     C = heads * 64
     rows = n_seq * S
-    qk32 = rnd(rows, 2 * C, seed=1)
-    v = rnd(rows, C, seed=2).half().to(DEV)
-    qk32[: S // 2, :64] *= 4.0                     # sharpen some rows so the running max moves between tiles
-    if shift:
-        qk32[:, 0] = abs(shift) ** 0.5 * 8 ** 0.5  # q_0 * k_0 * scale = shift
-        qk32[:, C] = (1 if shift > 0 else -1) * abs(shift) ** 0.5 * 8 ** 0.5
-        qk32[S // 3:, C] *= 0.5                    # ... and smaller for later keys: the first tile holds the max
-    qk = (qk32 * ops.QK_LOG2_PRESCALE).half().to(DEV)
+    qk_l2, v = shift_case(n_seq, S, heads, shift)
+    qk, v = qk_l2.half().to(DEV), v.to(DEV)
     vt = v.T.contiguous()
     o = torch.empty(rows, C, dtype=torch.float16, device=DEV)
     ops.attn_spatial_log2(qk, qk[:, C:], vt, o, n_seq, S, heads, 2 * C, rows, C)
-    q = qk[:, :C].float().reshape(n_seq, S, heads, 64).transpose(1, 2)
-    k = qk[:, C:].float().reshape(n_seq, S, heads, 64).transpose(1, 2)
-    vv = v.float().reshape(n_seq, S, heads, 64).transpose(1, 2)
+    q = qk[:, :C].double().reshape(n_seq, S, heads, 64).transpose(1, 2)
+    k = qk[:, C:].double().reshape(n_seq, S, heads, 64).transpose(1, 2)
+    vv = v.double().reshape(n_seq, S, heads, 64).transpose(1, 2)
     ref = F.scaled_dot_product_attention(q, k, vv, scale=math.log(2.0)).transpose(1, 2).reshape(rows, C)   # 2^(q.k) = e^(ln2 q.k)
     assert torch.isfinite(o).all()
-    e = rel_l2(o.float().cpu(), ref.cpu())
-    print(f"attn_spatial_log2 n_seq={n_seq} S={S} heads={heads} shift={shift}: rel-L2 {e:.2e}")
-    assert e < 2e-3
+    case = f"attn_spatial_log2 shift {n_seq}x{S}x{heads} {shift:g}"
+    report(case, o, ref, _wr(case), 2e-3)
 
 
-@pytest.mark.parametrize("pattern", ["ramp", "jumps", "overflow", "flat_below", "flat_above", "late_spike", "ragged_spike"])
+@pytest.mark.parametrize("pattern", LAZY_PATTERNS)
 def test_attn_spatial_log2_lazy_max(ops, pattern):
     """Round 5: the log2 kernel looks at a tile's maximum only when the tile's ROW SUM leaves the safe range (and on the first tile).  Score
     profiles that stress exactly that decision: key j carries an offset f(j) in log2 units (q channel 0 = 1, k channel 0 = f) on top of random
     scores -- slow ramps (many small raises), jumps up and down, jumps large enough to overflow the exponentials before the check sees them,
-    plateaus just below / just above the row-sum limit (32 keys x 2^4.9 = 955 < 1024 < 32 x 2^5.1), a spike in the very last (ragged) tile."""
-    n_seq, heads = 2, 2
-    S = 1000 if pattern == "ragged_spike" else 1024
+    plateaus just below / just above the row-sum limit (32 keys x 2^4.9 = 955 < 1024 < 32 x 2^5.1), a spike in the very last (ragged) tile.
+    (attn_cases.lazy_max_case builds the operands; test_gpu_attention.py runs them on the scale-and-shift form.)"""
+    n_seq, S, heads, qk32, v = lazy_max_case(pattern, "log2")
     C = heads * 64
     rows = n_seq * S
-    qk32 = rnd(rows, 2 * C, seed=5) * 0.6
-    v = rnd(rows, C, seed=6).half().to(DEV)
-    t = (torch.arange(S) // 64).float()
-    f = {"ramp": 0.37 * t, "jumps": 30.0 * ((t % 3) == 2).float() - 12.0 * ((t % 5) == 1).float(), "overflow": 200.0 * t,
-         "flat_below": 4.9 * (t > 0).float(), "flat_above": 5.1 * (t > 0).float(), "late_spike": 25.0 * (t == 15).float(),
-         "ragged_spike": 40.0 * (torch.arange(S) >= 990).float()}[pattern]
-    for h in range(heads):
-        qk32[:, h * 64] = 1.0
-        qk32[:, C + h * 64] = f.repeat(n_seq) * (1.0 if h == 0 else -0.5)       # the second head sees the mirrored (falling) profile
-    qk = qk32.half().to(DEV)                          # already in log2 units: what ew_attn_spatial_log2_f16 takes
+    qk, v = qk32.half().to(DEV), v.to(DEV)            # already in log2 units: what ew_attn_spatial_log2_f16 takes
     vt = v.T.contiguous()
     o = torch.empty(rows, C, dtype=torch.float16, device=DEV)
     ops.attn_spatial_log2(qk, qk[:, C:], vt, o, n_seq, S, heads, 2 * C, rows, C)
@@ -474,9 +473,8 @@ def test_attn_spatial_log2_lazy_max(ops, pattern):
     vv = v.double().reshape(n_seq, S, heads, 64).transpose(1, 2)
     ref = F.scaled_dot_product_attention(q, k, vv, scale=math.log(2.0)).transpose(1, 2).reshape(rows, C)
     assert torch.isfinite(o).all()
-    e = rel_l2(o.double().cpu(), ref.cpu())
-    print(f"attn_spatial_log2 lazy max, {pattern}: rel-L2 {e:.2e}")
-    assert e < 2e-3
+    case = f"attn_spatial_log2 lazy max {pattern}"
+    report(case, o, ref, _wr(case), 2e-3)
 
 
 @pytest.mark.parametrize("B,T,S,heads", [(2, 25, 37, 2), (1, 4, 512, 1), (2, 1, 9, 3), (1, 32, 5, 1), (2, 49, 21, 2), (1, 64, 7, 1),
