@@ -21,6 +21,7 @@
 //                      the offsets are the caller's scan of the byte counts.
 // No global atomics and no data-dependent order: two calls return identical bytes.
 #include "common.h"
+#include "jpeg_tables.h"
 
 namespace {
 
@@ -35,10 +36,6 @@ constexpr int ENT_WORDS = ENT_BLOCKS * BLOCK_MAX_BYTES / 4 + 4;   // + the carri
 
 struct QuantTables { unsigned char q[2][64]; };  // natural (row-major) order; [0] luminance, [1] chrominance
 
-// zigzag position -> natural index (T.81 figure A.6)
-__device__ __constant__ unsigned char d_zigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                                      41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                                      30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 // Annex K.1 / K.2, natural order
 const unsigned char K1_LUMA[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,
                                    69, 56, 14, 17, 22,  29,  51,  87,  80, 62, 18, 22, 37,  56,  68,  109, 103, 77, 24, 35, 55, 64,
@@ -62,25 +59,6 @@ QuantTables quant_tables(int quality) {
 }
 
 // ------------------------------------------------------------------------------------------------ DCT + quantisation
-// 0.5 * cos(j * pi / 16), j = 0 .. 8
-constexpr float HALF_COS[9] = {0.5f,
-                               0.4903926402016152f,
-                               0.46193976625564337f,
-                               0.4157348061512726f,
-                               0.35355339059327373f,
-                               0.27778511650980114f,
-                               0.19134171618254492f,
-                               0.09754516100806417f,
-                               0.0f};
-
-// entry (k, n) of the orthonormal 8-point DCT-II: sqrt(1/8) for k = 0, else 0.5 * cos((2n + 1) k pi / 16)
-constexpr float dct_m(int k, int n) {
-    if (k == 0) return HALF_COS[4];
-    int m = ((2 * n + 1) * k) % 32;
-    if (m > 16) m = 32 - m;
-    return m > 8 ? -HALF_COS[16 - m] : HALF_COS[m];
-}
-
 // p[0], p[stride], ... p[7 * stride] <- their DCT
 __device__ __forceinline__ void dct8(float* p, int stride) {
     float x[8], y[8];

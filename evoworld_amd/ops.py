@@ -589,6 +589,113 @@ def jpeg_pack(slots, seg_bytes, mcu_rows):
     return stream, frame_bytes
 
 
+JPEG_SEG_STATUS = {_lib.EW_JPEG_SEG_BAD_CODE: "no Huffman code matches the bits (or an EOBn symbol of a progressive scan)",
+                   _lib.EW_JPEG_SEG_INDEX: "a zero run leads past coefficient 63",
+                   _lib.EW_JPEG_SEG_SIZE: "a DC category above 11 or an AC size above 10",
+                   _lib.EW_JPEG_SEG_EXHAUSTED: "the segment's bytes end before its MCUs",
+                   _lib.EW_JPEG_SEG_LEFTOVER: "more than 7 bits are left behind the last MCU",
+                   _lib.EW_JPEG_SEG_MARKER: "a marker (FF followed by anything but 00) inside the segment",
+                   _lib.EW_JPEG_SEG_RANGE: "the segment lies outside the uploaded bytes"}
+
+
+def jpeg_huffman_decode(stream, seg_start, seg_bytes, tables, V, mcu_rows, mcu_cols, blocks_per_mcu, restart_interval, out=None):
+    """The entropy-coded bytes of V frames with identical headers -> (coef int16 [V, mcu_rows, mcu_cols, blocks_per_mcu, 64] in scan and
+    zigzag order, the layout of jpeg_dct_quant; seg_status int32 [n], 0 or a key of JPEG_SEG_STATUS) on the device
+    (ew_jpeg_huffman_decode).  stream uint8 [bytes]; seg_start int64 [n] and seg_bytes int32 [n]: every restart segment
+    without its RSTm marker, restart_interval MCUs each (0: one segment per frame); tables uint8 [4 * EW_JPEG_HUFF_TABLE_BYTES]
+    (video.huffman_device_tables).  `out`: a contiguous int16 tensor of the coefficients' shape to write into."""
+    _req(stream, torch.uint8, "stream"); _req(seg_start, torch.int64, "seg_start"); _req(seg_bytes, torch.int32, "seg_bytes")
+    _req(tables, torch.uint8, "tables")
+    for name, v, lo, hi in (("V", V, 1, 65535), ("mcu_rows", mcu_rows, 1, 8192), ("mcu_cols", mcu_cols, 1, 8192),
+                            ("restart_interval", restart_interval, 0, 65535)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError(f"{name} must be an integer {lo}..{hi}, got {v!r}")
+    if blocks_per_mcu not in (3, 6):
+        raise ValueError(f"blocks_per_mcu must be 6 (4:2:0) or 3 (4:4:4), got {blocks_per_mcu!r}")
+    mcus = mcu_rows * mcu_cols
+    interval = mcus if restart_interval == 0 or restart_interval > mcus else restart_interval
+    n = V * -(-mcus // interval)
+    if stream.ndim != 1 or stream.numel() == 0 or tuple(seg_start.shape) != (n,) or tuple(seg_bytes.shape) != (n,):
+        raise ValueError(f"stream must be a non-empty [bytes] and seg_start, seg_bytes [{n}] ({V} frames of {mcus} MCUs at interval "
+                         f"{restart_interval}), got {tuple(stream.shape)}, {tuple(seg_start.shape)}, {tuple(seg_bytes.shape)}")
+    if tables.numel() != 4 * _lib.EW_JPEG_HUFF_TABLE_BYTES:
+        raise ValueError(f"tables must hold 4 x {_lib.EW_JPEG_HUFF_TABLE_BYTES} bytes, got {tables.numel()}")
+    shape = (V, mcu_rows, mcu_cols, blocks_per_mcu, 64)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int16, device=stream.device)
+    elif tuple(out.shape) != shape:
+        raise ValueError(f"out must be {shape}, got {tuple(out.shape)}")
+    _req(out, torch.int16, "out")
+    status = torch.empty(n, dtype=torch.int32, device=stream.device)
+    _call("ew_jpeg_huffman_decode", _ptr(stream), stream.numel(), _ptr(seg_start), _ptr(seg_bytes), _ptr(_aligned(tables, 4)), _ptr(out),
+          _ptr(status), n, V, mcu_rows, mcu_cols, blocks_per_mcu, restart_interval)
+    return out, status
+
+
+def jpeg_idct(coef, qtables, out=None):
+    """coef int16 [V, mcu_rows, mcu_cols, 6 | 3, 64] and qtables uint8 [2,64] (natural order, luminance first), on the device -> the
+    sample planes (y uint8 [V, mcu_rows * m, mcu_cols * m] with m = 16 | 8, cb, cr uint8 [V, mcu_rows * 8, mcu_cols * 8]): dequantised,
+    inverse DCT, + 128, rounded half to even and clamped to 0..255 (ew_jpeg_idct).  `out`: three such tensors to write into."""
+    _req(coef, torch.int16, "coef"); _req(qtables, torch.uint8, "qtables")
+    if coef.ndim != 5 or coef.shape[3] not in (3, 6) or coef.shape[4] != 64 or coef.numel() == 0:
+        raise ValueError(f"coef must be [V, mcu_rows, mcu_cols, 6 | 3, 64], got {tuple(coef.shape)}")
+    if tuple(qtables.shape) != (2, 64):
+        raise ValueError(f"qtables must be [2,64], got {tuple(qtables.shape)}")
+    V, mr, mc, bpm, _ = coef.shape
+    m = 16 if bpm == 6 else 8
+    shapes = ((V, mr * m, mc * m), (V, mr * 8, mc * 8), (V, mr * 8, mc * 8))
+    if out is None:
+        out = tuple(torch.empty(s, dtype=torch.uint8, device=coef.device) for s in shapes)
+    elif len(out) != 3 or any(tuple(o.shape) != s for o, s in zip(out, shapes)):
+        raise ValueError(f"out must be three tensors {shapes}, got {[tuple(o.shape) for o in out]}")
+    for o in out:
+        _req(o, torch.uint8, "out")
+    _call("ew_jpeg_idct", _ptr(_aligned(coef)), _ptr(qtables), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), V, mr, mc, bpm)
+    return tuple(out)
+
+
+def jpeg_planes_to_rgb(planes, H, W, subsampling="4:2:0", out=None):
+    """planes (y, cb, cr) of jpeg_idct -> uint8 [V,H,W,3] on the device: cropped to H x W, the 4:2:0 chroma upsampled with the centred
+    triangle filter, JFIF YCbCr -> RGB in float32 (ew_jpeg_planes_to_rgb).  `out`: a tensor of that shape to write into."""
+    if subsampling not in JPEG_SAMPLING:
+        raise ValueError(f"subsampling must be one of {sorted(JPEG_SAMPLING)}, got {subsampling!r}")
+    mode, mcu, _ = JPEG_SAMPLING[subsampling]
+    if len(planes) != 3:
+        raise ValueError("planes must be (y, cb, cr)")
+    y, cb, cr = (_req(p, torch.uint8, "planes") for p in planes)
+    if not (1 <= H <= 65535 and 1 <= W <= 65535):
+        raise ValueError(f"H and W must be 1..65535, got {H}, {W}")
+    V, mr, mc = y.shape[0], -(-H // mcu), -(-W // mcu)
+    want = ((V, mr * mcu, mc * mcu), (V, mr * 8, mc * 8), (V, mr * 8, mc * 8))
+    if V < 1 or any(tuple(p.shape) != s for p, s in zip((y, cb, cr), want)):
+        raise ValueError(f"the planes of {H} x {W} frames at {subsampling} are {want}, got {[tuple(p.shape) for p in planes]}")
+    if out is None:
+        out = torch.empty(V, H, W, 3, dtype=torch.uint8, device=y.device)
+    elif tuple(out.shape) != (V, H, W, 3):
+        raise ValueError(f"out must be {(V, H, W, 3)}, got {tuple(out.shape)}")
+    _req(out, torch.uint8, "out")
+    _call("ew_jpeg_planes_to_rgb", _ptr(y), _ptr(cb), _ptr(cr), _ptr(out), V, H, W, mode)
+    return out
+
+
+def resize_linear_u8(src, h, w, out=None):
+    """src uint8 [V,H,W,3] on the device -> uint8 [V,h,w,3]: bilinear sampling at half-pixel centres without antialiasing, neighbours
+    clamped to the image, rounded half to even (ew_resize_linear_u8): what cv2.resize(frame, (w, h)) states, unlike resize_aa_u8."""
+    _req(src, torch.uint8, "src")
+    if src.ndim != 4 or src.shape[3] != 3 or src.numel() == 0:
+        raise ValueError(f"src must be a non-empty [V,H,W,3], got {tuple(src.shape)}")
+    if not (isinstance(h, (int, np.integer)) and isinstance(w, (int, np.integer)) and 1 <= h <= 65535 and 1 <= w <= 65535):
+        raise ValueError(f"h and w must be integers 1..65535, got {h!r}, {w!r}")
+    V, H, W, _ = src.shape
+    if out is None:
+        out = torch.empty(V, h, w, 3, dtype=torch.uint8, device=src.device)
+    elif tuple(out.shape) != (V, h, w, 3):
+        raise ValueError(f"out must be {(V, h, w, 3)}, got {tuple(out.shape)}")
+    _req(out, torch.uint8, "out")
+    _call("ew_resize_linear_u8", _ptr(src), _ptr(out), V, H, W, int(h), int(w))
+    return out
+
+
 def equi2pers(equi, rot, Hp, Wp, fov_x):
     _req(equi, torch.uint8, "equi"); _req(rot, torch.float32, "rot")
     F_, He, We, _ = equi.shape

@@ -401,6 +401,50 @@ ew_status ew_jpeg_entropy(const int16_t* coef, uint8_t* slots, int* seg_bytes, l
 ew_status ew_jpeg_pack(const uint8_t* slots, const int* seg_bytes, const long long* seg_offsets, uint8_t* out, long long n_segments,
                        int mcu_rows, size_t slot_bytes, long long out_bytes, void* stream);
 
+/* Baseline JPEG frames decoded on the device (csrc/video_decode.hip; added to ABI 19 without a bump: new symbols only):
+ * the way back from the files above, and from any SOF0 / 8-bit / three-component stream with sampling 22 11 11 or 11 11 11 and one
+ * interleaved scan, to pixels; evoworld_amd/video.py parses the headers and cuts the scan into restart segments on the host.
+ * ew_jpeg_huffman_decode: V frames with identical headers.  scan [scan_bytes] (device) holds their entropy-coded bytes; segment s is
+ *   scan[seg_start[s], seg_start[s] + seg_bytes[s]) without its RSTm marker (seg_start int64, seg_bytes int32, device) and codes
+ *   restart_interval MCUs in scan order, the last segment of a frame the rest (restart_interval 0: the frame is one segment);
+ *   n_segments = V * ceil(mcu_rows * mcu_cols / interval).  tables: 4 x EW_JPEG_HUFF_TABLE_BYTES (device, 4-byte aligned) in the order DC
+ *   luminance, DC chrominance, AC luminance, AC chrominance, each { uint16 look[512]: 9-bit prefix -> length << 8 | symbol, 0 where no
+ *   code of <= 9 bits matches; int32 maxcode[18]: the largest code of length l = 1 .. 16, -1 without one; int32 valoff[18]: index of
+ *   the first symbol of length l minus its first code; uint8 vals[256]: the symbols in code order }, built by the caller from the
+ *   file's DHT segments.  coef int16 [V, mcu_rows, mcu_cols, blocks_per_mcu, 64], each block in zigzag order (the layout
+ *   ew_jpeg_dct_quant writes), is zeroed and then filled; DC predictors start at 0 in every segment, FF 00 is unstuffed.  seg_status
+ *   int32 [n_segments] receives EW_JPEG_SEG_OK or the first thing that stopped the segment, whose remaining coefficients stay 0:
+ *   BAD_CODE (no Huffman code matches, or an EOBn symbol), INDEX (a run or ZRL leads past coefficient 63), SIZE (DC category > 11,
+ *   AC size > 10), EXHAUSTED (the bytes end before the MCUs), LEFTOVER (more than 7 bits unread behind the last MCU), MARKER (an FF
+ *   followed by anything but 00 inside the segment), RANGE (the segment leaves scan_bytes; nothing is read).  No read leaves a
+ *   segment's bytes and no write its blocks.
+ * ew_jpeg_idct: coef -> uint8 sample planes of the padded size, y [V, mcu_rows * m, mcu_cols * m] (m = 16 for blocks_per_mcu 6, 8 for
+ *   3) and cb, cr [V, mcu_rows * 8, mcu_cols * 8] (8-byte aligned): coefficient * qtables entry (qtables uint8 [2][64] on the device,
+ *   natural order, [0] luminance), the inverse of the encoder's orthonormal DCT along the columns and then the rows as fmaf chains,
+ *   + 128, round half to even, clamp to 0 .. 255 (T.81's 8-bit sample).
+ * ew_jpeg_planes_to_rgb: the planes of H x W frames -> rgb uint8 [V,H,W,3]: for EW_JPEG_420 the chroma planes upsampled with the centred
+ *   triangle filter (3/4, 1/4 per axis, taps clamped to the padded plane), then R = Y + 1.402 Cr', G = Y - 0.344136286 Cb' - 0.714136286
+ *   Cr', B = Y + 1.772 Cb' (Cb' = Cb - 128, Cr' = Cr - 128) in float32, round half to even, clamp.
+ * ew_resize_linear_u8: src [V,H,W,3] -> dst [V,h,w,3], bilinear without antialiasing: source position (d + 0.5) * n_src / n_dst - 0.5,
+ *   neighbours clamped to the image, float32 weights, round half to even (what cv2.resize(frame, (w, h)) states; not ew_resize_aa_u8). */
+#define EW_JPEG_HUFF_TABLE_BYTES 1424
+#define EW_JPEG_SEG_OK 0
+#define EW_JPEG_SEG_BAD_CODE 1
+#define EW_JPEG_SEG_INDEX 2
+#define EW_JPEG_SEG_SIZE 3
+#define EW_JPEG_SEG_EXHAUSTED 4
+#define EW_JPEG_SEG_LEFTOVER 5
+#define EW_JPEG_SEG_MARKER 6
+#define EW_JPEG_SEG_RANGE 7
+ew_status ew_jpeg_huffman_decode(const uint8_t* scan, long long scan_bytes, const long long* seg_start, const int* seg_bytes,
+                                 const uint8_t* tables, int16_t* coef, int* seg_status, long long n_segments, int V, int mcu_rows,
+                                 int mcu_cols, int blocks_per_mcu, int restart_interval, void* stream);
+ew_status ew_jpeg_idct(const int16_t* coef, const uint8_t* qtables, uint8_t* y, uint8_t* cb, uint8_t* cr, int V, int mcu_rows, int mcu_cols,
+                       int blocks_per_mcu, void* stream);
+ew_status ew_jpeg_planes_to_rgb(const uint8_t* y, const uint8_t* cb, const uint8_t* cr, uint8_t* rgb, int V, int H, int W, int subsampling,
+                                void* stream);
+ew_status ew_resize_linear_u8(const uint8_t* src, uint8_t* dst, int V, int H, int W, int h, int w, void* stream);
+
 /* Equirect -> perspective bilinear gather (pyequilib Equi2Pers restatement; unified_loop_consistency.py:299-334).
  * equi uint8 [F,He,We,3]; rot [F,3,3] f32 (camera->pano rotation); out uint8 [F,Hp,Wp,3]. */
 ew_status ew_equi2pers(const uint8_t* equi, const float* rot, uint8_t* out, int F, int He, int We, int Hp, int Wp,

@@ -8,7 +8,12 @@ the compressibility of a rendered panorama).  Per sampling (4:2:0, 4:4:4): devic
 (ew_jpeg_dct_quant, ew_jpeg_entropy, ew_jpeg_pack) with the bytes each must move at the least and that figure against the 8 TB/s of HBM;
 a host clock around the synchronised video.encode_jpeg call, device-to-host copy and header assembly included; the compressed size.
 Then the same frames through Pillow's Image.save as JPEG (same quality and sampling) and as PNG on this machine's CPU.  Prints one JSON
-line and, with --out, writes it there.  No gate: these are measurements."""
+line and, with --out, writes it there.  No gate: these are measurements.
+
+  python tools/bench_video.py --decode [--out profiles/video_decode_bench.json]
+
+times the way back on the same clip: the clip's own JPEGs through ew_jpeg_huffman_decode, ew_jpeg_idct, ew_jpeg_planes_to_rgb
+and ew_resize_linear_u8 (to 64 x 64), the synchronised video.decode_jpeg call, and Pillow's decode of the same bytes on the CPU."""
 import argparse
 import io
 import json
@@ -54,6 +59,64 @@ def stage(name, us, nbytes, note):
             "hbm_fraction": round(nbytes / us / 1e6 / HBM_TBS, 4), "note": note}
 
 
+def decode_runs(clip, q, it):
+    """--decode: the four decoder kernels (csrc/video_decode.hip) and the synchronised video.decode_jpeg call on the clip's own JPEGs, per
+    sampling, next to Pillow's decode of the same bytes on this machine's CPU"""
+    import numpy as np
+    from PIL import Image
+
+    from evoworld_amd import ops, video
+    V, H, W, _ = clip.shape
+    P = ops._ptr
+    pixels = V * H * W * 3
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    runs = []
+    for sub in video.SUBSAMPLINGS:
+        mode, mcu, bpm = ops.JPEG_SAMPLING[sub]
+        jpegs = video.encode_jpeg(clip, q, sub)
+        info = video.parse_jpeg(jpegs[0])
+        scan, starts, lengths = video.scan_batch(jpegs, info)
+        base = len(scan)
+        stream, seg_start, seg_bytes = dev(scan), dev(starts), dev(lengths)
+        tables, qt = dev(video.huffman_device_tables(info["huffman"])), dev(np.stack(info["qtables"]).astype(np.uint8))
+        mr, mc = -(-H // mcu), -(-W // mcu)
+        coef, status = ops.jpeg_huffman_decode(stream, seg_start, seg_bytes, tables, V, mr, mc, bpm, info["restart_interval"])
+        assert not bool(status.any())
+        planes = ops.jpeg_idct(coef, qt)
+        rgb = ops.jpeg_planes_to_rgb(planes, H, W, sub)
+        small = ops.resize_linear_u8(rgb, 64, 64)
+        n_seg, plane_bytes = len(lengths), sum(p.numel() for p in planes)
+        stages = [
+            stage("huffman_decode", timed(lambda: ops._call("ew_jpeg_huffman_decode", P(stream), base, P(seg_start), P(seg_bytes), P(tables), P(coef),
+                                                            P(status), n_seg, V, mr, mc, bpm, info["restart_interval"]), it),
+                  base + 2 * coef.numel() * 2, "scan bytes in; coefficients zeroed (memset), then written"),
+            stage("idct", timed(lambda: ops._call("ew_jpeg_idct", P(coef), P(qt), P(planes[0]), P(planes[1]), P(planes[2]), V, mr, mc, bpm), it),
+                  coef.numel() * 2 + plane_bytes, "int16 coefficients in, uint8 sample planes out"),
+            stage("planes_to_rgb", timed(lambda: ops._call("ew_jpeg_planes_to_rgb", P(planes[0]), P(planes[1]), P(planes[2]), P(rgb), V, H, W, mode), it),
+                  plane_bytes + pixels, "sample planes in, pixels out"),
+            stage("resize_linear_64", timed(lambda: ops._call("ew_resize_linear_u8", P(rgb), P(small), V, H, W, 64, 64), it),
+                  4 * small.numel() + small.numel(), "four taps per output value in, 64 x 64 out"),
+        ]
+        torch.cuda.synchronize()
+        wall = []
+        for _ in range(max(3, it // 2)):
+            t0 = time.perf_counter()
+            video.decode_jpeg(jpegs)
+            torch.cuda.synchronize()
+            wall.append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        for j in jpegs:
+            Image.open(io.BytesIO(j)).convert("RGB").load()
+        pillow_ms = (time.perf_counter() - t0) * 1e3
+        us = stages[0]["us"]
+        runs.append({"subsampling": sub, "stages": stages, "kernels_us": round(sum(s["us"] for s in stages[:3]), 1),
+                     "decode_jpeg_wall_ms": round(min(wall) * 1e3, 2), "pillow_decode_cpu_ms": round(pillow_ms, 1), "scan_bytes": base,
+                     "segments": n_seg, "longest_segment_bytes": int(lengths.max()), "mean_segment_bytes": round(float(lengths.mean()), 1),
+                     "huffman_ns_per_byte_of_the_longest_segment": round(us * 1e3 / int(lengths.max()), 2),
+                     "huffman_lanes_in_flight": n_seg, "coef_bytes": coef.numel() * 2})
+    return runs
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     p.add_argument("--iters", type=int, default=10)
@@ -62,12 +125,28 @@ def main(argv=None):
     p.add_argument("--width", type=int, default=1024)
     p.add_argument("--quality", type=int, default=90)
     p.add_argument("--out", type=str, default=None)
+    p.add_argument("--decode", action="store_true", help="time the decoder (csrc/video_decode.hip) on the same clip instead of the encoder")
     args = p.parse_args(argv)
     from PIL import Image
 
     from evoworld_amd import ops, video
     V, H, W, q, it = args.frames, args.height, args.width, args.quality, args.iters
     clip = synthetic_clip(V, H, W)
+    if args.decode:
+        rec = {"tool": "bench_video --decode", "device": torch.cuda.get_device_name(0), "frames": V, "height": H, "width": W, "quality": q,
+               "iters": it, "pixel_bytes": V * H * W * 3, "hbm_TBps": HBM_TBS, "device_runs": decode_runs(clip, q, it),
+               "note": "device events around whole kernel calls; decode_jpeg_wall_ms is the best synchronised call with the host's header parse "
+                       "and segment table, the upload of the scan bytes and the status read-back; pillow_decode_cpu_ms is one single-threaded "
+                       "pass over the same bytes on the host.  The Huffman kernel runs one lane per restart segment, 4 lanes per workgroup: "
+                       "its time is the serial walk of the longest segment's bits (dependent byte loads, a table lookup and a scattered 2-byte "
+                       "store per symbol), not bandwidth; huffman_ns_per_byte_of_the_longest_segment states that latency.  No gate."}
+        line = json.dumps(rec)
+        print(line)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as fh:
+                fh.write(line + "\n")
+        return
     P = ops._ptr
     pixels = V * H * W * 3
     runs = []
