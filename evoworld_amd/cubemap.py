@@ -5,6 +5,7 @@
       --size W H resizes frames that are not 2:1 (the model's 1024x576) first, with the Pillow-exact bilinear.
   python -m evoworld_amd.cubemap to-pano --input DIR --output DIR --size W H [--scale_factor 2]
       every NNN_{face}.png set of --input -> NNN.png, a W x H panorama.
+  --device_png (either command) encodes the output files on the device (evoworld_amd.png) instead of by Pillow.
 
 PNG decoding runs on at most 16 threads and is streamed to the device one batch at a time (as metrics.evaluate does); every
 batch is one launch per stage.
@@ -38,6 +39,8 @@ def parse_args(argv=None):
     b.add_argument("--output", required=True)
     b.add_argument("--size", type=int, nargs=2, metavar=("W", "H"), required=True)
     b.add_argument("--scale_factor", type=int, default=2)
+    for p in (a, b):
+        p.add_argument("--device_png", action="store_true", help="encode the output PNG files on the device")
     args = ap.parse_args(argv)
     if args.scale_factor < 1:
         ap.error("--scale_factor must be at least 1")
@@ -53,6 +56,11 @@ def _decode(path):
 def _save(path, arr):
     from PIL import Image
     Image.fromarray(arr).save(path)
+
+
+def _save_on_device(paths, frames_u8):
+    from .png import write_png_files
+    write_png_files(paths, frames_u8.contiguous())
 
 
 def _batches(items, n=BATCH):
@@ -90,6 +98,11 @@ def to_cubemap(args, device="cuda"):
             if args.size is not None:
                 x = RP.resize_u8(x, args.size[1], args.size[0], "bilinear")
             cross, faces = RP.panorama_to_cubemap(x, not args.nearest, args.scale_factor)
+            if args.device_png:
+                _save_on_device([os.path.join(args.output, f"{s}_cubemap.png") for s in batch], cross)
+                for n in FACES:
+                    _save_on_device([os.path.join(args.output, f"{s}_{n}.png") for s in batch], faces[n])
+                continue
             out = [(os.path.join(args.output, f"{s}_cubemap.png"), c) for s, c in zip(batch, cross.cpu().numpy())]
             for n in FACES:
                 out += [(os.path.join(args.output, f"{s}_{n}.png"), f) for s, f in zip(batch, faces[n].cpu().numpy())]
@@ -107,6 +120,9 @@ def to_pano(args, device="cuda"):
             faces = {n: _stack(list(pool.map(_decode, [os.path.join(args.input, f"{s}_{n}.png") for s in batch])), batch).to(device)
                      for n in FACES}
             pano = RP.cubemap_to_panorama(faces, args.size[0], args.size[1], args.scale_factor)
+            if args.device_png:
+                _save_on_device([os.path.join(args.output, s + ".png") for s in batch], pano)
+                continue
             list(pool.map(lambda pa: _save(*pa), [(os.path.join(args.output, s + ".png"), p) for s, p in zip(batch, pano.cpu().numpy())]))
     return len(stems)
 

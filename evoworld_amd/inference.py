@@ -354,7 +354,7 @@ class UnifiedLoopConsistencyPipeline:
 
     def process_episode(self, start_image, camera_params, image_latents_fn=None, save_dir=None, pos_scale=0.1,
                         save_segment_frames=False, episode_path=None, export_memory=False, memory_voxel_size=None,
-                        save_video=False, video_fps=10, video_quality=90, **pipe_kw):
+                        save_video=False, video_fps=10, video_quality=90, png_on_device=False, **pipe_kw):
         """start_image float [3,H,W] in [-1,1]; camera_params [P,6] numpy: the UNSCALED RDF poses of camera_poses.txt
         (unified_loop_consistency.py:370-395), used as they are for the target yaws and the reprojection alignment; the
         Navigator / Plücker path gets the copy with xyz * pos_scale that the dataset hands out as batch['cam_traj']
@@ -384,7 +384,9 @@ class UnifiedLoopConsistencyPipeline:
         With save_video and a save_dir, navigated.avi holds all generated frames -- the very uint8 tensor that is returned -- as
         Motion-JPEG encoded on the device (evoworld_amd.video; video_fps, video_quality), and, for an `episode_path` with ground-truth
         panoramas, original.avi holds the frames load_gt_window_u8 yields for the same poses (panorama ids 1 .. N, frame for frame
-        beside navigated.avi): the pair calculate_scores.py loads per episode (there as .mp4).  The returned frames do not depend on it."""
+        beside navigated.avi): the pair calculate_scores.py loads per episode (there as .mp4).  The returned frames do not depend on it.
+        With png_on_device (opt-in) every PNG named above -- the per-segment dumps and the memory panoramas -- is encoded on the device
+        (evoworld_amd.png): same names, the same pixels for any decoder, other file bytes than Pillow's."""
         from . import ops
         dev = start_image.device
         camera_params = np.asarray(camera_params, dtype=np.float64)
@@ -423,18 +425,18 @@ class UnifiedLoopConsistencyPipeline:
             if all_u8 is not None:
                 frames_u8 = frames_u8[1:]                                               # drop the duplicated first frame (:427-429)
             if save_dir and save_segment_frames:                                        # :432-435, file index continues across segments
-                _save_u8_frames(frames_u8, os.path.join(save_dir, f"predictions_{seg}"), seg * (self.num_frames - 1))
+                _save_u8_frames(frames_u8, os.path.join(save_dir, f"predictions_{seg}"), seg * (self.num_frames - 1), png_on_device)
                 if episode_path is not None:                                            # :437-439
                     from .dataset import load_gt_window_u8
                     gt = load_gt_window_u8(episode_path, start_idx, end_idx, self.height, self.width, dev, len(camera_params))
                     if gt is not None:
                         _save_u8_frames(ops.gt_dump_map_u8(gt), os.path.join(save_dir, f"predictions_gt_{seg}"),
-                                        seg * (self.num_frames - 1))
+                                        seg * (self.num_frames - 1), png_on_device)
             all_u8 = frames_u8 if all_u8 is None else torch.cat([all_u8, frames_u8], dim=0)
             if seg < self.num_segments - 1:
                 pers, target_yaws = self.convert_pano_to_pers(all_u8, camera_params, seg)
                 if save_dir and save_segment_frames:
-                    _save_u8_frames(pers, os.path.join(save_dir, f"perspective_look_at_center_{seg}"))   # :449-453
+                    _save_u8_frames(pers, os.path.join(save_dir, f"perspective_look_at_center_{seg}"), 0, png_on_device)   # :449-453
                 temp_cam = camera_params.copy()
                 s = max(0, end_idx - len(target_yaws))
                 temp_cam[s:end_idx, 4] = target_yaws[: end_idx - s]                        # :456-459
@@ -448,7 +450,7 @@ class UnifiedLoopConsistencyPipeline:
                 panos = RP.predictions_to_target_view(preds, poses.numpy(), conf_thres=50.0, prediction_mode="depth_unproject",
                                                       num_target_view=24, outdir=outdir, cubemap_renderer=_Sized(self.renderer, self.pano_size),
                                                       return_device_tensor=True, save_png=bool(save_dir), voxel_size=memory_voxel_size,
-                                                      export_glb=glb)
+                                                      export_glb=glb, png_on_device=png_on_device)
                 mem24 = RP.memory_to_pixel_values(panos, self.height, self.width)           # [24,3,H,W]
                 memory = torch.cat([start_image[None], mem24], dim=0)                      # [episode frame 1] + 24 reprojected (:277-279)
         self.last_frames_u8 = all_u8
@@ -486,8 +488,13 @@ def check_path_episode(run_lengths, n_poses, num_segments, num_frames=25):
                              f"but the episode has {n_poses} poses")
 
 
-def _save_u8_frames(u8_hwc, d, start=0):
-    """NNN.png (1-based, offset by `start`) dumps of uint8 [F,H,W,3] frames (unified_loop_consistency.py:104-108,432-453)"""
+def _save_u8_frames(u8_hwc, d, start=0, png_on_device=False):
+    """NNN.png (1-based, offset by `start`) dumps of uint8 [F,H,W,3] frames (unified_loop_consistency.py:104-108,432-453);
+    png_on_device: encoded by evoworld_amd.png instead of Pillow"""
+    if png_on_device:
+        from .png import write_png_frames
+        write_png_frames(d, u8_hwc, start)
+        return
     from PIL import Image
     os.makedirs(d, exist_ok=True)
     for i, f in enumerate(u8_hwc.cpu().numpy()):
@@ -498,5 +505,5 @@ class _Sized:
     def __init__(self, cr, pano_size):
         self.cr, self.pano_size = cr, pano_size
 
-    def render_cubemaps_to_panoramas(self, v, c, target, n, outdir):
-        return self.cr.render_cubemaps_to_panoramas(v, c, target, n, outdir, width=self.pano_size[1], height=self.pano_size[0])
+    def render_cubemaps_to_panoramas(self, v, c, target, n, outdir, **kw):
+        return self.cr.render_cubemaps_to_panoramas(v, c, target, n, outdir, width=self.pano_size[1], height=self.pano_size[0], **kw)

@@ -589,6 +589,102 @@ def jpeg_pack(slots, seg_bytes, mcu_rows):
     return stream, frame_bytes
 
 
+PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": _lib.EW_PNG_FILTER_ADAPTIVE}
+PNG_HIST_COLS = _lib.EW_PNG_HIST_COLS                    # 286 literal/length symbols, then 30 distance codes
+PNG_SEGMENT_TARGET = 32768                               # bytes: the default rows_per_segment keeps a segment at or below it
+
+
+def png_rows_per_segment(H, W, rows_per_segment=None):
+    """The rows of one deflate segment: as given (at least 1, at most H), else the most whole filtered rows (1 + 3 W bytes each) that
+    stay within 32 KiB, at least 1."""
+    if rows_per_segment is None:
+        rows_per_segment = max(1, PNG_SEGMENT_TARGET // (1 + 3 * W))
+    if not (isinstance(rows_per_segment, int) and rows_per_segment >= 1):
+        raise ValueError(f"rows_per_segment must be an integer >= 1, got {rows_per_segment!r}")
+    return min(rows_per_segment, H)
+
+
+def _png_geometry(V, H, W, rows_per_segment):
+    """-> (rows per segment, segments per frame, bytes of a full segment) after the checks every PNG entry shares"""
+    if not (1 <= V <= 65535 and 1 <= H <= 65535 and 1 <= W <= 65535):
+        raise ValueError(f"V, H and W must be 1..65535, got {V}, {H}, {W}")
+    rps = png_rows_per_segment(H, W, rows_per_segment)
+    spf = -(-H // rps)
+    if V * spf >= 1 << 31:
+        raise ValueError(f"n_segments = {V * spf} must be below 2^31")
+    if rps * (1 + 3 * W) > _lib.EW_PNG_MAX_SEGMENT_BYTES:
+        raise ValueError(f"a segment of {rps} rows of {1 + 3 * W} bytes exceeds {_lib.EW_PNG_MAX_SEGMENT_BYTES} bytes")
+    return rps, spf, rps * (1 + 3 * W)
+
+
+def _png_filtered(filtered):
+    if filtered.ndim != 3 or filtered.shape[2] < 4 or (filtered.shape[2] - 1) % 3 or filtered.numel() == 0:
+        raise ValueError(f"filtered must be [V,H,1+3W], got {tuple(filtered.shape)}")
+    return filtered.shape[0], filtered.shape[1], (filtered.shape[2] - 1) // 3
+
+
+def png_filter(frames_u8, filter="adaptive", rows_per_segment=None):
+    """frames uint8 [V,H,W,3] on the device -> (filtered uint8 [V,H,1+3W]: every row behind its PNG filter type; adler int32
+    [n_segments, 2]: the Adler-32 halves of every segment of rows_per_segment rows) (ew_png_filter).  filter: "none" |
+    "sub" | "up" | "average" | "paeth" (or 0..4) forces a type, "adaptive" picks per row by the minimum sum of absolute differences."""
+    if frames_u8.dtype != torch.uint8:                   # the argument checks come before the device check: they need no GPU
+        raise TypeError(f"frames_u8: expected {torch.uint8}, got {frames_u8.dtype}")
+    if frames_u8.ndim != 4 or frames_u8.shape[3] != 3:
+        raise ValueError(f"frames_u8 must be [V,H,W,3], got {tuple(frames_u8.shape)}")
+    mode = PNG_FILTERS.get(filter) if isinstance(filter, str) else (filter if isinstance(filter, int) and 0 <= filter <= 4 else None)
+    if mode is None:
+        raise ValueError(f"filter must be one of {sorted(PNG_FILTERS)} or 0..4, got {filter!r}")
+    V, H, W, _ = frames_u8.shape
+    rps, spf, _ = _png_geometry(V, H, W, rows_per_segment)
+    _req(frames_u8, torch.uint8, "frames_u8")
+    filtered = torch.empty(V, H, 1 + 3 * W, dtype=torch.uint8, device=frames_u8.device)
+    adler = torch.empty(V * spf, 2, dtype=torch.int32, device=frames_u8.device)
+    _call("ew_png_filter", _ptr(frames_u8), _ptr(filtered), _ptr(adler), V, H, W, mode, rps)
+    return filtered, adler
+
+
+def png_lz77(filtered, rows_per_segment=None):
+    """filtered uint8 [V,H,1+3W] (png_filter) -> (tokens int32 [n_segments, segment bytes], n_tokens int32 [n_segments], hist int32
+    [n_segments, 316]) on the device (ew_png_lz77).  A token's 32 bits: a literal byte, or bit 31 | distance - 1 << 8 | length - 3; a
+    token slot holds the worst case of one token per byte."""
+    V, H, W = _png_filtered(filtered)
+    rps, spf, seg_bytes = _png_geometry(V, H, W, rows_per_segment)
+    _req(filtered, torch.uint8, "filtered")
+    n = V * spf
+    tokens = torch.empty(n, seg_bytes, dtype=torch.int32, device=filtered.device)
+    n_tokens = torch.empty(n, dtype=torch.int32, device=filtered.device)
+    hist = torch.empty(n, PNG_HIST_COLS, dtype=torch.int32, device=filtered.device)
+    _call("ew_png_lz77", _ptr(filtered), _ptr(tokens), _ptr(n_tokens), _ptr(hist), V, H, W, rps, seg_bytes)
+    return tokens, n_tokens, hist
+
+
+def png_emit(tokens, n_tokens, filtered, seg_mode, seg_offsets, seg_bytes, luts, headers, header_bits, out, rows_per_segment=None):
+    """The segments' final bytes into `out` uint8 [bytes] (ew_png_emit): segment s to out[seg_offsets[s] : + seg_bytes[s]] (int64), coded
+    with its frame's luts int32 [V,316] / headers uint8 [V,n] / header_bits int32 [V] or, where seg_mode int32 says so, as stored
+    blocks.  A segment whose range leaves `out` is skipped.  Returns out."""
+    V, H, W = _png_filtered(filtered)
+    rps, spf, sb = _png_geometry(V, H, W, rows_per_segment)
+    _req(filtered, torch.uint8, "filtered")
+    n = V * spf
+    for t, dt, name, shape in ((tokens, torch.int32, "tokens", None), (n_tokens, torch.int32, "n_tokens", (n,)),
+                               (seg_mode, torch.int32, "seg_mode", (n,)), (seg_offsets, torch.int64, "seg_offsets", (n,)),
+                               (seg_bytes, torch.int64, "seg_bytes", (n,)), (luts, torch.int32, "luts", (V, PNG_HIST_COLS)),
+                               (headers, torch.uint8, "headers", None), (header_bits, torch.int32, "header_bits", (V,)),
+                               (out, torch.uint8, "out", None)):
+        _req(t, dt, name)
+        if shape is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+    if tokens.ndim != 2 or tokens.shape[0] != n or tokens.shape[1] < sb:
+        raise ValueError(f"tokens must be [{n}, >= {sb}], got {tuple(tokens.shape)}")
+    if headers.ndim != 2 or headers.shape[0] != V or headers.shape[1] < 1:
+        raise ValueError(f"headers must be [{V}, n], got {tuple(headers.shape)}")
+    if out.ndim != 1 or out.numel() < 1:
+        raise ValueError(f"out must be a non-empty 1-D tensor, got {tuple(out.shape)}")
+    _call("ew_png_emit", _ptr(tokens), _ptr(n_tokens), _ptr(filtered), _ptr(seg_mode), _ptr(seg_offsets), _ptr(seg_bytes), _ptr(luts),
+          _ptr(headers), _ptr(header_bits), headers.shape[1], _ptr(out), out.numel(), V, H, W, rps, tokens.shape[1])
+    return out
+
+
 JPEG_SEG_STATUS = {_lib.EW_JPEG_SEG_BAD_CODE: "no Huffman code matches the bits (or an EOBn symbol of a progressive scan)",
                    _lib.EW_JPEG_SEG_INDEX: "a zero run leads past coefficient 63",
                    _lib.EW_JPEG_SEG_SIZE: "a DC category above 11 or an AC size above 10",

@@ -243,11 +243,15 @@ class CubemapRenderer:
         return faces                                                             # uint8 [V,6,res,res,3|4], FACE_ORDER
 
     def render_cubemaps_to_panoramas(self, vertices, colors, target_extrinsic, num_target_view=24, outdir=None,
-                                     width=2000, height=1000):
+                                     width=2000, height=1000, png_on_device=False):
         faces = self.render_cubemaps(vertices, colors, target_extrinsic, face_channels=4)   # RGBX words: aligned gathers
         lut = build_cube2equi_lut(width, height, self.face_res).to(vertices.device)
         panos = ops.cube2equi_gather(faces, lut, height, width)                   # uint8 [V,H,W,3] on the device
-        if outdir:
+        if outdir and png_on_device:                                             # opt-in: the same files, encoded on the device
+            from .png import write_png_files
+            os.makedirs(outdir, exist_ok=True)
+            write_png_files([os.path.join(outdir, f"{i:02}.png") for i in range(panos.shape[0])], panos)
+        elif outdir:
             os.makedirs(outdir, exist_ok=True)
             from PIL import Image
             for i, p in enumerate(panos.cpu().numpy()):
@@ -260,12 +264,13 @@ def predictions_to_target_view(predictions, camera_pose, conf_thres=50.0, filter
                                show_cam=True, mask_sky=False, target_dir=None, image_subdir=None,
                                prediction_mode="Predicted Pointmap", num_target_view=24, outdir="demo_pyrender_render",
                                only_render_last_24_frame=False, return_device_tensor=False, save_png=True, voxel_size=None,
-                               export_glb=None):
+                               export_glb=None, png_on_device=False):
     """VGGT predictions -> 24 reprojected panoramas uint8 [24,1000,2000,3] (:1216-1282).  `outdir`'s `_{segment}` suffix
     selects the target poses, as in the reference (:487-492).
     voxel_size (opt-in): the filtered cloud is thinned by ops.voxel_downsample between the filter and the splat (one averaged point
     per occupied voxel).  export_glb (opt-in): a path; the cloud that is rendered -- after the downsample, when there is one -- is
-    also written there as a GLB with the predictions' cameras (memory.SceneMemory; show_cam as given), without a second filter pass."""
+    also written there as a GLB with the predictions' cameras (memory.SceneMemory; show_cam as given), without a second filter pass.
+    png_on_device (opt-in): the save_png files are encoded on the device (evoworld_amd.png) instead of by Pillow."""
     if not isinstance(predictions, dict):
         raise ValueError("predictions must be a dictionary")
     pp = point_processor or PointCloudProcessor()
@@ -283,7 +288,8 @@ def predictions_to_target_view(predictions, camera_pose, conf_thres=50.0, filter
     if export_glb is not None:
         SceneMemory.from_cloud(v, c, predictions["extrinsic"], show_cam).to_glb(export_glb)
     target = sb.align_extrinsics(camera_pose, predictions["extrinsic"], num_target_view, outdir, only_render_last_24_frame)
-    panos = cr.render_cubemaps_to_panoramas(v, c, target, num_target_view, outdir if save_png else None)
+    kw = {"png_on_device": True} if png_on_device else {}                      # a caller's renderer without the option is left as it is
+    panos = cr.render_cubemaps_to_panoramas(v, c, target, num_target_view, outdir if save_png else None, **kw)
     return panos if return_device_tensor else panos.cpu().numpy()
 
 

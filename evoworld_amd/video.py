@@ -563,7 +563,11 @@ def _cli_encode(args):
 def _cli_extract(args):
     fps, width, height, frames = read_avi(args.input)
     os.makedirs(args.output, exist_ok=True)
-    if args.format == "png":
+    if args.format == "png" and args.device_png:
+        if frames:
+            from .png import write_png_frames
+            write_png_frames(args.output, decode_jpeg(frames))
+    elif args.format == "png":
         from PIL import Image
         if frames:
             for i, f in enumerate(decode_jpeg(frames).cpu().numpy()):
@@ -601,6 +605,7 @@ def parse_arguments(argv=None):
     x.add_argument("--input", required=True)
     x.add_argument("--output", required=True)
     x.add_argument("--format", choices=("jpg", "png"), default="jpg")
+    x.add_argument("--device_png", action="store_true", help="with --format png: encode the files on the GPU (evoworld_amd.png)")
     x.set_defaults(run=_cli_extract)
     s = sub.add_parser("scores", help="PSNR / SSIM (LPIPS, FVD with their weights) of navigated.avi against original.avi over the "
                                       "sub-folders of a folder, as the reference's calculate_scores.py")

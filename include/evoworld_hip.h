@@ -445,6 +445,46 @@ ew_status ew_jpeg_planes_to_rgb(const uint8_t* y, const uint8_t* cb, const uint8
                                 void* stream);
 ew_status ew_resize_linear_u8(const uint8_t* src, uint8_t* dst, int V, int H, int W, int h, int w, void* stream);
 
+/* PNG files encoded on the device (csrc/png.hip; added to ABI 20 without a bump: new symbols only).  The frame dumps of
+ * the reference's --save_frames runs go through PIL's Image.save on one host thread; here only a frame's compressed bytes leave the
+ * GPU and evoworld_amd/png.py adds the chunk framing.  The stream: 8-bit RGB, colour type 2, no interlace; the filtered scanlines
+ * (a type byte, then 3 W bytes per row) of a frame are cut into segments of rows_per_segment whole rows (a value above H means H; the
+ * last segment of a frame may be ragged; segs_per_frame = ceil(H / rows_per_segment), n_segments = V * segs_per_frame, below 2^31;
+ * a segment holds at most EW_PNG_MAX_SEGMENT_BYTES bytes).  Every segment is deflated on its own -- no back-reference reaches before
+ * its first byte -- as one dynamic-Huffman block followed by an empty stored block (000, pad, 00 00 FF FF), so that the next segment
+ * starts on a byte; a frame's last segment sets BFINAL on its block instead and pads with zero bits.  V, H, W 1 .. 65535.
+ * ew_png_filter: frames uint8 [V,H,W,3] -> filtered uint8 [V,H,1+3W].  filter_mode 0 .. 4 forces None / Sub / Up / Average / Paeth
+ *   (RFC 2083 section 6; bpp = 3, bytes left of the first pixel and above row 0 are 0, Average is floor((a + b) / 2), Paeth breaks ties
+ *   in the order a, b, c); EW_PNG_FILTER_ADAPTIVE picks per row the type with the smallest sum of cost(v) = v < 128 ? v : 256 - v over
+ *   the row's filtered bytes (libpng's minimum sum of absolute differences), a tie going to the lowest type.  The frames are read as
+ *   words when they are 4-byte aligned and 3 W % 4 == 0.  adler int32 [n_segments, 2] receives the Adler-32 halves (a, b) of every
+ *   segment's filtered bytes, each on its own (a starts at 1); the caller combines them: A = A1 + A2 - 1, B = B1 + B2 + len2 (A1 - 1).
+ * ew_png_lz77: filtered -> tokens uint32 [n_segments, token_stride] (token_stride >= the bytes of a full segment: one token per byte
+ *   at worst), n_tokens int32 [n_segments], hist int32 [n_segments, 286 + 30].  A literal is its byte in bits 0 - 7; a match has bit 31
+ *   set, length - 3 in bits 0 - 7 and distance - 1 in bits 8 - 22, length 3 .. 258, distance 1 .. min(32768, position in the segment).
+ *   hist counts the segment's literal/length symbols (the end-of-block symbol 256 once) and, from column 286 on, its distance codes.
+ *   Greedy parse, one probe of a 3-byte hash per position.
+ * ew_png_emit: the segments' final bytes.  Segment s goes to out[seg_offsets[s], seg_offsets[s] + seg_bytes[s]) (int64, device; the
+ *   caller's exact sizes and their exclusive scan) and nowhere else; one whose range leaves out_bytes is skipped.  seg_mode int32:
+ *   EW_PNG_SEG_CODED writes the tokens with the frame's codes -- luts uint32 [V, 286 + 30]: bit-reversed code | length << 16 per
+ *   literal/length symbol, then per distance code; headers uint8 [V, header_stride] and header_bits int32 [V]: the block header
+ *   (BFINAL = 0, BTYPE = 10, HLIT, HDIST, HCLEN, the code-length code and the coded lengths) as an LSB-first bit string --,
+ *   EW_PNG_SEG_STORED copies the segment's filtered bytes as stored blocks of at most 65535 bytes (5 bytes of overhead each, BFINAL on
+ *   a frame's last).  Extra bits go LSB-first.  No atomics anywhere: two calls return identical bytes. */
+#define EW_PNG_FILTER_ADAPTIVE 5
+#define EW_PNG_SEG_CODED 0
+#define EW_PNG_SEG_STORED 1
+#define EW_PNG_HIST_COLS 316
+#define EW_PNG_MAX_SEGMENT_BYTES 1073741824
+ew_status ew_png_filter(const uint8_t* frames, uint8_t* filtered, int* adler, int V, int H, int W, int filter_mode, int rows_per_segment,
+                        void* stream);
+ew_status ew_png_lz77(const uint8_t* filtered, uint32_t* tokens, int* n_tokens, int* hist, int V, int H, int W, int rows_per_segment,
+                      long long token_stride, void* stream);
+ew_status ew_png_emit(const uint32_t* tokens, const int* n_tokens, const uint8_t* filtered, const int* seg_mode,
+                      const long long* seg_offsets, const long long* seg_bytes, const uint32_t* luts, const uint8_t* headers,
+                      const int* header_bits, int header_stride, uint8_t* out, long long out_bytes, int V, int H, int W,
+                      int rows_per_segment, long long token_stride, void* stream);
+
 /* Equirect -> perspective bilinear gather (pyequilib Equi2Pers restatement; unified_loop_consistency.py:299-334).
  * equi uint8 [F,He,We,3]; rot [F,3,3] f32 (camera->pano rotation); out uint8 [F,Hp,Wp,3]. */
 ew_status ew_equi2pers(const uint8_t* equi, const float* rot, uint8_t* out, int F, int He, int We, int Hp, int Wp,

@@ -9,6 +9,7 @@ Same flags as the reference.  Additions (all optional):
   --num_inference_steps N    (reference fixes 25)
   --height/--width           (reference fixes 576x1024)
   --save_video               navigated.avi / original.avi per episode (Motion-JPEG, encoded on the device); --video_fps, --video_quality
+  --device_png               the --save_frames PNG files are encoded on the device (evoworld_amd.png): same names and pixels, other bytes
   --qkv_fp8                  fp8 (e4m3) q / k / v projections in the U-Net's self-attention (BASELINE.json configs[4]); default off = fp16
 
 Launch on N GPUs:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 unified_loop_consistency.py ...
@@ -52,6 +53,8 @@ def parse_arguments(argv=None):
                    help="write navigated.avi (and original.avi for an episode with panoramas): Motion-JPEG encoded on the device")
     p.add_argument("--video_fps", type=float, default=10, help="frame rate of the --save_video files")
     p.add_argument("--video_quality", type=int, default=90, help="JPEG quality (1..100) of the --save_video files")
+    p.add_argument("--device_png", action="store_true",
+                   help="encode the --save_frames PNG files on the device (same names, same pixels, file bytes other than Pillow's)")
     return p.parse_args(argv)
 
 
@@ -91,7 +94,11 @@ def synthetic_path_episode(num_segments, extra=8, step=0.4):
     return np.asarray(rows, np.float64)
 
 
-def _save_frames_u8(u8_hwc, d, start=0):
+def _save_frames_u8(u8_hwc, d, start=0, device_png=False):
+    if device_png:
+        from evoworld_amd.png import write_png_frames
+        write_png_frames(d, u8_hwc, start)
+        return
     from PIL import Image
     os.makedirs(d, exist_ok=True)
     for i, f in enumerate(u8_hwc.cpu().numpy()):
@@ -132,8 +139,9 @@ def run_single_segment(args, ep, pipe, unet, dev, out_dir, synthetic):
     torch.cuda.synchronize()
     dt = time.time() - t0
     if args.save_frames:
-        _save_frames_u8(frames_u8, os.path.join(out_dir, "predictions"))                  # forward_evoworld.save_frames
-        _save_frames_u8(ops.f32_chw_to_u8_hwc(batch["pixel_values"][0].float().contiguous()), os.path.join(out_dir, "predictions_gt"))
+        _save_frames_u8(frames_u8, os.path.join(out_dir, "predictions"), 0, args.device_png)     # forward_evoworld.save_frames
+        _save_frames_u8(ops.f32_chw_to_u8_hwc(batch["pixel_values"][0].float().contiguous()), os.path.join(out_dir, "predictions_gt"), 0,
+                        args.device_png)
     if args.save_video:                                                                   # the clip and its ground truth, as process_episode names them
         from evoworld_amd.video import write_video
         write_video(os.path.join(out_dir, "navigated.avi"), frames_u8, fps=args.video_fps, quality=args.video_quality)
@@ -167,11 +175,12 @@ def run_episode(args, ep, pipe, unet, dev, out_dir, synthetic):
     frames = loop.process_episode(start, cam, save_dir=out_dir if args.save_frames or args.export_glb or args.save_video else None,
                                   save_segment_frames=args.save_frames, episode_path=None if synthetic else ep,
                                   export_memory=args.export_glb, memory_voxel_size=args.memory_voxel_size,
-                                  save_video=args.save_video, video_fps=args.video_fps, video_quality=args.video_quality)
+                                  save_video=args.save_video, video_fps=args.video_fps, video_quality=args.video_quality,
+                                  png_on_device=args.device_png)
     torch.cuda.synchronize()
     dt = time.time() - t0
     if args.save_frames:
-        _save_frames_u8(loop.last_frames_u8, os.path.join(out_dir, "predictions"))
+        _save_frames_u8(loop.last_frames_u8, os.path.join(out_dir, "predictions"), 0, args.device_png)
     return {"episode": os.path.basename(ep), "frames": int(frames.shape[0]), "seconds": round(dt, 3)}
 
 
