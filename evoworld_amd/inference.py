@@ -26,6 +26,7 @@ import torch
 
 from . import reprojection as RP
 from .geometry import UNITY_TO_OPENCV, xyz_euler_to_four_by_four_matrix_batch, xyz_euler_to_three_by_four_matrix_batch
+from .mvs import call_depth_model
 from .plucker import equirectangular_to_ray, ray_c2w_to_plucker
 
 logger = logging.getLogger(__name__)
@@ -333,7 +334,8 @@ class Navigator:
 class UnifiedLoopConsistencyPipeline:
     """process_episode of unified_loop_consistency.py:398-492 with every stage on the device.
     `frames_from_latents(latents[1,T,4,h,w]) -> float [T,3,H,W] in [-1,1]` stands for the VAE decode (row N1);
-    `depth_model(persp_u8 [F,384,512,3]) -> dict(depth, depth_conf, images, extrinsic, intrinsic)` stands for VGGT (row N4)."""
+    `depth_model(persp_u8 [F,384,512,3]) -> dict(depth, depth_conf, images, extrinsic, intrinsic)` stands for VGGT (row N4); one that
+    declares `wants_view_poses = True` (evoworld_amd.mvs.PlaneSweepDepth) is called with `view_w2c=mvs.view_poses(...)` as well."""
 
     def __init__(self, pipeline, depth_model, frames_from_latents=None, height=576, width=1024, num_frames=25, num_segments=3,
                  num_inference_steps=25, pano_size=(1000, 2000), face_res=512, curve_path=True):
@@ -440,7 +442,7 @@ class UnifiedLoopConsistencyPipeline:
                 temp_cam = camera_params.copy()
                 s = max(0, end_idx - len(target_yaws))
                 temp_cam[s:end_idx, 4] = target_yaws[: end_idx - s]                        # :456-459
-                preds = self.depth_model(pers)
+                preds = call_depth_model(self.depth_model, pers, camera_params, seg)    # a stage that wants them also gets the views' poses
                 poses = xyz_euler_to_four_by_four_matrix_batch(torch.tensor(temp_cam, dtype=torch.float32), relative=True)
                 outdir = os.path.join(save_dir or "", f"rendered_panorama_vggt_open3d_{seg}")
                 glb = None

@@ -1,0 +1,251 @@
+"""Plane-sweep multi-view stereo: a weight-free depth stage for the N-segment loop.
+
+The reference gets depth, confidence and cameras from VGGT-1B (unified_loop_consistency.py:336-368).  In this loop the cameras are
+known -- the perspective views fed to the depth stage are cut from the generated panoramas at poses the episode file states -- so depth
+can come from geometry instead of a network: every view is swept against its neighbours over planes of constant depth
+(ew_mvs_plane_sweep), the winners are cross-checked between views (ew_mvs_consistency), and the result has the duck type of the
+depth network's predictions.  It is opt-in (`--depth_stage mvs`); how it compares with VGGT is not measured.
+
+  view_poses       the world->camera matrices of the views `UnifiedLoopConsistencyPipeline.convert_pano_to_pers` produces
+  sweep_setup      sources per view, inverse depths, homographies (host, float64)
+  PlaneSweepDepth  the callable: uint8 views [F,H,W,3] on the device -> predictions dict (device tensors)
+  python -m evoworld_amd.mvs cloud --frames DIR --poses camera_poses.txt --segment K --output scene.ply|.glb
+"""
+import argparse
+import json
+import os
+import sys
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+from .geometry import xyz_euler_to_four_by_four_matrix_batch
+
+
+def pinhole(height, width):
+    """float64 [3,3]: the 90-degree pinhole of the views (f = W / 2, centre (W / 2, H / 2)), as the stand-in states it and
+    ew_equi2pers renders it (pixel index x <-> ray ((x - W / 2) / f, (y - H / 2) / f, 1))."""
+    f = width / 2.0
+    return np.array([[f, 0, width / 2.0], [0, f, height / 2.0], [0, 0, 1]], np.float64)
+
+
+def view_poses(camera_params, n_frames, segment_id, relative=True):
+    """float64 [F,3,4] world->camera of the perspective views convert_pano_to_pers cuts from the first n_frames panoramas, in the
+    convention ew_depth_unproject expects (x right, y down, z forward; Xc = R Xw + t).  camera_params: the UNSCALED [P,6] poses of
+    camera_poses.txt, as the alignment uses them.  A view's camera is its panorama's camera (xyz_euler_to_four_by_four_matrix_batch)
+    turned by the view's own rotation, Equi2Pers.rotation at the yaw calculate_target_yaws gives -- the float32 camera->panorama
+    matrix ew_equi2pers is handed.  relative: in the frame of the first VIEW (its matrix is the identity), which is what a depth
+    network reports; otherwise in the frame the poses are given in."""
+    from . import reprojection as RP
+    cam = np.asarray(camera_params, dtype=np.float64)
+    if n_frames < 1 or n_frames > len(cam):
+        raise ValueError(f"n_frames = {n_frames} must be 1 .. {len(cam)} (the poses of the episode)")
+    c2w = xyz_euler_to_four_by_four_matrix_batch(torch.tensor(cam[:n_frames], dtype=torch.float64), relative=False).numpy()
+    yaws = RP.calculate_target_yaws(cam, n_frames, segment_id)
+    for i, y in enumerate(yaws):
+        turn = np.eye(4)
+        turn[:3, :3] = RP.Equi2Pers.rotation({"pitch": 0, "roll": 0, "yaw": float(y)}).astype(np.float64)
+        c2w[i] = c2w[i] @ turn
+    if relative:
+        c2w = np.linalg.inv(c2w[0])[None] @ c2w
+    return np.linalg.inv(c2w)[:, :3, :4]
+
+
+def _w2c_4x4(w2c):
+    w = np.asarray(w2c.detach().cpu() if isinstance(w2c, torch.Tensor) else w2c, dtype=np.float64)
+    if w.ndim != 3 or w.shape[1:] not in ((3, 4), (4, 4)):
+        raise ValueError(f"w2c must be [F,3,4] or [F,4,4], got {w.shape}")
+    E = np.tile(np.eye(4), (len(w), 1, 1))
+    E[:, :3, :4] = w[:, :3, :4]
+    return E
+
+
+def choose_sources(centres, n_src, min_baseline=1e-6):
+    """int32 [F, n_src]: per view the n_src nearest views by index distance (i-1, i+1, i-2, i+2, ...) whose camera centre is more
+    than min_baseline away; a slot that cannot be filled is -1.  At an end of the sequence the slots fill from the one side there is."""
+    F = len(centres)
+    out = np.full((F, n_src), -1, np.int32)
+    for i in range(F):
+        got = 0
+        for d in range(1, F):
+            for j in (i - d, i + d):
+                if 0 <= j < F and got < n_src and np.linalg.norm(centres[j] - centres[i]) > min_baseline:
+                    out[i, got] = j
+                    got += 1
+    return out
+
+
+def sweep_setup(w2c, K, n_src, D, z_near=None, z_far=None, min_baseline=1e-6):
+    """What ew_mvs_plane_sweep and ew_mvs_consistency need, computed on the host in float64 (the *_f32 members are the uploads):
+      src_index [F,n_src] int32 (choose_sources); baseline [F,n_src]; z_near, z_far [F]; inv_depth [F,D], uniform in inverse depth from
+      1 / z_far (plane 0) to 1 / z_near (plane D - 1); homographies [F,n_src,D,3,3], reference pixel -> source pixel:
+      K_s (R + t e3^T / z) K_r^-1 for the plane of depth z in the reference camera; rel_pose [F,n_src,3,4], reference camera -> source
+      camera.  Default range per view: z_far = f b_max -- one pixel of disparity over the view's widest baseline -- and z_near = z_far / D,
+      so that one plane step is one pixel of disparity at that baseline.  A view without a source sweeps the single depth z_far of the
+      nearest view that has one (1.0 when none has)."""
+    E = _w2c_4x4(w2c)
+    F = len(E)
+    K = np.asarray(K, np.float64)
+    K = np.broadcast_to(K, (F, 3, 3)) if K.ndim == 2 else K
+    if n_src < 1 or D < 1:
+        raise ValueError(f"n_src = {n_src} and D = {D} must be positive")
+    c2w = np.linalg.inv(E)
+    centres = c2w[:, :3, 3]
+    src = choose_sources(centres, n_src, min_baseline)
+    base = np.where(src >= 0, np.linalg.norm(centres[np.maximum(src, 0)] - centres[:, None], axis=-1), 0.0)
+    has = (src >= 0).any(1)
+    far = np.where(has, K[:, 0, 0] * base.max(1), 0.0) if z_far is None else np.broadcast_to(np.asarray(z_far, np.float64), (F,)).copy()
+    for i in np.flatnonzero(~has):                 # nothing to sweep against: the neighbour's far plane
+        with_src = np.flatnonzero(has)
+        far[i] = far[with_src[np.argmin(np.abs(with_src - i))]] if len(with_src) else 1.0
+    near = far / D if z_near is None else np.broadcast_to(np.asarray(z_near, np.float64), (F,)).copy()
+    near = np.where(has, near, far)
+    t = np.linspace(0.0, 1.0, D) if D > 1 else np.zeros(1)
+    inv_depth = 1.0 / far[:, None] + t[None] * (1.0 / near - 1.0 / far)[:, None]
+    rel = np.zeros((F, n_src, 4, 4))
+    Hs = np.zeros((F, n_src, D, 3, 3))
+    e3 = np.array([0.0, 0.0, 1.0])
+    for i in range(F):
+        Kinv = np.linalg.inv(K[i])
+        for s in range(n_src):
+            j = src[i, s]
+            if j < 0:
+                rel[i, s] = np.eye(4)
+                Hs[i, s] = np.eye(3)
+                continue
+            T = E[j] @ c2w[i]
+            rel[i, s] = T
+            Hs[i, s] = K[j] @ (T[:3, :3][None] + np.outer(T[:3, 3], e3)[None] * inv_depth[i][:, None, None]) @ Kinv
+    return SimpleNamespace(src_index=src, baseline=base, z_near=near, z_far=far, inv_depth=inv_depth, homographies=Hs,
+                           rel_pose=rel[:, :, :3, :4].copy(), K=K.copy(), has_source=has,
+                           inv_depth_f32=inv_depth.astype(np.float32), homographies_f32=Hs.astype(np.float32),
+                           rel_pose_f32=rel[:, :, :3, :4].astype(np.float32))
+
+
+def call_depth_model(depth_model, pers_u8, camera_params, segment_id):
+    """How process_episode calls its depth stage: a stage that declares `wants_view_poses` also gets the views' world->camera
+    matrices (view_poses); any other callable is called with the frames alone, exactly as before."""
+    if getattr(depth_model, "wants_view_poses", False):
+        return depth_model(pers_u8, view_w2c=view_poses(camera_params, len(pers_u8), segment_id))
+    return depth_model(pers_u8)
+
+
+class PlaneSweepDepth:
+    """The depth stage: `__call__(views uint8 [F,H,W,3] on the device, view_w2c [F,3,4])` -> the predictions dict of the depth network's
+    duck type, as device tensors: depth [F,H,W,1], depth_conf [F,H,W], images [F,3,H,W] (the frames / 255), extrinsic [F,3,4] (view_w2c),
+    intrinsic [F,3,3] (pinhole).  n_src sources per view, `planes` depth planes (sweep_setup); patch_radius and oob_cost as
+    ew_mvs_plane_sweep; a pixel keeps its confidence when at least min_consistent sources hold a depth within rel_tol of its own
+    (min_consistent is capped at the number of sources a view has; 0 switches the check off).  Without view_w2c the poses come from
+    view_poses(camera_params, F, segment_id), the segment inferred from F = 25 + 24 k when it is not given."""
+    wants_view_poses = True
+
+    def __init__(self, camera_params=None, n_src=4, planes=64, patch_radius=2, oob_cost=48.0, min_consistent=2, rel_tol=0.02,
+                 z_near=None, z_far=None, min_baseline=1e-6, segment_id=None):
+        if patch_radius not in (0, 1, 2, 3):
+            raise ValueError(f"patch_radius must be 0 .. 3, got {patch_radius!r}")
+        if n_src < 1 or planes < 1:
+            raise ValueError(f"n_src = {n_src} and planes = {planes} must be positive")
+        self.camera_params = None if camera_params is None else np.asarray(camera_params, np.float64)
+        self.n_src, self.planes, self.patch_radius, self.oob_cost = int(n_src), int(planes), int(patch_radius), float(oob_cost)
+        self.min_consistent, self.rel_tol = int(min_consistent), float(rel_tol)
+        self.z_near, self.z_far, self.min_baseline, self.segment_id = z_near, z_far, min_baseline, segment_id
+        self.last_setup = None
+
+    def _poses(self, n):
+        if self.camera_params is None:
+            raise ValueError("PlaneSweepDepth needs view_w2c, or camera_params to derive it from")
+        seg = self.segment_id
+        if seg is None:
+            if n < 25 or (n - 25) % 24:
+                raise ValueError(f"cannot infer the segment from {n} views (25 + 24 k expected): pass segment_id or view_w2c")
+            seg = (n - 25) // 24
+        return view_poses(self.camera_params, n, seg)
+
+    def __call__(self, pers_u8, view_w2c=None):
+        from . import ops
+        if not isinstance(pers_u8, torch.Tensor) or pers_u8.dtype != torch.uint8 or pers_u8.ndim != 4 or pers_u8.shape[3] != 3:
+            raise TypeError("PlaneSweepDepth: the views must be a device uint8 [F,H,W,3] tensor")
+        F, H, W, _ = pers_u8.shape
+        dev = pers_u8.device
+        w2c = self._poses(F) if view_w2c is None else view_w2c
+        K = pinhole(H, W)
+        st = sweep_setup(w2c, K, self.n_src, self.planes, self.z_near, self.z_far, self.min_baseline)
+        self.last_setup = st
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        src = up(st.src_index)
+        grey = ops.mvs_luma(pers_u8.contiguous())
+        depth, conf, _, _ = ops.mvs_plane_sweep(grey, up(st.homographies_f32), src, up(st.inv_depth_f32), self.patch_radius, self.oob_cost)
+        need = min(self.min_consistent, int((st.src_index >= 0).sum(1).max()))
+        if need > 0:
+            ops.mvs_consistency(depth, up(st.rel_pose_f32), src, conf, K[0, 0], K[1, 1], K[0, 2], K[1, 2], self.rel_tol, need)
+        E = _w2c_4x4(w2c)[:, :3, :4]
+        return {"depth": depth[..., None], "depth_conf": conf, "images": pers_u8.permute(0, 3, 1, 2).float() / 255,
+                "extrinsic": up(E.astype(np.float32)), "intrinsic": up(np.repeat(K[None].astype(np.float32), F, 0))}
+
+
+# ------------------------------------------------------------------ command line
+def _load_frames(folder, n, device):
+    from PIL import Image
+    names = sorted(f for f in os.listdir(folder) if f.lower().endswith((".png", ".jpg")))
+    if not names:
+        raise SystemExit(f"no .png / .jpg frames under {folder}")
+    names = names[:n] if n else names
+    return torch.from_numpy(np.stack([np.array(Image.open(os.path.join(folder, f)).convert("RGB")) for f in names])).to(device)
+
+
+def _cloud_main(args):
+    from . import reprojection as RP
+    from .dataset import load_camera_poses
+    from .memory import SceneMemory
+    poses = args.poses
+    cam = load_camera_poses(os.path.dirname(os.path.abspath(poses)) if os.path.isfile(poses) else poses)
+    n = 25 + 24 * args.segment
+    frames = _load_frames(args.frames, n, "cuda")
+    n = min(n, len(frames), len(cam))
+    frames = frames[:n]
+    yaws = RP.calculate_target_yaws(cam, n, args.segment)
+    views = RP.Equi2Pers(height=args.view_height, width=args.view_width, fov_x=90.0).batch(
+        frames, [{"pitch": 0, "roll": 0, "yaw": float(y)} for y in yaws])
+    stage = PlaneSweepDepth(cam, n_src=args.sources, planes=args.planes, patch_radius=args.patch_radius)
+    preds = stage(views, view_w2c=view_poses(cam, n, args.segment))
+    mem = SceneMemory.from_predictions(preds, conf_thres=args.conf_thres, show_cam=args.show_cam, prediction_mode="depth_unproject")
+    n_in = len(mem)
+    if args.voxel_size is not None:
+        mem = mem.voxel_downsample(args.voxel_size)
+    if args.output.lower().endswith(".ply"):
+        mem.to_ply(args.output)
+    elif args.output.lower().endswith(".glb"):
+        mem.to_glb(args.output)
+    else:
+        raise SystemExit(f"--output must end in .glb or .ply (got {args.output})")
+    print(json.dumps({"output": args.output, "views": int(n), "points_in": n_in, "points_out": len(mem), "scene_scale": mem.scene_scale,
+                      "planes": args.planes, "sources": args.sources}))
+
+
+def build_parser():
+    p = argparse.ArgumentParser(prog="python -m evoworld_amd.mvs", description=__doc__.split("\n\n")[0])
+    sub = p.add_subparsers(dest="command", required=True)
+    c = sub.add_parser("cloud", help="panorama frames + poses -> perspective views -> plane-sweep depth -> filtered cloud (.ply | .glb)")
+    c.add_argument("--frames", required=True, help="folder of panorama frames (NNN.png, sorted by name), e.g. an episode's predictions/")
+    c.add_argument("--poses", required=True, help="camera_poses.txt (or the folder that holds it)")
+    c.add_argument("--segment", type=int, default=0, help="segment K: the first 25 + 24 K frames, looking at the segment's target pose")
+    c.add_argument("--output", required=True, help="scene.ply or scene.glb")
+    c.add_argument("--planes", type=int, default=64)
+    c.add_argument("--sources", type=int, default=4)
+    c.add_argument("--patch_radius", type=int, default=2)
+    c.add_argument("--conf_thres", type=float, default=50.0, help="confidence percentile below which points are dropped")
+    c.add_argument("--voxel_size", type=float, default=None, help="voxel-grid downsample on the device before the export")
+    c.add_argument("--show_cam", action="store_true", help="add one pyramid marker per camera (GLB)")
+    c.add_argument("--view_height", type=int, default=384)
+    c.add_argument("--view_width", type=int, default=512)
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    _cloud_main(args)
+
+
+if __name__ == "__main__":
+    sys.exit(main())

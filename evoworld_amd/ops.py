@@ -792,6 +792,81 @@ def resize_linear_u8(src, h, w, out=None):
     return out
 
 
+def _mvs_out(out, shape, dtype, device, name):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(out.shape) != tuple(shape):
+        raise ValueError(f"{name} must be {tuple(shape)}, got {tuple(out.shape)}")
+    return _req(out, dtype, name)
+
+
+def mvs_luma(frames_u8, out=None):
+    """frames uint8 [F,H,W,3] on the device -> grey uint8 [F,H,W] = (77 R + 150 G + 29 B + 128) >> 8 (ew_mvs_luma_u8)."""
+    if frames_u8.dtype != torch.uint8:
+        raise TypeError(f"frames_u8: expected {torch.uint8}, got {frames_u8.dtype}")
+    if frames_u8.ndim != 4 or frames_u8.shape[3] != 3 or frames_u8.numel() == 0:
+        raise ValueError(f"frames_u8 must be a non-empty [F,H,W,3], got {tuple(frames_u8.shape)}")
+    _req(frames_u8, torch.uint8, "frames_u8")
+    F_, H, W, _ = frames_u8.shape
+    out = _mvs_out(out, (F_, H, W), torch.uint8, frames_u8.device, "out")
+    _call("ew_mvs_luma_u8", _ptr(frames_u8), _ptr(out), F_, H, W)
+    return out
+
+
+def _mvs_sources(src_index, F_):
+    if src_index.ndim != 2 or src_index.shape[0] != F_ or src_index.shape[1] < 1:
+        raise ValueError(f"src_index must be [F = {F_}, S >= 1], got {tuple(src_index.shape)}")
+    _req(src_index, torch.int32, "src_index")
+    return src_index.shape[1]
+
+
+def mvs_plane_sweep(grey, homographies, src_index, inv_depth, patch_radius=2, oob_cost=48.0, out=None):
+    """grey uint8 [F,H,W], homographies fp32 [F,S,D,3,3] (reference pixel -> source pixel), src_index int32 [F,S] (-1: absent), inv_depth
+    fp32 [F,D] -> (depth fp32, conf fp32, winner int32, winner cost fp32), each [F,H,W] (ew_mvs_plane_sweep).
+    out: the four output tensors to write into."""
+    if grey.ndim != 3 or grey.numel() == 0:
+        raise ValueError(f"grey must be a non-empty [F,H,W], got {tuple(grey.shape)}")
+    _req(grey, torch.uint8, "grey")
+    F_, H, W = grey.shape
+    S = _mvs_sources(src_index, F_)
+    if inv_depth.ndim != 2 or inv_depth.shape[0] != F_ or inv_depth.shape[1] < 1:
+        raise ValueError(f"inv_depth must be [F = {F_}, D >= 1], got {tuple(inv_depth.shape)}")
+    D = inv_depth.shape[1]
+    if tuple(homographies.shape) != (F_, S, D, 3, 3):
+        raise ValueError(f"homographies must be {(F_, S, D, 3, 3)}, got {tuple(homographies.shape)}")
+    if patch_radius not in (0, 1, 2, 3):
+        raise ValueError(f"patch_radius must be 0 .. 3, got {patch_radius!r}")
+    _req(homographies, torch.float32, "homographies"); _req(inv_depth, torch.float32, "inv_depth")
+    dev = grey.device
+    given = out if out is not None else (None,) * 4
+    depth = _mvs_out(given[0], (F_, H, W), torch.float32, dev, "out[0]")
+    conf = _mvs_out(given[1], (F_, H, W), torch.float32, dev, "out[1]")
+    winner = _mvs_out(given[2], (F_, H, W), torch.int32, dev, "out[2]")
+    cost = _mvs_out(given[3], (F_, H, W), torch.float32, dev, "out[3]")
+    _call("ew_mvs_plane_sweep", _ptr(grey), _ptr(homographies), _ptr(src_index), _ptr(inv_depth), _ptr(depth), _ptr(conf), _ptr(winner),
+          _ptr(cost), F_, H, W, S, D, int(patch_radius), float(oob_cost))
+    return depth, conf, winner, cost
+
+
+def mvs_consistency(depth, rel_pose, src_index, conf, fx, fy, cx, cy, rel_tol=0.02, min_consistent=2):
+    """depth fp32 [F,H,W], rel_pose fp32 [F,S,3,4] (reference camera -> source camera), src_index int32 [F,S]; conf fp32 [F,H,W] is set
+    to 0 IN PLACE where fewer than min_consistent present sources hold a depth within rel_tol of the lifted pixel's (ew_mvs_consistency).
+    Returns conf."""
+    if depth.ndim != 3 or depth.numel() == 0:
+        raise ValueError(f"depth must be a non-empty [F,H,W], got {tuple(depth.shape)}")
+    _req(depth, torch.float32, "depth")
+    F_, H, W = depth.shape
+    S = _mvs_sources(src_index, F_)
+    if tuple(rel_pose.shape) != (F_, S, 3, 4):
+        raise ValueError(f"rel_pose must be {(F_, S, 3, 4)}, got {tuple(rel_pose.shape)}")
+    if tuple(conf.shape) != (F_, H, W):
+        raise ValueError(f"conf must be {(F_, H, W)}, got {tuple(conf.shape)}")
+    _req(rel_pose, torch.float32, "rel_pose"); _req(conf, torch.float32, "conf")
+    _call("ew_mvs_consistency", _ptr(depth), _ptr(rel_pose), _ptr(src_index), _ptr(conf), F_, H, W, S, float(fx), float(fy), float(cx),
+          float(cy), float(rel_tol), int(min_consistent))
+    return conf
+
+
 def equi2pers(equi, rot, Hp, Wp, fov_x):
     _req(equi, torch.uint8, "equi"); _req(rot, torch.float32, "rot")
     F_, He, We, _ = equi.shape

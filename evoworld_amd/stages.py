@@ -123,13 +123,28 @@ class HipStages(SyntheticStages):
         return torch.cat([self.vae.decode(z[i:i + c], num_frames=min(c, z.shape[0] - i)).sample for i in range(0, z.shape[0], c)])
 
 
-def load_stages(spec, args, **kw):
-    """spec 'pkg.mod:factory' -> factory(args); 'hip' -> HipStages (VAE + CLIP on the HIP kernels); None -> SyntheticStages."""
+DEPTH_STAGES = ("synthetic", "mvs")
+
+
+def load_stages(spec, args, depth_stage=None, **kw):
+    """spec 'pkg.mod:factory' -> factory(args); 'hip' -> HipStages (VAE + CLIP on the HIP kernels); None -> SyntheticStages.
+    depth_stage (opt-in): 'mvs' replaces ONLY `depth_model` of whichever stages object was chosen by the plane-sweep stereo stage
+    (evoworld_amd.mvs.PlaneSweepDepth; planes and sources from args.mvs_planes / args.mvs_sources when they are set); None or
+    'synthetic' leaves the object as it is."""
+    if depth_stage not in (None,) + DEPTH_STAGES:
+        raise ValueError(f"depth_stage must be one of {DEPTH_STAGES}, got {depth_stage!r}")
+    camera_params = kw.get("camera_params")
     if spec == "hip":
-        return HipStages(svd_path=getattr(args, "svd_path", None), cross_attention_dim=kw.get("cross_attention_dim", 1024),
-                         camera_params=kw.get("camera_params"), depth_hw=(392, 518))
-    if not spec:
-        return SyntheticStages(**kw)
-    import importlib
-    mod, _, fn = spec.partition(":")
-    return getattr(importlib.import_module(mod), fn or "make_stages")(args)
+        stages = HipStages(svd_path=getattr(args, "svd_path", None), cross_attention_dim=kw.get("cross_attention_dim", 1024),
+                           camera_params=camera_params, depth_hw=(392, 518))
+    elif not spec:
+        stages = SyntheticStages(**kw)
+    else:
+        import importlib
+        mod, _, fn = spec.partition(":")
+        stages = getattr(importlib.import_module(mod), fn or "make_stages")(args)
+    if depth_stage == "mvs":
+        from .mvs import PlaneSweepDepth
+        opt = {k: v for k, v in (("planes", getattr(args, "mvs_planes", None)), ("n_src", getattr(args, "mvs_sources", None))) if v is not None}
+        stages.depth_model = PlaneSweepDepth(camera_params, **opt)
+    return stages

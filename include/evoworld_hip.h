@@ -485,6 +485,37 @@ ew_status ew_png_emit(const uint32_t* tokens, const int* n_tokens, const uint8_t
                       const int* header_bits, int header_stride, uint8_t* out, long long out_bytes, int V, int H, int W,
                       int rows_per_segment, long long token_stride, void* stream);
 
+/* Plane-sweep multi-view stereo on posed perspective views (csrc/mvs.hip; added to ABI 20 without a bump: new symbols only, DESIGN.md
+ * 4.8).  A weight-free depth source that stands in for the depth network of unified_loop_consistency.py:336-368 (VGGT-1B: depth,
+ * confidence, cameras): here the cameras are known and depth comes from photo-consistency.  fp32 in the order written below; no atomics:
+ * two calls return identical bits, and a view's outputs depend only on that view and its sources.
+ * ew_mvs_luma_u8 (stands in for the network's own preprocessing, unified_loop_consistency.py:336-368): rgb uint8 [F,H,W,3] -> grey uint8
+ *   [F,H,W] = (77 R + 150 G + 29 B + 128) >> 8.
+ * ew_mvs_plane_sweep (unified_loop_consistency.py:336-368, the depth and depth_conf outputs): grey uint8 [F,H,W]; homographies fp32
+ *   [F,S,D,3,3] row-major, reference pixel -> source pixel for S source slots and D planes; src_index int32 [F,S], the view a slot reads
+ *   (outside [0, F), e.g. -1: the slot is absent); inv_depth fp32 [F,D].  For the reference pixel (x, y) -- integer indices, the pixel
+ *   convention of ew_depth_unproject --: q_i = (h_i0 x + h_i1 y) + h_i2, sx = q0 / q2, sy = q1 / q2; AD = |I_ref(x, y) - bilinear(I_src,
+ *   sx, sy)| with x0 = floor(sx), ax = sx - x0, x1 = min(x0 + 1, W - 1) (rows alike), top = v00 (1 - ax) + v01 ax, bot = v10 (1 - ax) +
+ *   v11 ax, value = top (1 - ay) + bot ay; AD = oob_cost unless q2 > 0 and 0 <= sx <= W - 1 and 0 <= sy <= H - 1.  A = the sum of AD over
+ *   the present slots in slot order; C(k) = (the sum over the window's rows, top to bottom, of the sum over a row's taps, left to right,
+ *   of A) / (taps inside the reference image x present slots): the mean over the (2 patch_radius + 1)^2 window, taps outside the image
+ *   dropped, of the mean over the sources.  Winner k* = the lowest C, ties to the lowest k.  With 0 < k* < D - 1 and curv = (C(k* - 1) +
+ *   C(k* + 1)) - 2 C(k*) > 0: off = clamp(0.5 (C(k* - 1) - C(k* + 1)) / curv, -0.5, 0.5) and the inverse depth moves from inv_depth[k*]
+ *   by |off| of the way to the neighbour on that side; otherwise it is inv_depth[k*].  depth = 1 / that.  conf = (C2 - C1) / max(C2,
+ *   1e-6), C1 = C(k*), C2 = the lowest C among the planes with |k - k*| > 1; 0 when there is no such plane or no slot is present (then
+ *   every C is 0 and k* = 0).  Outputs depth, conf, winner_cost fp32 [F,H,W], winner int32 [F,H,W].  patch_radius 0 .. 3.
+ * ew_mvs_consistency (unified_loop_consistency.py:336-368, what makes depth_conf mean agreement between views): depth fp32 [F,H,W];
+ *   rel_pose fp32 [F,S,3,4], reference camera -> source camera (R | t); src_index as above; pinhole fx, fy, cx, cy.  Per pixel: Xc =
+ *   ((x - cx) z / fx, (y - cy) z / fy, z), Xs = R Xc + t (each row ((r0 xc + r1 yc) + r2 z) + t); a slot agrees when Xs.z > 0, the nearest
+ *   pixel (floor((fx Xs.x / Xs.z + cx) + 0.5), rows alike) lies in the source and |depth_src there - Xs.z| <= rel_tol Xs.z.  conf [F,H,W]
+ *   is set to 0, in place, where fewer than min_consistent slots agree. */
+ew_status ew_mvs_luma_u8(const uint8_t* rgb, uint8_t* grey, int F, int H, int W, void* stream);
+ew_status ew_mvs_plane_sweep(const uint8_t* grey, const float* homographies, const int* src_index, const float* inv_depth, float* depth,
+                             float* conf, int* winner, float* winner_cost, int F, int H, int W, int S, int D, int patch_radius,
+                             float oob_cost, void* stream);
+ew_status ew_mvs_consistency(const float* depth, const float* rel_pose, const int* src_index, float* conf, int F, int H, int W, int S,
+                             float fx, float fy, float cx, float cy, float rel_tol, int min_consistent, void* stream);
+
 /* Equirect -> perspective bilinear gather (pyequilib Equi2Pers restatement; unified_loop_consistency.py:299-334).
  * equi uint8 [F,He,We,3]; rot [F,3,3] f32 (camera->pano rotation); out uint8 [F,Hp,Wp,3]. */
 ew_status ew_equi2pers(const uint8_t* equi, const float* rot, uint8_t* out, int F, int He, int We, int Hp, int Wp,

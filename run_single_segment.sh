@@ -29,6 +29,7 @@ CMD="unified_loop_consistency.py --unet_path $CKPT --svd_path $CKPT --base_folde
 [ "$QKV_FP8" = 1 ] && CMD="$CMD --qkv_fp8"      # opt-in fp8 (e4m3) q / k / v projections: BASELINE.json configs[4]
 [ "$SAVE_VIDEO" = 1 ] && CMD="$CMD --save_video"   # opt-in: navigated.avi + original.avi, Motion-JPEG encoded on the device
 [ "$DEVICE_PNG" = 1 ] && CMD="$CMD --device_png"   # opt-in: the --save_frames PNG files are encoded on the device (same pixels)
+[ -n "$DEPTH_STAGE" ] && CMD="$CMD --depth_stage $DEPTH_STAGE"   # accepted for symmetry with run_unified_pipeline.sh: this path renders no memory, so no depth stage runs
 [ -n "$VIDEO_FPS" ] && CMD="$CMD --video_fps $VIDEO_FPS"
 [ -n "$VIDEO_QUALITY" ] && CMD="$CMD --video_quality $VIDEO_QUALITY"
 

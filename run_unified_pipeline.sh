@@ -31,6 +31,9 @@ CMD="unified_loop_consistency.py --unet_path $CKPT --svd_path $CKPT --base_folde
 [ -n "$MEMORY_VOXEL_SIZE" ] && CMD="$CMD --memory_voxel_size $MEMORY_VOXEL_SIZE"   # opt-in voxel-grid downsample of the memory
 [ "$SAVE_VIDEO" = 1 ] && CMD="$CMD --save_video"   # opt-in: navigated.avi (+ original.avi) per episode, Motion-JPEG encoded on the device
 [ "$DEVICE_PNG" = 1 ] && CMD="$CMD --device_png"   # opt-in: the --save_frames PNG files are encoded on the device (same pixels)
+[ -n "$DEPTH_STAGE" ] && CMD="$CMD --depth_stage $DEPTH_STAGE"   # opt-in: mvs = plane-sweep stereo depth from the generated frames (default: synthetic)
+[ -n "$MVS_PLANES" ] && CMD="$CMD --mvs_planes $MVS_PLANES"
+[ -n "$MVS_SOURCES" ] && CMD="$CMD --mvs_sources $MVS_SOURCES"
 [ -n "$VIDEO_FPS" ] && CMD="$CMD --video_fps $VIDEO_FPS"
 [ -n "$VIDEO_QUALITY" ] && CMD="$CMD --video_quality $VIDEO_QUALITY"
 

@@ -1,0 +1,93 @@
+"""Times the plane-sweep stereo stage (csrc/mvs.hip, evoworld_amd/mvs.py) entry by entry at the sizes the N-segment loop
+hands it: 25 and 73 perspective views of 384 x 512 (the hand-offs after segments 0 and 2).
+
+  python tools/bench_mvs.py [--iters 3] [--views 25 73] [--planes 64] [--sources 4] [--patch_radius 2] [--out profiles/mvs_bench.json]
+
+The views: bench_video.synthetic_clip (gradients, a texture of sinusoids, noise of sigma 4) -- the timing does not depend on what the
+sweep finds -- at the poses view_poses gives for the curved synthetic episode of unified_loop_consistency.py.  Device events around
+`iters` calls of each entry (ew_mvs_luma_u8, ew_mvs_plane_sweep, ew_mvs_consistency) with the bytes each must move at the least and,
+for the sweep, the warped samples it evaluates (views x pixels x planes x present sources, the tile halos not counted); a host clock
+around the synchronised PlaneSweepDepth call, which adds sweep_setup's float64 homographies on the host and the uploads.  Prints one
+JSON line and, with --out, writes it there.  No gate and no speed claim: these are measurements."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from bench_video import HBM_TBS, stage, synthetic_clip, timed  # noqa: E402
+
+
+def run(V, H, W, D, S, r, it):
+    import unified_loop_consistency as cli
+    from evoworld_amd import mvs, ops
+    seg = max(0, (V - 25) // 24)
+    cam = cli.synthetic_episode(max(V, 24 * (seg + 2) + 8))
+    clip = synthetic_clip(V, H, W)
+    w2c = mvs.view_poses(cam, V, seg)
+    K = mvs.pinhole(H, W)
+    t0 = time.perf_counter()
+    st = mvs.sweep_setup(w2c, K, S, D)
+    setup_ms = (time.perf_counter() - t0) * 1e3
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    homog, src, invd, pose = up(st.homographies_f32), up(st.src_index), up(st.inv_depth_f32), up(st.rel_pose_f32)
+    grey = ops.mvs_luma(clip)
+    depth, conf, win, cost = ops.mvs_plane_sweep(grey, homog, src, invd, r, 48.0)
+    P = ops._ptr
+    px = V * H * W
+    samples = int((st.src_index >= 0).sum(1).astype(np.int64).sum()) * H * W * D
+    stages = [
+        stage("luma", timed(lambda: ops._call("ew_mvs_luma_u8", P(clip), P(grey), V, H, W), it), 4 * px, "RGB in, grey out"),
+        stage("plane_sweep", timed(lambda: ops._call("ew_mvs_plane_sweep", P(grey), P(homog), P(src), P(invd), P(depth), P(conf), P(win), P(cost),
+                                                     V, H, W, S, D, r, 48.0), it),
+              px + 16 * px + homog.numel() * 4, "grey in once, four planes out, the homographies; the gathers from the sources hit the caches"),
+        stage("consistency", timed(lambda: ops._call("ew_mvs_consistency", P(depth), P(pose), P(src), P(conf), V, H, W, S, float(K[0, 0]), float(K[1, 1]),
+                                                     float(K[0, 2]), float(K[1, 2]), 0.02, 2), it),
+              8 * px, "depth and confidence in, confidence out; one gathered depth per present source"),
+    ]
+    sweep_us = stages[1]["us"]
+    stage_obj = mvs.PlaneSweepDepth(n_src=S, planes=D, patch_radius=r)
+    wall = []
+    for _ in range(2):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        stage_obj(clip, view_w2c=w2c)
+        torch.cuda.synchronize()
+        wall.append(time.perf_counter() - t0)
+    return {"views": V, "height": H, "width": W, "planes": D, "sources": S, "patch_radius": r, "segment": seg, "stages": stages,
+            "warped_samples": samples, "sweep_Gsamples_per_s": round(samples / sweep_us / 1e3, 2), "kernels_ms": round(sum(s["us"] for s in stages) / 1e3, 2),
+            "host_setup_ms": round(setup_ms, 1), "stage_call_wall_ms": round(min(wall) * 1e3, 1), "homography_bytes": homog.numel() * 4}
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    p.add_argument("--iters", type=int, default=3)
+    p.add_argument("--views", type=int, nargs="+", default=[25, 73])
+    p.add_argument("--height", type=int, default=384)
+    p.add_argument("--width", type=int, default=512)
+    p.add_argument("--planes", type=int, default=64)
+    p.add_argument("--sources", type=int, default=4)
+    p.add_argument("--patch_radius", type=int, default=2)
+    p.add_argument("--out", type=str, default=None)
+    args = p.parse_args(argv)
+    rec = {"tool": "bench_mvs", "device": torch.cuda.get_device_name(0), "iters": args.iters, "hbm_TBps": HBM_TBS,
+           "runs": [run(V, args.height, args.width, args.planes, args.sources, args.patch_radius, args.iters) for V in args.views],
+           "note": "device events around whole entry calls; stage_call_wall_ms is the best of two synchronised PlaneSweepDepth calls with the "
+                   "host's float64 homographies (host_setup_ms, timed alone) and their upload.  The sweep is compute-bound: per warped sample two "
+                   "IEEE divisions, a bilinear blend of four gathered bytes and the LDS box filter.  No gate."}
+    line = json.dumps(rec)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

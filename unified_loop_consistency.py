@@ -55,6 +55,10 @@ def parse_arguments(argv=None):
     p.add_argument("--video_quality", type=int, default=90, help="JPEG quality (1..100) of the --save_video files")
     p.add_argument("--device_png", action="store_true",
                    help="encode the --save_frames PNG files on the device (same names, same pixels, file bytes other than Pillow's)")
+    p.add_argument("--depth_stage", choices=("synthetic", "mvs"), default="synthetic",
+                   help="depth source of the memory hand-off: the stand-in's fixed room, or plane-sweep stereo on the generated frames (opt-in)")
+    p.add_argument("--mvs_planes", type=int, default=64, help="depth planes of --depth_stage mvs")
+    p.add_argument("--mvs_sources", type=int, default=4, help="source views per reference view of --depth_stage mvs")
     return p.parse_args(argv)
 
 
@@ -158,7 +162,7 @@ def run_episode(args, ep, pipe, unet, dev, out_dir, synthetic):
         cam = synthetic_episode(24 * args.num_segments + 8) if args.curve_path else synthetic_path_episode(args.num_segments)
     else:
         cam = load_camera_poses(ep)
-    stages = load_stages(args.stages, args, cross_attention_dim=unet._cfg["cross_attention_dim"], camera_params=cam)
+    stages = load_stages(args.stages, args, depth_stage=getattr(args, "depth_stage", None), cross_attention_dim=unet._cfg["cross_attention_dim"], camera_params=cam)
     start = None if synthetic else load_complete_episode_batch(ep, args.height, args.width, dev, cam=cam)["first_frame"]
     if start is None:
         g = torch.Generator().manual_seed(0)
