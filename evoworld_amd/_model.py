@@ -54,6 +54,14 @@ class Weights:
         """[O, I, 3, 3] or [O, I, 3, 1, 1] -> ([O, K] in ew_gemm_f16's conv order, K = [I/64][taps][64], bias)"""
         return ops.pack_conv_weight(self.f32(p + ".weight"), cpad), self.h(self.f32(p + ".bias"))
 
+    def conv_up(self, p):
+        """the conv of a nearest-x2 upsampler -> (w, bias, upsample): the four-phase pack [4 O, 4 I] with upsample = 2 where ew_gemm_f16 runs that
+        form for these channel counts (ops.convup2_ok), the nine taps with upsample = 1 otherwise.  One form per layer."""
+        w = self.f32(p + ".weight")
+        if ops.convup2_ok(w.shape[0], w.shape[1]):
+            return ops.pack_convup2_weight(w), self.h(self.f32(p + ".bias")), 2
+        return self.conv(p) + (1,)
+
 
 class PackedModel:
     DEFAULTS = {}           # config keys and their defaults: what config.json is filtered by
@@ -135,8 +143,9 @@ class PackedModel:
         c1 = x.shape[-1]
         lda2 = x2.shape[-1] if x2 is not None else 0
         M = N * Ho * Wo
-        out = self._res(M, w.shape[0], x.device, head="r1" not in kw) if res_out else torch.empty(M, w.shape[0], dtype=torch.float16, device=x.device)
-        return ops.gemm(x, w, out, M=M, N=w.shape[0], c1=c1, lda=c1, a2=x2, c2=lda2 if c2 is None else c2, lda2=lda2, bias=b,
+        n_out = w.shape[0] // 4 if upsample == 2 else w.shape[0]      # upsample=2: w is the four-phase pack (Weights.conv_up)
+        out = self._res(M, n_out, x.device, head="r1" not in kw) if res_out else torch.empty(M, n_out, dtype=torch.float16, device=x.device)
+        return ops.gemm(x, w, out, M=M, N=n_out, c1=c1, lda=c1, a2=x2, c2=lda2 if c2 is None else c2, lda2=lda2, bias=b,
                         mode=A_CONV3X3, conv=(N, H, W_, Ho, Wo, stride, upsample), **kw)
 
     def _convt(self, x, w, b, B, T, P, res_out=False, **kw):

@@ -13,7 +13,8 @@
 //     read of the tile (step 17 of 20) so that steps 18-19 already prefetch the next tile's first fragments;
 //   * persistent workgroups, XCD-chunked tile order, fused epilogue (bias / row-bias / SiLU / GEGLU / 2 residuals) through a
 //     wave-private fp32 LDS patch in two 80-column passes, as in generation 2.
-// Same argument block and A addressing modes (dense / conv3x3 / temporal 3-tap, dual source, zero page) as gen 1/2.
+// Same argument block and A addressing modes (dense / conv3x3 / temporal 3-tap, dual source, zero page) as gen 1/2, plus one of its own:
+// EW_A_CONVUP2 (gemm_common.h), the 3x3 conv over a nearest-x2 upsampled image as four 2x2 phase convs over the source image (K = 4 C).
 // Requires N % 320 == 0 (the dispatcher falls back to generation 2 otherwise).
 #include "gemm_gen23.h"
 
@@ -63,6 +64,17 @@ __device__ __forceinline__ void tile_coords(int id, int tiles_m, int tiles_n, in
     const int w = k == nb - 1 ? tiles_n - k * band : band;
     tm = r / w;
     tn = k * band + (r - tm * w);
+}
+
+// EW_A_CONVUP2 (gemm_common.h): tile row tm of the tiles_m = 4 x (tiles per phase) phase-major M tiles -> its phase 2a + b (the return value) and
+// its tile row inside the phase.  The phase is the OUTER coordinate: a phase's tiles are consecutive and its W slice stays in L2.  (Phase inner -- the four
+// phases of an A row tile consecutive, re-hitting its rows -- measured within +-3 % of this on the three shapes of the U-Net, slower at four
+// times their rows: DESIGN.md section 3.6a.)
+__device__ __forceinline__ int convup2_phase(const GemmP& p, int& tm) {
+    const int per_phase = p.tiles_m >> 2;
+    const int ph = tm / per_phase;
+    tm -= ph * per_phase;
+    return ph;
 }
 
 template <int MODE, int EPI>
@@ -141,14 +153,19 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm3_kernel(const GemmP p, const 
     constexpr int NTAP = ew_a_ntap<MODE>;
     int ld_w = 0, ld_kt = 0, ld_k1 = 0, ld_tap = 0, ld_cc = 0;   // ld_kt == ld_k1: the next stage_begin opens work item ld_w
     int a_ctr[GA];                         // centre-tap pixel (row) index in the source tensors, relative to the wave's reference pixel a_ref
-    int a_mask[GA];                        // bits 0..8 tap validity, bits 16..27 upsample (dy,dx) codes
+    int a_mask[GA];                        // bits 0..8 tap validity (EW_A_CONVUP2: bits 0..3), bits 16..27 upsample (dy,dx) codes
     int a_ref = 0;                         // wave-uniform reference pixel: every a_ctr[i] (+ an upsample delta) of this wave is >= 0 relative to it
     unsigned b_off = 0;                    // byte offset of this lane's W row (first piece) + 16-byte slot inside the tile column's W slice; piece j adds j*NW*8 rows
     int w_n0 = 0;                          // first W row of the tile column (wave-uniform)
+    int up_ph = 0, up_d0 = 0;              // EW_A_CONVUP2: the tile's phase 2a + b and the pixel delta of its tap (0, 0): (a - 1) * w_in + (b - 1)
 
     auto loader_new_tile = [&](const int id) __attribute__((always_inline)) {
         int tm, tn;
         tile_coords(id, p.tiles_m, p.tiles_n, p.band, tm, tn);
+        if constexpr (MODE == EW_A_CONVUP2) {
+            up_ph = convup2_phase(p, tm);
+            up_d0 = ((up_ph >> 1) - 1) * p.w_in + (up_ph & 1) - 1;
+        }
         const int m0 = tm * BM, n0 = tn * BN;
         // per-lane constants are re-derived from an opaque copy of the lane id: hoisted out of the K-tile stream they would
         // be live across the main loop, where every VGPR is taken, and come back as scratch reloads (each with a vmcnt(0))
@@ -183,6 +200,19 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm3_kernel(const GemmP p, const 
                 } else {
                     ctr = (img * p.h_in + cy) * p.w_in + cx;
                 }
+            } else if constexpr (MODE == EW_A_CONVUP2) {
+                // row m = source pixel (img, sy, sx); tap (r, c) reads (sy + a - 1 + r, sx + b - 1 + c): the same delta for every row of the tile
+                // (stage_begin), so a row only keeps its four validity bits
+                const int rowi = m / p.w_in;
+                const int sx = m - rowi * p.w_in, sy = rowi % p.h_in;
+                const int y0 = sy + (up_ph >> 1) - 1, x0 = sx + (up_ph & 1) - 1;
+                mask = 0;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const int iy = y0 + (t >> 1), ix = x0 + (t & 1);
+                    if (iy >= 0 && iy < p.h_in && ix >= 0 && ix < p.w_in) mask |= 1 << t;
+                }
+                ctr = m;
             } else if constexpr (MODE == EW_A_CONVT3) {
                 const int tp = p.tT * p.tP;
                 const int bb = m / tp, rem = m - bb * tp;
@@ -250,9 +280,13 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm3_kernel(const GemmP p, const 
         st_ch = second ? cc - p.c1 : cc;
         int dpix = ew_a_tap_delta<MODE>(p, st_tap);                         // wave-uniform tap delta in pixels
         if constexpr (MODE == EW_A_CONV3X3) { if (p.upsample) dpix = 0; }          // per-row deltas instead (stage_piece)
+        if constexpr (MODE == EW_A_CONVUP2) dpix += up_d0;                         // the phase's tap (0, 0); goes into the base, so a_ref needs no slack
         const char* ua = (const char*)st_base + ((long long)(a_ref + dpix) * st_ld + st_ch) * 2;
         st_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)ua, 0, 0x7fffffff, 0x00020000);
         st_ld2 = (unsigned)st_ld * 2u;
+        if constexpr (MODE == EW_A_CONVUP2)            // W = [phase][N][K]
+            st_wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.w + (((size_t)up_ph * p.N + w_n0) * p.K + (size_t)ld_kt * BK) * 2), 0, 0x7fffffff, 0x00020000);
+        else
         st_wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.w + ((size_t)w_n0 * p.K + (size_t)ld_kt * BK) * 2), 0, 0x7fffffff, 0x00020000);
         // K order: channel-chunk major, tap minor (the taps of a 64-channel chunk re-hit the same lines in L2 / TCP)
         if (++ld_tap == NTAP) { ld_tap = 0; ld_cc += BK; }
@@ -308,7 +342,7 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm3_kernel(const GemmP p, const 
 #pragma unroll
             for (int i = 0; i < FM; ++i) acc[i][j] = b;
         }
-        if constexpr (RB_INIT) {
+        if constexpr (RB_INIT && MODE != EW_A_CONVUP2) {       // (the four-phase upsample conv takes no row-bias: refused on the host)
             // + row-bias of the row group of each of the lane's FM rows (same 4 / 8 consecutive columns as the bias above)
             const int frow_o = lane_o & 15;
             const int onr = (p.rowbias && k0 == 0) ? 1 : 0;
@@ -408,6 +442,8 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm3_kernel(const GemmP p, const 
             ++cur_w;
             int tm, tn;
             tile_coords(id, p.tiles_m, p.tiles_n, p.band, tm, tn);
+            int out_ph = 0;                                             // EW_A_CONVUP2: rows below are source pixels, the phase places them in the output
+            if constexpr (MODE == EW_A_CONVUP2) out_ph = convup2_phase(p, tm);
             const bool full = (tm * BM + wm * WM + WM <= p.M);          // N is always full (N % 320 == 0)
             // wave-private fp32 patch in the slot just consumed (free since the barrier of step 17; the DMA of the next
             // K-tile into it is issued by the NEXT position, after the closing barrier below)
@@ -632,10 +668,13 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm3_kernel(const GemmP p, const 
                             ew_pin();
                             if (k + ED < FM * NQ) fetch(k + ED);
                             ew_pin();
+                            int mo = m;
+                            if constexpr (MODE == EW_A_CONVUP2)       // source pixel (img, i, j) -> output pixel (img, 2i + a, 2j + b): one division per row fragment
+                                mo = 2 * m + 2 * (m / p.w_in) * p.w_in + (out_ph >> 1) * 2 * p.w_in + (out_ph & 1);
                             if ((FULL || m < p.M)) {
-                                *(f16x8*)((char*)p.out + (unsigned)(m * p.ld_out + n) * 2u) = o;
+                                *(f16x8*)((char*)p.out + (unsigned)(mo * p.ld_out + n) * 2u) = o;
                                 if constexpr (LO) {
-                                    if (p.out_lo) *(u32x2*)((char*)p.out_lo + (unsigned)(m * p.ld_out + n)) = ol;
+                                    if (p.out_lo) *(u32x2*)((char*)p.out_lo + (unsigned)(mo * p.ld_out + n)) = ol;
                                 }
                             }
                         }
@@ -931,6 +970,23 @@ struct Plan3 {
     SkWorkspace* w;           // non-null with a split: ws / flags / epoch are taken from it at the launch
 };
 
+// Persistent schedule of `tiles` output tiles: one 8-wave workgroup per CU, with the stream-K tail where it is allowed and worth it.
+// Stream-K tail: T tiles over 256 blocks cost ceil(T/256) rounds; every C-wide output of the U-Net is 1800 / 900 / 452 tiles =
+// 7.03 / 3.52 / 1.77 rounds paid as 8 / 4 / 2.  When the loss is worth it, the last (T mod 256) + 256 tiles are cut along K
+// into 256 equal ranges instead (gemm3_kernel: contributor / finisher hand-over through the uncached workspace).
+void plan3_persistent(Plan3& pl, long long tiles, int NCU, bool tail_ok, hipStream_t s) {
+    pl.grid = NCU;
+    if (tiles < pl.grid) pl.grid = (int)((tiles + 7) / 8 * 8);
+    if (tail_ok && tiles > NCU && tiles % NCU != 0) {
+        const long long rounds = (tiles + NCU - 1) / NCU;
+        const double loss = 1.0 - (double)tiles / ((double)NCU * rounds);
+        if (loss > 0.04 && (pl.w = ew_sk_workspace(SK_INST, s))) {       // no workspace: whole tiles
+            pl.sk.dp_rounds = (int)(tiles / NCU) - 1;
+            pl.sk.tiles = (int)(tiles - (long long)NCU * pl.sk.dp_rounds);
+        }
+    }
+}
+
 // *taken: generation 3 can run the problem AND is expected to be the faster choice (enough tiles to fill the chip, or the half split);
 // otherwise the problem goes to generation 2
 ew_status plan3(const GemmP& p, hipStream_t s, Plan3& pl, bool* taken) {
@@ -964,24 +1020,12 @@ ew_status plan3(const GemmP& p, hipStream_t s, Plan3& pl, bool* taken) {
     pl.q.band = ((long long)p.N * p.K * 2 > 3LL * 1024 * 1024) ? 4 : 0;
     pl.sk = SkP{nullptr, nullptr, 0u, 0, 0}; pl.w = nullptr;
     if (tiles * 256 >= 200LL * NCU) {                 // (200 of 256 CUs busy, scaled to the CU budget)
-        pl.grid = NCU;                                // persistent: one 8-wave workgroup per CU
-        if (tiles < pl.grid) pl.grid = (int)((tiles + 7) / 8 * 8);
-        // Stream-K tail: T tiles over 256 blocks cost ceil(T/256) rounds; every C-wide output of the U-Net is 1800 / 900 / 452 tiles =
-        // 7.03 / 3.52 / 1.77 rounds paid as 8 / 4 / 2.  When the loss is worth it, the last (T mod 256) + 256 tiles are cut along K
-        // into 256 equal ranges instead (gemm3_kernel: contributor / finisher hand-over through the uncached workspace).
         constexpr int sk_min_k = 1280;
-        // Where it pays (A/B per shape on the U-Net's problems, same box): 3x3 convs at every level (-6 ... -10 %), dense / temporal
+        // Where the tail pays (A/B per shape on the U-Net's problems, same box): 3x3 convs at every level (-6 ... -10 %), dense / temporal
         // GEMMs with at most two tile columns and K >= 1280 (-4 ... -8 %).  With four tile columns (level 2) the blocks of an XCD
         // are out of phase along K and stop sharing the A rows and W slices in L2: +7 ... +16 % -- left on the whole-tile schedule.
         const bool sk_shape = p.mode == EW_A_CONV3X3 || (pl.q.tiles_n <= 2 && p.K >= sk_min_k);
-        if (sk_shape && sk_ok && tiles > NCU && tiles % NCU != 0) {
-            const long long rounds = (tiles + NCU - 1) / NCU;
-            const double loss = 1.0 - (double)tiles / ((double)NCU * rounds);
-            if (loss > 0.04 && (pl.w = ew_sk_workspace(SK_INST, s))) {       // no workspace: whole tiles
-                pl.sk.dp_rounds = (int)(tiles / NCU) - 1;
-                pl.sk.tiles = (int)(tiles - (long long)NCU * pl.sk.dp_rounds);
-            }
-        }
+        plan3_persistent(pl, tiles, NCU, sk_shape && sk_ok, s);
     } else {
         // Half split (round 4): problems with at most 128 tiles (the deepest level: M = 7200 -> 29 x 4 = 116 tiles) leave more than
         // half of the 256 CUs idle on the whole-tile schedule and used to run on generation 2's 256x160 tiles.  With a long K every
@@ -1034,3 +1078,26 @@ ew_status EW3_NAME(ew_gemm3_try)(const GemmP& p, hipStream_t s, bool* taken) {
     if (p.mode == EW_A_CONVT3) return dispatch_epi3<EW_A_CONVT3>(pl, s);
     return dispatch_epi3<EW_A_DENSE>(pl, s);
 }
+
+#if EW3_BN == 320
+// conv3x3 with upsample = 2 (validated by ew_gemm_f16: stride 1, one source, bias only, h_out = 2 h_in, w_out = 2 w_in, N % 320 == 0, w in the phase
+// pack).  p is the caller's problem (M output rows, K = 9 C); the kernel's copy is the four-phase problem of gemm_common.h.  Always generation 3:
+// the "too few tiles" and "M < 320" rules of plan3 are speed rules, and no other family reads the phase pack.
+ew_status ew_gemm3_convup2(const GemmP& p, hipStream_t s) {
+    Plan3 pl;
+    pl.epi = 16 | 1;                                  // bias-initialised accumulators, direct epilogue, hi (+ lo8) planes
+    pl.q = p;
+    pl.q.M = p.M / 4;
+    pl.q.K = 4 * p.c1;
+    const int NCU = ew_cu_budget();
+    const int per_phase = ew_cdiv(pl.q.M, BM);
+    const long long tiles = 4LL * per_phase * (p.N / BN);
+    EW_REQUIRE(tiles <= (long long)NCU * (ITEMS_BYTES / 16 - 4), "ew_gemm_f16: upsample = 2: %lld tiles exceed the work-item table of %d persistent blocks", tiles, NCU);
+    EW_REQUIRE((long long)p.M * p.ld_out * 2 < (1LL << 32), "ew_gemm_f16: upsample = 2 addresses its output with 32-bit byte offsets (M * ld_out * 2 < 4 GB)");
+    pl.q.tiles_m = 4 * per_phase; pl.q.tiles_n = p.N / BN;
+    pl.q.band = ((long long)p.N * pl.q.K * 2 > 3LL * 1024 * 1024) ? 4 : 0;
+    pl.sk = SkP{nullptr, nullptr, 0u, 0, 0}; pl.w = nullptr;
+    plan3_persistent(pl, tiles, NCU, !(p.dbg & 4), s);      // the tail as for the 3x3 convs
+    return dispatch_epi3<EW_A_CONVUP2>(pl, s);
+}
+#endif

@@ -27,6 +27,17 @@ struct GemmP {
     int dbg;   // ew_set_gemm_debug: bit 2 (value 4) = generation 3 runs the whole-tile schedule (no stream-K tail / half split)
 };
 
+// Internal A-mode of generation 3 (never in ew_gemm_args.mode: the caller passes EW_A_CONV3X3 with upsample = 2): the 3x3 conv over a nearest-x2
+// upsampled image as four 2x2 phase convs over the SOURCE image.  For a fixed output parity (a, b) = (oy & 1, ox & 1) the nine taps land on 2x2
+// source pixels, so the taps that share a pixel are summed once at load time (evoworld_amd.ops.pack_convup2_weight): K = 4 C instead of 9 C.
+//   GEMM row m  = source pixel (img, i, j), n_img * h_in * w_in rows per phase; the M tiles are phase-major (every row of a tile shares W):
+//                 tile row tm = phase * ceil(M / 256) + tile row inside the phase
+//   tap (r, c)  = source pixel (i + a - 1 + r, j + b - 1 + c), zero outside the source image (== outside the upsampled image for the 3x3 taps)
+//   W           = [4 phases (2a + b)][N][C/64 chunks][4 taps (2r + c)][64]
+//   output row  = (img, 2i + a, 2j + b) = 2m + 2 (m / w_in) w_in + 2 a w_in + b
+// The kernel's GemmP then carries M = rows per phase, K = 4 C and tiles_m = 4 * ceil(M / 256).
+constexpr int EW_A_CONVUP2 = 3;
+
 // generation 3, stream-K tail (gemm3_f16.hip), passed as a second kernel argument (GemmP is kept under 256 bytes: beyond that the
 // by-value kernel argument was copied to scratch instead of being read from the kernarg segment): the last `tiles` (G <= tiles <
 // 2G) output tiles are split along K over the G persistent blocks; 0 = off.  ws: uncached fp32 partial-accumulator slots, flags:
@@ -42,6 +53,7 @@ struct SkP {
 // try: the family decides once per call whether it takes the problem (*taken) and, if so, launches it
 ew_status ew_conv_small_n_try(const GemmP& p, hipStream_t s, bool* taken);   // conv_small_n.hip: 3x3 convs with N <= 16 (conv_out)
 ew_status ew_gemm3_try(const GemmP& p, hipStream_t s, bool* taken);          // gemm3_f16.hip, 256x320 tile
+ew_status ew_gemm3_convup2(const GemmP& p, hipStream_t s);                   // gemm3_f16.hip: conv3x3 with upsample = 2 (EW_A_CONVUP2), any tile count
 ew_status ew_gemm3_try_b256(const GemmP& p, hipStream_t s, bool* taken);     // gemm3_f16.hip compiled with EW3_BN=256
 ew_status ew_gemm2_dispatch(const GemmP& p, hipStream_t s);                  // gemm2_f16.hip: takes everything
 ew_status ew_gemm1_dispatch(const GemmP& p, hipStream_t s);                  // gemm_f16.hip: takes everything (the suite's cross-check)

@@ -17,6 +17,8 @@ void ew_gemm_note_kernel(const char* fmt, ...) {
     va_end(ap);
 }
 
+extern "C" int ew_gemm_convup2_ok(int N, int C) { return N > 0 && N % 320 == 0 && C > 0 && C % 64 == 0; }
+
 // operand sets that occur in the U-Net (evoworld_amd/unet.py); any other mask runs on the smallest compiled superset
 ew_status ew_gemm_select_epi(const GemmP& p, int generation, int* epi) {
     const bool dense = p.mode == EW_A_DENSE;
@@ -56,11 +58,18 @@ extern "C" ew_status ew_gemm_f16(const ew_gemm_args* a, void* stream) {
     if (a->mode == EW_A_CONV3X3) {
         taps = 9;
         EW_REQUIRE(a->n_img > 0 && a->h_in > 0 && a->w_in > 0 && a->h_out > 0 && a->w_out > 0 &&
-                       (a->stride == 1 || a->stride == 2) && (a->upsample == 0 || a->upsample == 1),
+                       (a->stride == 1 || a->stride == 2) && (a->upsample >= 0 && a->upsample <= 2),
                    "ew_gemm_f16: bad conv3x3 geometry");
         EW_REQUIRE((long long)a->n_img * a->h_out * a->w_out == a->M, "ew_gemm_f16: M != n_img*h_out*w_out");
         EW_REQUIRE(!(a->upsample && a->stride != 1), "ew_gemm_f16: upsample needs stride 1");
         EW_REQUIRE((a->conv_shift == 0 || a->conv_shift == 1) && !(a->conv_shift && a->upsample), "ew_gemm_f16: conv_shift must be 0 or 1 (not with upsample)");
+        if (a->upsample == 2) {      // four 2x2 phase convs over the source image, w in the phase pack (evoworld_hip.h)
+            EW_REQUIRE(!a->a2 && a->c2 == 0, "ew_gemm_f16: upsample = 2 reads one source (no a2 / c2)");
+            EW_REQUIRE(a->h_out == 2 * a->h_in && a->w_out == 2 * a->w_in, "ew_gemm_f16: upsample = 2 needs h_out = 2 h_in and w_out = 2 w_in (got %dx%d -> %dx%d)",
+                       a->h_in, a->w_in, a->h_out, a->w_out);
+            EW_REQUIRE(!a->rowbias && !a->r1 && !a->r2 && a->act == EW_ACT_NONE, "ew_gemm_f16: upsample = 2 is bias + (split) output only: no rowbias / r1 / r2 / act");
+            EW_REQUIRE(ew_gemm_convup2_ok(a->N, a->c1), "ew_gemm_f16: upsample = 2 runs on generation 3's 256x320 tile only: N %% 320 == 0 (N=%d c1=%d)", a->N, a->c1);
+        }
     } else if (a->mode == EW_A_CONVT3) {
         taps = 3;
         EW_REQUIRE(a->tB > 0 && a->tT > 0 && a->tP > 0 && (long long)a->tB * a->tT * a->tP == a->M,
@@ -91,6 +100,8 @@ extern "C" ew_status ew_gemm_f16(const ew_gemm_args* a, void* stream) {
     const int gen = ew_get_gemm_generation();
     bool taken = false;
     ew_status st = EW_OK;
+    // the four-phase form of the upsample conv has one kernel (generation 3), whichever generation is selected: no other family reads its weight pack
+    if (p.mode == EW_A_CONV3X3 && p.upsample == 2) return ew_gemm3_convup2(p, s);
     // 3x3 convs with a handful of output channels (conv_out: N = 4) have their own kernel (round 6); generation 1 stays the independent cross-check
     if (gen >= 2 && ((st = ew_conv_small_n_try(p, s, &taken)) || taken)) return st;
     // generation 3 (256x320 tile, then 256x256) where it applies and fills the chip, generation 2 otherwise

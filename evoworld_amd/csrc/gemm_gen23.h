@@ -8,12 +8,13 @@
 
 // ---------------- K walk of the A loaders: channel-chunk major, tap minor (dense / conv3x3 / temporal 3-tap) ----------------
 template <int MODE>
-constexpr int ew_a_ntap = MODE == EW_A_CONV3X3 ? 9 : (MODE == EW_A_CONVT3 ? 3 : 1);
+constexpr int ew_a_ntap = MODE == EW_A_CONV3X3 ? 9 : (MODE == EW_A_CONVUP2 ? 4 : (MODE == EW_A_CONVT3 ? 3 : 1));
 
-// wave-uniform pixel delta of tap `tap` against the centre tap
+// wave-uniform pixel delta of tap `tap` against the centre tap (EW_A_CONVUP2: against tap (0, 0) of the tile's phase, whose own delta the loader adds)
 template <int MODE>
 __device__ __forceinline__ int ew_a_tap_delta(const GemmP& p, int tap) {
     if constexpr (MODE == EW_A_CONV3X3) return (tap / 3 - 1) * p.w_in + (tap % 3 - 1);
+    else if constexpr (MODE == EW_A_CONVUP2) return (tap >> 1) * p.w_in + (tap & 1);
     else if constexpr (MODE == EW_A_CONVT3) return (tap - 1) * p.tP;
     else return 0;
 }
@@ -26,6 +27,10 @@ __device__ __forceinline__ int ew_a_tap_delta(const GemmP& p, int tap) {
 template <int GEN, int MODE, class Launch>
 ew_status ew_gemm_visit_variant(int epi, Launch&& launch) {
     constexpr bool D = MODE == EW_A_DENSE;
+    // the four-phase upsample conv (generation 3 only) is bias + split output and nothing else: one kernel
+    if constexpr (MODE == EW_A_CONVUP2) {
+        if (GEN == 3 && epi == (16 | 1)) return launch(std::integral_constant<int, (16 | 1)>{});
+    } else {
 #define EW_VARIANT(E, COMPILED)                                                        \
     case (E):                                                                          \
         if constexpr (COMPILED) return launch(std::integral_constant<int, (E)>{});     \
@@ -42,6 +47,7 @@ ew_status ew_gemm_visit_variant(int epi, Launch&& launch) {
         EW_VARIANT(3, D)
         EW_VARIANT(6, D)
         EW_VARIANT(7, true)
+    }
     }
 #undef EW_VARIANT
     ew_set_error("ew_gemm_f16: generation %d has no kernel <%d, %d>", GEN, MODE, epi);

@@ -1286,3 +1286,32 @@ def pack_conv_weight(w, cpad=None):
     taps = wt.shape[1]
     wt = wt.reshape(O, taps, I // 64, 64).permute(0, 2, 1, 3)       # [O, chunks, taps, 64]
     return wt.reshape(O, -1).to(torch.float16).contiguous()
+
+
+# 3x3 conv over a nearest-x2 upsampled image: for output parity a (0 / 1) along one axis, the kernel rows (columns) k that read source pixel
+# i + a - 1 + r, r = 0 / 1:  upsampled row 2i + a + k - 1 -> source row (2i + a + k - 1) >> 1
+CONVUP2_TAPS = (((0,), (1, 2)), ((0, 1), (2,)))
+
+
+def convup2_ok(N, C):
+    """ew_gemm_f16 runs a 3x3 conv with N output / C input channels as upsample=2 (four 2x2 phase convs, pack_convup2_weight)"""
+    return bool(_lib.load().ew_gemm_convup2_ok(int(N), int(C)))
+
+
+def pack_convup2_weight(w, dtype=torch.float16):
+    """[O, I, 3, 3] -> [4 * O, 4 * I]: the weights of ew_gemm_f16's upsample=2 form, [phase 2a+b][O][I/64 chunks][tap 2r+c][64 channels].
+    The taps of the 3x3 kernel that read the same source pixel for output parity (a, b) are summed in w's dtype (fp32 from a checkpoint) and
+    rounded to `dtype` once."""
+    O, I = w.shape[0], w.shape[1]
+    if tuple(w.shape[2:]) != (3, 3) or I % 64:
+        raise ValueError(f"pack_convup2_weight: expected [O, I % 64 == 0, 3, 3], got {tuple(w.shape)}")
+    ph = w.new_zeros(2, 2, O, 2, 2, I)                               # [a, b, O, r, c, I]
+    for a in range(2):
+        for b in range(2):
+            for r in range(2):
+                for c in range(2):
+                    for ky in CONVUP2_TAPS[a][r]:
+                        for kx in CONVUP2_TAPS[b][c]:
+                            ph[a, b, :, r, c] += w[:, :, ky, kx]
+    ph = ph.reshape(4, O, 4, I // 64, 64).permute(0, 1, 3, 2, 4)     # [phase, O, chunks, taps, 64]
+    return ph.reshape(4 * O, 4 * I).to(dtype).contiguous()

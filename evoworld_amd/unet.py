@@ -406,8 +406,12 @@ class UNetSpatioTemporalConditionModel(PackedModel):
         W["cv"] = (h(torch.cat(cv_w)), h(torch.cat(cv_b)))
         self._cv_total = off
 
-        for smp in [blk.down for blk in self.arch.downs if blk.down] + [blk.up for blk in self.arch.ups if blk.up]:
-            W[smp.p] = f.conv(smp.p)
+        for blk in self.arch.downs:
+            if blk.down:
+                W[blk.down.p] = f.conv(blk.down.p)
+        for blk in self.arch.ups:
+            if blk.up:              # (w, bias, upsample): four 2x2 phase convs (upsample = 2) where the channel counts allow, nine taps otherwise
+                W[blk.up.p] = f.conv_up(blk.up.p)
         if self.in_split:
             W["conv_in"] = (ops.pack_conv_weight(split_conv_in_weight(f32("conv_in.weight"), self.in_split)), h(f32("conv_in.bias")))
         else:
@@ -595,7 +599,8 @@ class UNetSpatioTemporalConditionModel(PackedModel):
                 if blk.attn:
                     h = self._transformer(blk.attn[l], h, cvecs, B, T, H, W_)
             if blk.up:
-                h = self._conv3x3(h.hi, *Wt[blk.up.p], N, H, W_, 2 * H, 2 * W_, upsample=1, res_out=True)
+                wu, bu, form = Wt[blk.up.p]
+                h = self._conv3x3(h.hi, wu, bu, N, H, W_, 2 * H, 2 * W_, upsample=form, res_out=True)
                 H, W_ = 2 * H, 2 * W_
             if taps is not None:
                 taps[f"up{bi}"] = (h.float(), H, W_)

@@ -44,6 +44,13 @@ const char* ew_last_error(void);
  *   EW_A_CONV3X3 m -> (img, oy, ox) on an [n_img, h_out, w_out] grid; tap = ky*3+kx;
  *                A(m, (tap, c))   = in[img, iy, ix, c], iy = oy*stride+ky-1, ix = ox*stride+kx-1, zero
  *                outside; with upsample=1 the input is read as nearest-x2 upsampled ([h_in,w_in] -> 2x).
+ *                upsample=2: the same conv (stride 1, h_out = 2 h_in, w_out = 2 w_in) as four 2x2 phase convs over the SOURCE image:
+ *                for output parity (a, b) = (oy & 1, ox & 1) the nine taps land on 2x2 source pixels, so `w` holds, per phase, the
+ *                sums of the taps that share a pixel: [4 phases 2a+b][N][c1/64][4 taps 2r+c][64], tap (r, c) = source pixel
+ *                (oy/2 + a-1+r, ox/2 + b-1+c), rows ky of 3x3 kernel row group r: a=0: {0} {1,2}, a=1: {0,1} {2}; columns likewise
+ *                (evoworld_amd.ops.pack_convup2_weight).  K = 4 c1: 4/9 of the MFMA work.  One source (no a2 / c2), bias only
+ *                (no rowbias / r1 / r2 / act), out / out_lo; N and c1 as ew_gemm_convup2_ok says; runs on generation 3 whatever
+ *                ew_set_gemm_generation selected.  M, c1 and mode are the caller's 3x3 problem (M = n_img*h_out*w_out).
  *   EW_A_CONVT3  m -> (b, t, p) on a [B, T, P] grid; A(m, (kt, c)) = in[b, t+kt-1, p, c], zero outside.
  * In the conv modes channels [0,c1) come from `a`, [c1,c1+c2) from `a2` (the up-block skip concat,
  * evoworld/trainer/unet_plucker.py:458-475 + diffusers up blocks) without materialising the concat.
@@ -92,6 +99,9 @@ typedef struct ew_gemm_args {
 } ew_gemm_args;
 
 ew_status ew_gemm_f16(const ew_gemm_args* args, void* stream);
+/* 1 if ew_gemm_f16 runs EW_A_CONV3X3 with upsample = 2 for N output and C input channels (N % 320 == 0, C % 64 == 0), else 0: a weight loader asks
+ * once per layer and packs either the phase form or the nine taps. */
+int ew_gemm_convup2_ok(int N, int C);
 /* Kernel generation behind ew_gemm_f16: 1 = 128x160 tile, 2 blocks/CU; 2 = persistent 3-stage ring, 256x160 / 128x256 tiles;
  * 3 (default) = persistent 256x320 (and 256x256) tile with a stream-K tail where N % 320 == 0 (or
  * N % 256 == 0) and the problem fills the chip, generation 2 for everything else.  Same arguments, same results to rounding;

@@ -24,13 +24,15 @@ import sys
 
 R_MFMA, R_ATTN, R_HBM = 1300e12, 1225e12, 5.3e12
 P_MFMA, P_HBM, NOMINAL_GHZ = 2500e12, 8.0e12, 2.4         # the true roofline (MI355X_MICROARCH.md)
-TAPS = {"0": 1, "1": 9, "2": 3}
+TAPS = {"0": 1, "1": 9, "2": 3, "3": 9}       # "3": the four-phase upsample conv (gemm3_kernel<3, 17>), reported with the caller's K = 9 C
 
 
 def gemm_bytes(M, N, K, mode, epi):
     cin = K // TAPS[mode]
     a = M * cin * 2
     w = N * K * 2
+    if mode == "3":                                          # four phase packs of 4 C each
+        w = N * (K // 9) * 16 * 2
     split = bool(epi & 16)
     n_out = N // 2 if epi & 8 else N
     out = M * n_out * (3 if split else 2)
@@ -67,6 +69,8 @@ def main(path, clock=None, vendor_path=None):
             mode, epi = e[-2], int(e[-1])
             M, N, K = int(kv["M"]), int(kv["N"]), int(kv["K"])
             fl, by = 2.0 * M * N * K, gemm_bytes(M, N, K, mode, epi)
+            if mode == "3":                                  # 4 of the 9 taps' worth of MFMA work: the phase sums were formed at load time
+                fl *= 4.0 / 9.0
             vk = (M, N, K)
         elif name == "attn_spatial_kernel":
             S = int(kv["S"])
