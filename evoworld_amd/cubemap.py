@@ -7,20 +7,16 @@
       every NNN_{face}.png set of --input -> NNN.png, a W x H panorama.
   --device_png (either command) encodes the output files on the device (evoworld_amd.png) instead of by Pillow.
 
-PNG decoding runs on at most 16 threads and is streamed to the device one batch at a time (as metrics.evaluate does); every
-batch is one launch per stage.
+PNG decoding (and Pillow's encoding) runs on at most 16 threads (evoworld_amd.frames) and is streamed to the device one batch at a
+time (as metrics.evaluate does); every batch is one launch per stage.
 """
 import argparse
 import os
 import sys
-from concurrent.futures import ThreadPoolExecutor
 
-import numpy as np
-import torch
-
+from . import frames
 from . import reprojection as RP
 
-MAX_DECODE_THREADS = 16
 BATCH = 25
 FACES = RP.CUBEMAP_FACE_NAMES
 
@@ -47,37 +43,18 @@ def parse_args(argv=None):
     return args
 
 
-def _decode(path):
-    from PIL import Image
-    with Image.open(path) as im:
-        return np.asarray(im.convert("RGB"))
-
-
-def _save(path, arr):
-    from PIL import Image
-    Image.fromarray(arr).save(path)
-
-
-def _save_on_device(paths, frames_u8):
-    from .png import write_png_files
-    write_png_files(paths, frames_u8.contiguous())
-
-
 def _batches(items, n=BATCH):
     for i in range(0, len(items), n):
         yield items[i:i + n]
 
 
-def _stack(frames, names):
-    shapes = {f.shape for f in frames}
-    if len(shapes) != 1:
-        raise ValueError(f"images of one batch differ in size ({sorted(shapes)}), first file {names[0]}")
-    return torch.from_numpy(np.stack(frames))
+def _paths(folder, stems, suffix=""):
+    return [os.path.join(folder, f"{s}{suffix}.png") for s in stems]
 
 
 def panorama_stems(folder):
     """NNN of every NNN.png that is not itself an output of this tool"""
-    return sorted(f[:-4] for f in os.listdir(folder) if f.lower().endswith(".png") and "_" not in f)
+    return sorted(f[:-4] for f in frames.list_images(folder, (".png",)) if "_" not in f)
 
 
 def face_stems(folder):
@@ -91,22 +68,13 @@ def to_cubemap(args, device="cuda"):
     stems = panorama_stems(args.input)
     if not stems:
         raise ValueError(f"no NNN.png panoramas under {args.input}")
-    os.makedirs(args.output, exist_ok=True)
-    with ThreadPoolExecutor(max_workers=min(MAX_DECODE_THREADS, os.cpu_count() or 1)) as pool:
-        for batch in _batches(stems):
-            x = _stack(list(pool.map(_decode, [os.path.join(args.input, s + ".png") for s in batch])), batch).to(device)
-            if args.size is not None:
-                x = RP.resize_u8(x, args.size[1], args.size[0], "bilinear")
-            cross, faces = RP.panorama_to_cubemap(x, not args.nearest, args.scale_factor)
-            if args.device_png:
-                _save_on_device([os.path.join(args.output, f"{s}_cubemap.png") for s in batch], cross)
-                for n in FACES:
-                    _save_on_device([os.path.join(args.output, f"{s}_{n}.png") for s in batch], faces[n])
-                continue
-            out = [(os.path.join(args.output, f"{s}_cubemap.png"), c) for s, c in zip(batch, cross.cpu().numpy())]
-            for n in FACES:
-                out += [(os.path.join(args.output, f"{s}_{n}.png"), f) for s, f in zip(batch, faces[n].cpu().numpy())]
-            list(pool.map(lambda pa: _save(*pa), out))
+    for batch in _batches(stems):
+        x = frames.read_frames(_paths(args.input, batch), device)
+        if args.size is not None:
+            x = RP.resize_u8(x, args.size[1], args.size[0], "bilinear")
+        cross, faces = RP.panorama_to_cubemap(x, not args.nearest, args.scale_factor)
+        for name, frames_u8 in {"cubemap": cross, **faces}.items():
+            frames.write_frames(_paths(args.output, batch, f"_{name}"), frames_u8, args.device_png, frames.MAX_DECODE_THREADS)
     return len(stems)
 
 
@@ -114,16 +82,10 @@ def to_pano(args, device="cuda"):
     stems = face_stems(args.input)
     if not stems:
         raise ValueError(f"no complete NNN_{{face}}.png sets under {args.input}")
-    os.makedirs(args.output, exist_ok=True)
-    with ThreadPoolExecutor(max_workers=min(MAX_DECODE_THREADS, os.cpu_count() or 1)) as pool:
-        for batch in _batches(stems):
-            faces = {n: _stack(list(pool.map(_decode, [os.path.join(args.input, f"{s}_{n}.png") for s in batch])), batch).to(device)
-                     for n in FACES}
-            pano = RP.cubemap_to_panorama(faces, args.size[0], args.size[1], args.scale_factor)
-            if args.device_png:
-                _save_on_device([os.path.join(args.output, s + ".png") for s in batch], pano)
-                continue
-            list(pool.map(lambda pa: _save(*pa), [(os.path.join(args.output, s + ".png"), p) for s, p in zip(batch, pano.cpu().numpy())]))
+    for batch in _batches(stems):
+        faces = {n: frames.read_frames(_paths(args.input, batch, f"_{n}"), device) for n in FACES}
+        pano = RP.cubemap_to_panorama(faces, args.size[0], args.size[1], args.scale_factor)
+        frames.write_frames(_paths(args.output, batch), pano, args.device_png, frames.MAX_DECODE_THREADS)
     return len(stems)
 
 

@@ -14,6 +14,7 @@ import os
 import numpy as np
 import torch
 
+from . import frames
 from .geometry import UNITY_TO_OPENCV
 
 POS_SCALE = 0.1            # CameraTrajDataset default (dataset/CameraTrajDataset.py:223)
@@ -36,20 +37,15 @@ def load_camera_poses(episode_path):
     return np.asarray(rows, dtype=float) * np.asarray(UNITY_TO_OPENCV, dtype=float)
 
 
-def _open_rgb(path):
-    from PIL import Image
-    if not os.path.exists(path):
-        alt = os.path.splitext(path)[0] + ".jpg"                     # the reference falls back to .jpg (:430-433)
-        if os.path.exists(alt):
-            path = alt
-    return np.array(Image.open(path).convert("RGB"))
+def _load_u8(paths, device):
+    """image files (a missing X.png read from X.jpg) of equal sizes -> uint8 [N,H,W,3] on the device"""
+    return frames.stack_frames([frames.decode_rgb(p, jpg_fallback=True) for p in paths], device, paths[0])
 
 
-def _to_pixel_values(arrays, height, width, device):
-    """list of uint8 [H,W,3] (equal sizes) -> fp32 [N,3,height,width] in [-1,1] on the device (Pillow-exact resize)."""
+def _to_pixel_values(paths, height, width, device):
+    """image files of equal sizes -> fp32 [N,3,height,width] in [-1,1] on the device (Pillow-exact resize)."""
     from . import reprojection as RP
-    u8 = torch.tensor(np.stack(arrays)).to(device)
-    return RP.memory_to_pixel_values(u8, height, width)
+    return RP.memory_to_pixel_values(_load_u8(paths, device), height, width)
 
 
 def load_single_segment_batch(episode_path, height=576, width=1024, device="cuda", sequence_length=SEQUENCE_LENGTH,
@@ -70,10 +66,10 @@ def load_single_segment_batch(episode_path, height=576, width=1024, device="cuda
         pix = torch.zeros(sequence_length, 3, height, width, device=device)
         mem = torch.zeros(sequence_length, 3, height, width, device=device)
     else:
-        pix = _to_pixel_values([_open_rgb(os.path.join(episode_path, "panorama", f"{i:03}.png")) for i in ids], height, width, device)
-        names = sorted(f for f in os.listdir(rdir) if f.endswith(".png"))
-        renders = [_open_rgb(os.path.join(rdir, f"{i:02}.png")) for i in range(len(names))]      # :478-505
-        first = _to_pixel_values([_open_rgb(os.path.join(episode_path, "panorama", "001.png"))], height, width, device)
+        pix = _to_pixel_values([os.path.join(episode_path, "panorama", f"{i:03}.png") for i in ids], height, width, device)
+        names = [f for f in frames.list_images(rdir, (".png",)) if f.endswith(".png")]           # lower-case .png only
+        renders = frames.numbered_paths(rdir, len(names), first=0, digits=2)                     # :478-505
+        first = _to_pixel_values([os.path.join(episode_path, "panorama", "001.png")], height, width, device)
         # first frame inserted at 0 (:506-514).  With sequence_length < 25 (BASELINE configs[0]: 8 frames) the reference's dataset still returns all
         # 1 + 24 memory frames and its pipeline then fails the channel concat at pipeline_evoworld.py:643; here the memory is cut to the window
         # length ([001] + renders 00 .. sequence_length - 2), which for the default 25 is the identity
@@ -92,7 +88,7 @@ def load_complete_episode_batch(episode_path, height=576, width=1024, device="cu
     traj[:, :3] *= pos_scale
     f = os.path.join(episode_path, "panorama", "001.png")
     if os.path.isfile(f) or os.path.isfile(f[:-4] + ".jpg"):
-        first = _to_pixel_values([_open_rgb(f)], height, width, device)[0]
+        first = _to_pixel_values([f], height, width, device)[0]
     else:
         first = None
     return {"first_frame": first, "cam_traj": traj[None], "camera_params": cam, "episode_path": [episode_path]}
@@ -104,17 +100,17 @@ def load_gt_window_u8(episode_path, start_idx, end_idx, height=576, width=1024, 
     resized on the device -> uint8 [n,height,width,3].  The window stops at the first missing panorama (or at n_poses); None
     when the episode has no panorama for the window's first id (synthetic and pose-only episodes)."""
     from . import reprojection as RP
-    arrays = []
+    paths = []
     for i in range(start_idx + 1, end_idx + 1):
         if n_poses is not None and i > n_poses:
             break
         f = os.path.join(episode_path, "panorama", f"{i:03}.png")
         if not (os.path.isfile(f) or os.path.isfile(f[:-4] + ".jpg")):
             break
-        arrays.append(_open_rgb(f))
-    if not arrays:
+        paths.append(f)
+    if not paths:
         return None
-    u8 = torch.tensor(np.stack(arrays)).to(device)
+    u8 = _load_u8(paths, device)
     Hi, Wi = u8.shape[1:3]
     if (Hi, Wi) == (height, width):
         return u8.contiguous()

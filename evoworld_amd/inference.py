@@ -19,12 +19,14 @@ File output (PNG dumps) is optional and off the hot path.
 """
 import logging
 import os
-from types import SimpleNamespace
 
 import numpy as np
 import torch
 
+from . import ops
 from . import reprojection as RP
+from .dataset import load_gt_window_u8
+from .frames import numbered_paths, pil_to_rgb, write_numbered
 from .geometry import UNITY_TO_OPENCV, xyz_euler_to_four_by_four_matrix_batch, xyz_euler_to_three_by_four_matrix_batch
 from .mvs import call_depth_model
 from .plucker import equirectangular_to_ray, ray_c2w_to_plucker
@@ -58,8 +60,8 @@ def process_batch(batch, args, pipeline, rays, weight_dtype=torch.float32, outpu
     if output_path and isinstance(frames, list):
         d = os.path.join(output_path, episode, "predictions")
         os.makedirs(d, exist_ok=True)
-        for i, f in enumerate(frames[0]):
-            f.save(os.path.join(d, f"{i + 1:03}.png"))
+        for f, path in zip(frames[0], numbered_paths(d, len(frames[0]))):
+            f.save(path)
     return frames
 
 
@@ -120,8 +122,7 @@ class Navigator:
         """the window's last generated frame as the next window's start image (navigator :436-437: movement[-1] through
         the ToTensor + rescale transform)"""
         if isinstance(frames, list):                      # PIL clips [[img]*T]
-            arr = np.asarray(frames[0][n - 1].convert("RGB"))
-            return (torch.from_numpy(arr.copy()).permute(2, 0, 1).float() / 255.0 * 2 - 1).cuda()
+            return (torch.from_numpy(pil_to_rgb(frames[0][n - 1])).permute(2, 0, 1).float() / 255.0 * 2 - 1).cuda()
         raise NotImplementedError("chaining windows needs decoded frames (output_type='pil'); with output_type='latent' "
                                   "run one window per call (infer_segment=True), as process_episode does")
 
@@ -134,8 +135,7 @@ class Navigator:
         parts = []
         for frames, n in self.generations:
             if isinstance(frames, list):
-                arr = np.stack([np.asarray(f.convert("RGB")) for f in frames[0][:n]])
-                u8 = torch.from_numpy(arr).cuda()
+                u8 = torch.from_numpy(np.stack([pil_to_rgb(f) for f in frames[0][:n]])).cuda()
             elif isinstance(frames, np.ndarray) and frames.dtype == np.uint8 and frames.ndim == 5:
                 u8 = torch.from_numpy(np.ascontiguousarray(frames[0][:n])).cuda()
             elif isinstance(frames, torch.Tensor) and frames.ndim == 5 and frames.shape[2] == 3:
@@ -204,7 +204,6 @@ class Navigator:
         """Yaw rotation of one panorama (navigator_evoworld.py:466-512), bit-exact, one kernel (ew_pano_yaw_rotate): image fp32
         [3,H,W] or the 8-bit frame uint8 [H,W,3] (converted x/255*2-1 in the same pass) -> fp32 [3,H,W].  Unlike a plain
         integer roll the map is not the identity even at 0 degrees: callers rotate only for a non-zero turn, as the reference."""
-        from . import ops
         return ops.pano_yaw_rotate(image[None].contiguous(), torch.as_tensor(rotation_degrees, dtype=torch.float32).reshape(1))[0]
 
     @staticmethod
@@ -214,8 +213,7 @@ class Navigator:
             if x.dtype != torch.uint8 or x.ndim not in (3, 4) or x.shape[-1] != 3:
                 raise TypeError(f"{what}: expected a PIL image or a device uint8 [H,W,3] / [V,H,W,3] tensor, got {x.dtype} {tuple(x.shape)}")
             return (x[None] if x.ndim == 3 else x), ("frame" if x.ndim == 3 else "clip")
-        arr = np.asarray(x.convert("RGB"))
-        return torch.from_numpy(arr.copy())[None].cuda(), "pil"
+        return torch.from_numpy(pil_to_rgb(x))[None].cuda(), "pil"
 
     @staticmethod
     def _like(t, kind):
@@ -262,7 +260,6 @@ class Navigator:
         if rotation_degrees != 0:
             return cls.rotate_panorama(image, rotation_degrees)
         if image.dtype == torch.uint8:
-            from . import ops
             return ops.u8_hwc_to_f32_chw(image[None].contiguous())[0]
         return image
 
@@ -389,11 +386,14 @@ class UnifiedLoopConsistencyPipeline:
         beside navigated.avi): the pair calculate_scores.py loads per episode (there as .mp4).  The returned frames do not depend on it.
         With png_on_device (opt-in) every PNG named above -- the per-segment dumps and the memory panoramas -- is encoded on the device
         (evoworld_amd.png): same names, the same pixels for any decoder, other file bytes than Pillow's."""
-        from . import ops
         dev = start_image.device
         camera_params = np.asarray(camera_params, dtype=np.float64)
         cam_t = torch.tensor(camera_params, dtype=torch.float32, device=dev)
         cam_t[:, :3] *= pos_scale
+        gt_window = lambda a, b: None if episode_path is None else load_gt_window_u8(episode_path, a, b, self.height, self.width, dev,
+                                                                                     len(camera_params))
+        out = _EpisodeOutputs(save_dir, save_segment_frames, export_memory, save_video and {"fps": video_fps, "quality": video_quality},
+                              png_on_device, stride=self.num_frames - 1, gt_window=gt_window)
         all_u8 = None
         memory = torch.zeros(self.num_frames, 3, self.height, self.width, device=dev)       # 'empty_with_traj' memory
         if not self.curve_path:
@@ -426,45 +426,25 @@ class UnifiedLoopConsistencyPipeline:
                 frames_u8 = frames_u8[:n]                                               # frames[:num_frames] (navigator :223)
             if all_u8 is not None:
                 frames_u8 = frames_u8[1:]                                               # drop the duplicated first frame (:427-429)
-            if save_dir and save_segment_frames:                                        # :432-435, file index continues across segments
-                _save_u8_frames(frames_u8, os.path.join(save_dir, f"predictions_{seg}"), seg * (self.num_frames - 1), png_on_device)
-                if episode_path is not None:                                            # :437-439
-                    from .dataset import load_gt_window_u8
-                    gt = load_gt_window_u8(episode_path, start_idx, end_idx, self.height, self.width, dev, len(camera_params))
-                    if gt is not None:
-                        _save_u8_frames(ops.gt_dump_map_u8(gt), os.path.join(save_dir, f"predictions_gt_{seg}"),
-                                        seg * (self.num_frames - 1), png_on_device)
+            out.segment(seg, frames_u8, start_idx, end_idx)                             # :432-439
             all_u8 = frames_u8 if all_u8 is None else torch.cat([all_u8, frames_u8], dim=0)
             if seg < self.num_segments - 1:
                 pers, target_yaws = self.convert_pano_to_pers(all_u8, camera_params, seg)
-                if save_dir and save_segment_frames:
-                    _save_u8_frames(pers, os.path.join(save_dir, f"perspective_look_at_center_{seg}"), 0, png_on_device)   # :449-453
+                out.perspective(seg, pers)                                                # :449-453
                 temp_cam = camera_params.copy()
                 s = max(0, end_idx - len(target_yaws))
                 temp_cam[s:end_idx, 4] = target_yaws[: end_idx - s]                        # :456-459
                 preds = call_depth_model(self.depth_model, pers, camera_params, seg)    # a stage that wants them also gets the views' poses
                 poses = xyz_euler_to_four_by_four_matrix_batch(torch.tensor(temp_cam, dtype=torch.float32), relative=True)
-                outdir = os.path.join(save_dir or "", f"rendered_panorama_vggt_open3d_{seg}")
-                glb = None
-                if export_memory and save_dir:
-                    os.makedirs(save_dir, exist_ok=True)
-                    glb = os.path.join(save_dir, f"glbscene_{seg}.glb")
+                outdir, glb, save_png = out.memory(seg)
                 panos = RP.predictions_to_target_view(preds, poses.numpy(), conf_thres=50.0, prediction_mode="depth_unproject",
                                                       num_target_view=24, outdir=outdir, cubemap_renderer=_Sized(self.renderer, self.pano_size),
-                                                      return_device_tensor=True, save_png=bool(save_dir), voxel_size=memory_voxel_size,
+                                                      return_device_tensor=True, save_png=save_png, voxel_size=memory_voxel_size,
                                                       export_glb=glb, png_on_device=png_on_device)
                 mem24 = RP.memory_to_pixel_values(panos, self.height, self.width)           # [24,3,H,W]
                 memory = torch.cat([start_image[None], mem24], dim=0)                      # [episode frame 1] + 24 reprojected (:277-279)
         self.last_frames_u8 = all_u8
-        if save_video and save_dir:
-            from .video import write_video
-            os.makedirs(save_dir, exist_ok=True)
-            write_video(os.path.join(save_dir, "navigated.avi"), all_u8, fps=video_fps, quality=video_quality)
-            if episode_path is not None:
-                from .dataset import load_gt_window_u8
-                gt = load_gt_window_u8(episode_path, 0, all_u8.shape[0], self.height, self.width, dev, len(camera_params))
-                if gt is not None:
-                    write_video(os.path.join(save_dir, "original.avi"), gt, fps=video_fps, quality=video_quality)
+        out.finish(all_u8)
         return ops.u8_hwc_to_f32_chw(all_u8)
 
 
@@ -490,17 +470,48 @@ def check_path_episode(run_lengths, n_poses, num_segments, num_frames=25):
                              f"but the episode has {n_poses} poses")
 
 
-def _save_u8_frames(u8_hwc, d, start=0, png_on_device=False):
-    """NNN.png (1-based, offset by `start`) dumps of uint8 [F,H,W,3] frames (unified_loop_consistency.py:104-108,432-453);
-    png_on_device: encoded by evoworld_amd.png instead of Pillow"""
-    if png_on_device:
-        from .png import write_png_frames
-        write_png_frames(d, u8_hwc, start)
-        return
-    from PIL import Image
-    os.makedirs(d, exist_ok=True)
-    for i, f in enumerate(u8_hwc.cpu().numpy()):
-        Image.fromarray(f).save(os.path.join(d, f"{i + start + 1:03}.png"))
+# What an episode leaves under save_dir (unified_loop_consistency.py:432-453, 487-492; T frames per segment); nothing without one:
+#   predictions_{seg}/NNN.png                   the segment's new frames, NNN going on at seg * (T - 1) + 1          save_segment_frames
+#   predictions_gt_{seg}/NNN.png                their ground truth, numbered alike, where the episode has panoramas  save_segment_frames
+#   perspective_look_at_center_{seg}/NNN.png    the views handed to the depth stage, from 001                        save_segment_frames
+#   rendered_panorama_vggt_open3d_{seg}/NN.png  the 24 memory panoramas of the hand-off, from 00                     any save_dir
+#   glbscene_{seg}.glb                          the 3D memory of the hand-off                                        export_memory
+#   navigated.avi, original.avi                 all generated frames; their ground truth, where there is one         save_video
+class _EpisodeOutputs:
+    """Every file name and every `if save_dir` of process_episode.  video: write_video's keywords or None; stride: T - 1;
+    gt_window(first, end): the ground-truth frames uint8 [n,H,W,3] of poses first .. end - 1, or None."""
+
+    def __init__(self, save_dir, segment_frames, export_memory, video, png_on_device, stride, gt_window):
+        self.dir, self.png_on_device, self.stride, self.gt_window = save_dir, png_on_device, stride, gt_window
+        self.dumps, self.glb, self.video = bool(save_dir and segment_frames), bool(save_dir and export_memory), save_dir and video
+
+    def segment(self, seg, frames_u8, start_idx, end_idx):
+        if self.dumps:
+            write_numbered(os.path.join(self.dir, f"predictions_{seg}"), frames_u8, seg * self.stride, self.png_on_device)
+            gt = self.gt_window(start_idx, end_idx)
+            if gt is not None:
+                write_numbered(os.path.join(self.dir, f"predictions_gt_{seg}"), ops.gt_dump_map_u8(gt), seg * self.stride, self.png_on_device)
+
+    def perspective(self, seg, pers):
+        if self.dumps:
+            write_numbered(os.path.join(self.dir, f"perspective_look_at_center_{seg}"), pers, 0, self.png_on_device)
+
+    def memory(self, seg):
+        """(outdir, glb path or None, save_png) of predictions_to_target_view.  outdir is more than a destination: its _{seg} suffix selects
+        the target poses (SceneBuilder.align_extrinsics), so it is named even when nothing is saved."""
+        if self.glb:
+            os.makedirs(self.dir, exist_ok=True)
+        return (os.path.join(self.dir or "", f"rendered_panorama_vggt_open3d_{seg}"),
+                os.path.join(self.dir, f"glbscene_{seg}.glb") if self.glb else None, bool(self.dir))
+
+    def finish(self, all_u8):
+        if self.video:
+            from .video import write_video
+            os.makedirs(self.dir, exist_ok=True)
+            write_video(os.path.join(self.dir, "navigated.avi"), all_u8, **self.video)
+            gt = self.gt_window(0, all_u8.shape[0])
+            if gt is not None:
+                write_video(os.path.join(self.dir, "original.avi"), gt, **self.video)
 
 
 class _Sized:

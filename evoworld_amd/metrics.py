@@ -28,13 +28,13 @@ import math
 import os
 import sys
 import time
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
+from .frames import read_frames
+
 SEQUENCE = 25                  # read_video_our keeps the last 25 frames of each folder (:191)
-MAX_DECODE_THREADS = 16
 NOT_COMPUTED = {
     "fvd": "needs the I3D network (styleganv i3d_torchscript weights) and its code, absent from this project; no network access",
     "lpips": "needs the LPIPS network (AlexNet backbone and linear-layer weights) and its package, absent; no network access",
@@ -288,12 +288,6 @@ def frame_pairs(data_path, episode, gt_subdir, gen_subdir, pair_by_name=False):
     return [os.path.join(gd, f) for f in gt], [os.path.join(nd, f) for f in gen]
 
 
-def _decode(path):
-    from PIL import Image
-    with Image.open(path) as im:
-        return np.asarray(im.convert("RGB"))
-
-
 def evaluate(args, device="cuda"):
     """main(args) of calculate_all_metrics.py:209-236 for PSNR / SSIM: one episode at a time is decoded (thread pool) and streamed
     to the device as uint8.  Returns (result dict, timing dict)."""
@@ -320,46 +314,44 @@ def evaluate(args, device="cuda"):
         raise ValueError(f"no episode folders under {args.data_path}")
     psnr, ssim, ws_psnr, ws_ssim, shape, n_videos = [], [], [], [], None, 0
     t_decode = t_device = 0.0
-    with ThreadPoolExecutor(max_workers=min(MAX_DECODE_THREADS, os.cpu_count() or 1)) as pool:
-        for ep in episodes:
-            gp, np_ = frame_pairs(args.data_path, ep, args.gt_subdir, args.gen_subdir, args.pair_by_name)
-            t0 = time.perf_counter()
-            frames = list(pool.map(_decode, gp + np_))
-            gt, gen = np.stack(frames[:len(gp)]), np.stack(frames[len(gp):])
-            t1 = time.perf_counter()
-            if gt.shape != gen.shape:
-                raise ValueError(f"episode {ep}: ground-truth frames {gt.shape} and generated frames {gen.shape} differ")
-            if shape is not None and gt.shape != shape:
-                raise ValueError(f"episode {ep}: frames {gt.shape} differ from the first episode's {shape}")
-            shape = gt.shape
-            gt_d, gen_d = torch.from_numpy(gt).to(device), torch.from_numpy(gen).to(device)
-            clips = [(gt_d, gen_d)]
-            if projection == "cube":                                             # every (episode, face) is one video of every metric
-                clips = list(zip(cube_viewports(gt_d, viewport_size), cube_viewports(gen_d, viewport_size)))
-            for gt_c, gen_c in clips:
-                p, s = video_metrics_u8(gt_c, gen_c)
-                psnr.append(p)
-                ssim.append(s)
-                if ws_what:
-                    wp, wsm = video_metrics_ws_u8(gt_c, gen_c, ws_what)
-                    ws_psnr.append(wp)
-                    ws_ssim.append(wsm)
-                if "lpips" in names:
-                    lpips.append(lpips_model(gt_c, gen_c, lpips_order).cpu().numpy())
-                if "ws_lpips" in names:
-                    ws_lpips.append(lpips_model(gt_c, gen_c, lpips_order, row_weights=latitude_weights(gt_c.shape[1])).cpu().numpy())
-                if fvd_model is not None:
-                    if gt.shape[0] < 10:
-                        raise ValueError(f"episode {ep}: FVD compares clips of 10 frames and more, the folders hold {gt.shape[0]}")
-                    for feats, clip in zip(fvd_feats, (gt_c, gen_c)):            # ground truth first, as the reference's main
-                        for L, v in fvd_mod.clip_features(fvd_model, clip, fvd_order).items():
-                            feats.setdefault(L, []).append(v)
-                if latent_model is not None:                                     # one pass per clip serves both metrics
-                    for feats, clip in zip(latent_feats, (gt_c, gen_c)):
-                        feats.append(latent_model.features(clip, latent_order).cpu().numpy())
-            n_videos += len(clips)
-            t_device += time.perf_counter() - t1
-            t_decode += t1 - t0
+    for ep in episodes:
+        gp, np_ = frame_pairs(args.data_path, ep, args.gt_subdir, args.gen_subdir, args.pair_by_name)
+        t0 = time.perf_counter()
+        gt_d, gen_d = read_frames(gp, device), read_frames(np_, device)      # decode (thread pool) + upload, timed as decode
+        t1 = time.perf_counter()
+        gt_shape = tuple(gt_d.shape)
+        if gt_d.shape != gen_d.shape:
+            raise ValueError(f"episode {ep}: ground-truth frames {gt_shape} and generated frames {tuple(gen_d.shape)} differ")
+        if shape is not None and gt_shape != shape:
+            raise ValueError(f"episode {ep}: frames {gt_shape} differ from the first episode's {shape}")
+        shape = gt_shape
+        clips = [(gt_d, gen_d)]
+        if projection == "cube":                                             # every (episode, face) is one video of every metric
+            clips = list(zip(cube_viewports(gt_d, viewport_size), cube_viewports(gen_d, viewport_size)))
+        for gt_c, gen_c in clips:
+            p, s = video_metrics_u8(gt_c, gen_c)
+            psnr.append(p)
+            ssim.append(s)
+            if ws_what:
+                wp, wsm = video_metrics_ws_u8(gt_c, gen_c, ws_what)
+                ws_psnr.append(wp)
+                ws_ssim.append(wsm)
+            if "lpips" in names:
+                lpips.append(lpips_model(gt_c, gen_c, lpips_order).cpu().numpy())
+            if "ws_lpips" in names:
+                ws_lpips.append(lpips_model(gt_c, gen_c, lpips_order, row_weights=latitude_weights(gt_c.shape[1])).cpu().numpy())
+            if fvd_model is not None:
+                if shape[0] < 10:
+                    raise ValueError(f"episode {ep}: FVD compares clips of 10 frames and more, the folders hold {shape[0]}")
+                for feats, clip in zip(fvd_feats, (gt_c, gen_c)):            # ground truth first, as the reference's main
+                    for L, v in fvd_mod.clip_features(fvd_model, clip, fvd_order).items():
+                        feats.setdefault(L, []).append(v)
+            if latent_model is not None:                                     # one pass per clip serves both metrics
+                for feats, clip in zip(latent_feats, (gt_c, gen_c)):
+                    feats.append(latent_model.features(clip, latent_order).cpu().numpy())
+        n_videos += len(clips)
+        t_device += time.perf_counter() - t1
+        t_decode += t1 - t0
     T, H, W, C = shape
     if projection == "cube":
         H = W = int(viewport_size) if viewport_size else W // 4

@@ -186,12 +186,11 @@ class PlaneSweepDepth:
 
 # ------------------------------------------------------------------ command line
 def _load_frames(folder, n, device):
-    from PIL import Image
-    names = sorted(f for f in os.listdir(folder) if f.lower().endswith((".png", ".jpg")))
+    from .frames import list_images, read_frames
+    names = list_images(folder, (".png", ".jpg"))
     if not names:
         raise SystemExit(f"no .png / .jpg frames under {folder}")
-    names = names[:n] if n else names
-    return torch.from_numpy(np.stack([np.array(Image.open(os.path.join(folder, f)).convert("RGB")) for f in names])).to(device)
+    return read_frames([os.path.join(folder, f) for f in (names[:n] if n else names)], device)
 
 
 def _cloud_main(args):

@@ -19,7 +19,9 @@ import zlib
 
 import numpy as np
 
-NLIT, NDIST, NCLC = 286, 30, 19
+from .frames import list_images, numbered_paths, read_frames
+
+NLIT,NDIST, NCLC = 286, 30, 19
 MAX_BITS, MAX_CLC_BITS = 15, 7
 END_OF_BLOCK = 256
 CLC_ORDER = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15)        # RFC 1951 3.2.7
@@ -336,28 +338,26 @@ def write_png_files(paths, frames_u8, filter="adaptive", rows_per_segment=None):
 
 
 def write_png_frames(dir, frames, start=0, digits=3):
-    """uint8 [F,H,W,3] on the device -> dir/NNN.png, 1-based and offset by `start` (the names and numbering of inference._save_u8_frames);
+    """uint8 [F,H,W,3] on the device -> dir/NNN.png, 1-based and offset by `start` (frames.numbered_paths, the names of every frame dump);
     `digits` is the least width of the number.  Returns the paths."""
     os.makedirs(dir, exist_ok=True)
-    paths = [os.path.join(dir, f"{i + start + 1:0{digits}}.png") for i in range(frames.shape[0])]
+    paths = numbered_paths(dir, frames.shape[0], start, digits=digits)
     write_png_files(paths, frames)
     return paths
 
 
 # ------------------------------------------------------------------ command line
 def _cli_encode(args):
-    import torch
     if os.path.isdir(args.input):
-        from PIL import Image
-        names = sorted(n for n in os.listdir(args.input) if n.lower().endswith((".png", ".jpg", ".jpeg")))
+        names = list_images(args.input, (".png", ".jpg", ".jpeg"))
         if not names:
             raise SystemExit(f"{args.input}: no image files")
-        frames = torch.from_numpy(np.stack([np.asarray(Image.open(os.path.join(args.input, n)).convert("RGB")) for n in names])).cuda()
+        frames = read_frames([os.path.join(args.input, n) for n in names], "cuda")
     else:
         from .video import read_video
         frames = read_video(args.input)[0]
     os.makedirs(args.output, exist_ok=True)
-    paths = [os.path.join(args.output, f"{i + 1:03}.png") for i in range(frames.shape[0])]
+    paths = numbered_paths(args.output, frames.shape[0])
     size = write_png_files(paths, frames, args.filter, args.rows_per_segment)
     print(f"{args.output}: {len(paths)} frames {frames.shape[2]}x{frames.shape[1]}, {size} bytes")
 

@@ -12,12 +12,12 @@ The Open3D / pyequilib / vggt arithmetic is third-party and unpinned
 filter and segment math are pinned bit-exactly by goldens generated from the reference (tests/golden).
 """
 import math
-import os
 
 import numpy as np
 import torch
 
 from . import ops
+from .frames import write_numbered
 
 FACE_ORDER = ("right", "left", "bottom", "top", "front", "back")    # face ids of the cube->equirect LUT (:583-590)
 CUBEMAP_TRANSFORMS = {                                               # :29-36
@@ -247,15 +247,8 @@ class CubemapRenderer:
         faces = self.render_cubemaps(vertices, colors, target_extrinsic, face_channels=4)   # RGBX words: aligned gathers
         lut = build_cube2equi_lut(width, height, self.face_res).to(vertices.device)
         panos = ops.cube2equi_gather(faces, lut, height, width)                   # uint8 [V,H,W,3] on the device
-        if outdir and png_on_device:                                             # opt-in: the same files, encoded on the device
-            from .png import write_png_files
-            os.makedirs(outdir, exist_ok=True)
-            write_png_files([os.path.join(outdir, f"{i:02}.png") for i in range(panos.shape[0])], panos)
-        elif outdir:
-            os.makedirs(outdir, exist_ok=True)
-            from PIL import Image
-            for i, p in enumerate(panos.cpu().numpy()):
-                Image.fromarray(p).save(os.path.join(outdir, f"{i:02}.png"))      # RGB on disk, as cv2.imwrite(BGR(pano))
+        if outdir:                                     # 00.png ..: RGB on disk, as cv2.imwrite(BGR(pano)); png_on_device is the opt-in encoder
+            write_numbered(outdir, panos, first=0, digits=2, on_device=png_on_device)
         return panos
 
 

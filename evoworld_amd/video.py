@@ -550,33 +550,27 @@ def video_scores(input_folder, target_size=64, lpips_weights=None, fvd_weights=N
 
 # ------------------------------------------------------------------ command line
 def _cli_encode(args):
-    import torch
-    from PIL import Image
-    names = sorted(n for n in os.listdir(args.input) if n.lower().endswith(".png"))
+    from .frames import list_images, read_frames
+    names = list_images(args.input, (".png",))
     if not names:
         raise SystemExit(f"{args.input}: no .png frames")
-    arr = np.stack([np.asarray(Image.open(os.path.join(args.input, n)).convert("RGB")) for n in names])
-    size = write_video(args.output, torch.from_numpy(arr).cuda(), args.fps, args.quality, args.subsampling)
-    print(f"{args.output}: {len(names)} frames {arr.shape[2]}x{arr.shape[1]}, {size} bytes")
+    frames = read_frames([os.path.join(args.input, n) for n in names], "cuda")
+    size = write_video(args.output, frames, args.fps, args.quality, args.subsampling)
+    print(f"{args.output}: {len(names)} frames {frames.shape[2]}x{frames.shape[1]}, {size} bytes")
 
 
 def _cli_extract(args):
-    fps, width, height, frames = read_avi(args.input)
+    from .frames import numbered_paths, write_numbered
+    fps, width, height, jpegs = read_avi(args.input)
     os.makedirs(args.output, exist_ok=True)
-    if args.format == "png" and args.device_png:
-        if frames:
-            from .png import write_png_frames
-            write_png_frames(args.output, decode_jpeg(frames))
-    elif args.format == "png":
-        from PIL import Image
-        if frames:
-            for i, f in enumerate(decode_jpeg(frames).cpu().numpy()):
-                Image.fromarray(f).save(os.path.join(args.output, f"{i + 1:03}.png"))
+    if args.format == "png":
+        if jpegs:
+            write_numbered(args.output, decode_jpeg(jpegs), on_device=args.device_png)
     else:
-        for i, j in enumerate(frames):
-            with open(os.path.join(args.output, f"{i + 1:03}.jpg"), "wb") as f:
+        for path, j in zip(numbered_paths(args.output, len(jpegs), ext=".jpg"), jpegs):
+            with open(path, "wb") as f:
                 f.write(j)
-    print(f"{args.output}: {len(frames)} frames {width}x{height} at {fps:g} fps")
+    print(f"{args.output}: {len(jpegs)} frames {width}x{height} at {fps:g} fps")
 
 
 def _cli_scores(args):

@@ -187,7 +187,8 @@ def test_container_and_sizes():
 def test_prototypes_flags_and_signatures():
     import unified_loop_consistency as cli
     from evoworld_amd import _lib, cubemap, video
-    from evoworld_amd.inference import UnifiedLoopConsistencyPipeline, _save_u8_frames
+    from evoworld_amd.frames import write_numbered
+    from evoworld_amd.inference import UnifiedLoopConsistencyPipeline
     from evoworld_amd.reprojection import CubemapRenderer, predictions_to_target_view
     H = _lib.HEADER
     assert H.constants["EW_ABI_VERSION"] == _lib.ABI_VERSION == 20
@@ -206,7 +207,7 @@ def test_prototypes_flags_and_signatures():
         text = open(os.path.join(os.path.dirname(cli.__file__), script)).read()
         assert '[ "$DEVICE_PNG" = 1 ] && CMD="$CMD --device_png"' in text
     assert inspect.signature(UnifiedLoopConsistencyPipeline.process_episode).parameters["png_on_device"].default is False
-    assert inspect.signature(_save_u8_frames).parameters["png_on_device"].default is False
+    assert inspect.signature(write_numbered).parameters["on_device"].default is False
     assert inspect.signature(predictions_to_target_view).parameters["png_on_device"].default is False
     assert inspect.signature(CubemapRenderer.render_cubemaps_to_panoramas).parameters["png_on_device"].default is False
     x = video.parse_arguments(["extract", "--input", "x.avi", "--output", "d", "--format", "png"])

@@ -306,17 +306,16 @@ def _decoded(folder):
 
 
 def test_write_png_frames_names_like_save_u8_frames(tmp_path):
-    from evoworld_amd.inference import _save_u8_frames
+    from evoworld_amd.frames import write_numbered                              # the writer of every frame dump, episode and CLI
     frames = dev(np.stack([C.texture(12, 20, s) for s in range(3)]))
-    _save_u8_frames(frames, str(tmp_path / "a"), 24)
+    write_numbered(str(tmp_path / "a"), frames, 24)
     paths = png.write_png_frames(str(tmp_path / "b"), frames, 24)
-    _save_u8_frames(frames, str(tmp_path / "c"), 24, png_on_device=True)
+    write_numbered(str(tmp_path / "c"), frames, 24, on_device=True)
     assert [os.path.basename(p) for p in paths] == sorted(os.listdir(tmp_path / "a")) == ["025.png", "026.png", "027.png"]
     a, b, c = _decoded(tmp_path / "a"), _decoded(tmp_path / "b"), _decoded(tmp_path / "c")
     assert list(a) == list(b) == list(c) and all(np.array_equal(a[n], b[n]) and np.array_equal(a[n], c[n]) for n in a)
     assert open(tmp_path / "b" / "025.png", "rb").read() == open(tmp_path / "c" / "025.png", "rb").read()
-    import unified_loop_consistency as cli                                      # the helper of both CLI paths (episode, single segment)
-    cli._save_frames_u8(frames, str(tmp_path / "e"), 24, True)
+    assert write_numbered(str(tmp_path / "e"), frames, 24, True) == [str(tmp_path / "e" / n) for n in a]     # as both CLI paths call it
     assert sorted(os.listdir(tmp_path / "e")) == list(a)
     assert open(tmp_path / "e" / "026.png", "rb").read() == open(tmp_path / "b" / "026.png", "rb").read()
     assert png.write_png(str(tmp_path / "one.png"), frames[1]) == os.path.getsize(tmp_path / "one.png")
@@ -393,3 +392,25 @@ def test_cubemap_cli_device_png(tmp_path):
     cubemap.main(["to-pano", "--input", str(tmp_path / "host"), "--output", str(tmp_path / "p1"), "--size", "64", "32", "--device_png"])
     p0, p1 = _decoded(tmp_path / "p0"), _decoded(tmp_path / "p1")
     assert list(p0) == list(p1) == ["001.png", "002.png"] and all(np.array_equal(p0[n], p1[n]) for n in p0)
+
+
+def test_memory_panoramas_on_the_device(tmp_path):
+    """CubemapRenderer.render_cubemaps_to_panoramas, the writer the episode test reaches only through process_episode: with an outdir it
+    leaves 00.png .. (two digits, from zero) holding the panoramas it returns, whichever encoder wrote them; without one, no file."""
+    from evoworld_amd.reprojection import CubemapRenderer
+    g = torch.Generator().manual_seed(5)
+    xyz = (torch.rand(4000, 3, generator=g) * 4 - 2).cuda()                     # a cloud around the three cameras: every face sees points
+    rgb = torch.randint(0, 256, (4000, 3), generator=g, dtype=torch.uint8).cuda()
+    c2w = np.repeat(np.eye(4)[None], 3, 0)
+    c2w[:, 0, 3] = [0.0, 0.2, 0.4]
+    cr = CubemapRenderer(face_res=32)
+    host = cr.render_cubemaps_to_panoramas(xyz, rgb, c2w, 3, str(tmp_path / "host"), width=128, height=64)
+    device = cr.render_cubemaps_to_panoramas(xyz, rgb, c2w, 3, str(tmp_path / "new" / "device"), width=128, height=64, png_on_device=True)
+    none = cr.render_cubemaps_to_panoramas(xyz, rgb, c2w, 3, None, width=128, height=64, png_on_device=True)
+    assert host.shape == (3, 64, 128, 3) and torch.equal(host, device) and torch.equal(host, none)
+    assert len({p.cpu().numpy().tobytes() for p in host}) == 3 and all(bool(p.any()) for p in host)      # three different views, none blank
+    a, b = _decoded(tmp_path / "host"), _decoded(tmp_path / "new" / "device")
+    assert list(a) == list(b) == ["00.png", "01.png", "02.png"] == sorted(os.listdir(tmp_path / "host"))
+    assert sorted(os.listdir(tmp_path)) == ["host", "new"]
+    for k, n in enumerate(a):
+        assert np.array_equal(a[n], host[k].cpu().numpy()) and np.array_equal(b[n], a[n]), n

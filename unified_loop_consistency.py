@@ -98,17 +98,6 @@ def synthetic_path_episode(num_segments, extra=8, step=0.4):
     return np.asarray(rows, np.float64)
 
 
-def _save_frames_u8(u8_hwc, d, start=0, device_png=False):
-    if device_png:
-        from evoworld_amd.png import write_png_frames
-        write_png_frames(d, u8_hwc, start)
-        return
-    from PIL import Image
-    os.makedirs(d, exist_ok=True)
-    for i, f in enumerate(u8_hwc.cpu().numpy()):
-        Image.fromarray(f).save(os.path.join(d, f"{i + start + 1:03}.png"))
-
-
 def run_single_segment(args, ep, pipe, unet, dev, out_dir, synthetic):
     """The reference's single-segment fast path (`run_single_segment`, unified_loop_consistency.py:513-535): the dataset in
     'reprojection' mode hands out the episode's LAST 25 frames / poses (positions x pos_scale) with the PRE-RENDERED memory
@@ -116,6 +105,7 @@ def run_single_segment(args, ep, pipe, unet, dev, out_dir, synthetic):
     with mask_mem=False.  Counterparts: evoworld_amd.dataset.load_single_segment_batch -> evoworld_amd.inference.process_batch."""
     from evoworld_amd import ops
     from evoworld_amd.dataset import load_single_segment_batch
+    from evoworld_amd.frames import write_numbered
     from evoworld_amd.inference import process_batch
     from evoworld_amd.plucker import equirectangular_to_ray
     from evoworld_amd.stages import load_stages
@@ -143,9 +133,9 @@ def run_single_segment(args, ep, pipe, unet, dev, out_dir, synthetic):
     torch.cuda.synchronize()
     dt = time.time() - t0
     if args.save_frames:
-        _save_frames_u8(frames_u8, os.path.join(out_dir, "predictions"), 0, args.device_png)     # forward_evoworld.save_frames
-        _save_frames_u8(ops.f32_chw_to_u8_hwc(batch["pixel_values"][0].float().contiguous()), os.path.join(out_dir, "predictions_gt"), 0,
-                        args.device_png)
+        write_numbered(os.path.join(out_dir, "predictions"), frames_u8, on_device=args.device_png)     # forward_evoworld.save_frames
+        write_numbered(os.path.join(out_dir, "predictions_gt"), ops.f32_chw_to_u8_hwc(batch["pixel_values"][0].float().contiguous()),
+                       on_device=args.device_png)
     if args.save_video:                                                                   # the clip and its ground truth, as process_episode names them
         from evoworld_amd.video import write_video
         write_video(os.path.join(out_dir, "navigated.avi"), frames_u8, fps=args.video_fps, quality=args.video_quality)
@@ -156,6 +146,7 @@ def run_single_segment(args, ep, pipe, unet, dev, out_dir, synthetic):
 def run_episode(args, ep, pipe, unet, dev, out_dir, synthetic):
     """N segments with evolving 3D memory (`process_episode`, unified_loop_consistency.py:398-492)."""
     from evoworld_amd.dataset import load_complete_episode_batch
+    from evoworld_amd.frames import write_numbered
     from evoworld_amd.inference import UnifiedLoopConsistencyPipeline
     from evoworld_amd.stages import load_stages
     if synthetic:                                                                                    # UNSCALED
@@ -184,7 +175,7 @@ def run_episode(args, ep, pipe, unet, dev, out_dir, synthetic):
     torch.cuda.synchronize()
     dt = time.time() - t0
     if args.save_frames:
-        _save_frames_u8(loop.last_frames_u8, os.path.join(out_dir, "predictions"), 0, args.device_png)
+        write_numbered(os.path.join(out_dir, "predictions"), loop.last_frames_u8, on_device=args.device_png)
     return {"episode": os.path.basename(ep), "frames": int(frames.shape[0]), "seconds": round(dt, 3)}
 
 
