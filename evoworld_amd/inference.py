@@ -332,7 +332,9 @@ class UnifiedLoopConsistencyPipeline:
     """process_episode of unified_loop_consistency.py:398-492 with every stage on the device.
     `frames_from_latents(latents[1,T,4,h,w]) -> float [T,3,H,W] in [-1,1]` stands for the VAE decode (row N1);
     `depth_model(persp_u8 [F,384,512,3]) -> dict(depth, depth_conf, images, extrinsic, intrinsic)` stands for VGGT (row N4); one that
-    declares `wants_view_poses = True` (evoworld_amd.mvs.PlaneSweepDepth) is called with `view_w2c=mvs.view_poses(...)` as well."""
+    declares `wants_view_poses = True` (evoworld_amd.mvs.PlaneSweepDepth) is called with `view_w2c=mvs.view_poses(...)` as well, and one
+    that declares `wants_panoramas = True` (evoworld_amd.mvs.SphereSweepDepth) with the panoramas so far and `pano_w2c=mvs.pano_poses(...)`
+    instead of the views."""
 
     def __init__(self, pipeline, depth_model, frames_from_latents=None, height=576, width=1024, num_frames=25, num_segments=3,
                  num_inference_steps=25, pano_size=(1000, 2000), face_res=512, curve_path=True):
@@ -434,7 +436,10 @@ class UnifiedLoopConsistencyPipeline:
                 temp_cam = camera_params.copy()
                 s = max(0, end_idx - len(target_yaws))
                 temp_cam[s:end_idx, 4] = target_yaws[: end_idx - s]                        # :456-459
-                preds = call_depth_model(self.depth_model, pers, camera_params, seg)    # a stage that wants them also gets the views' poses
+                if getattr(self.depth_model, "wants_panoramas", False):                   # opt-in: the stage reads the panoramas, not the crops
+                    preds = call_depth_model(self.depth_model, pers, camera_params, seg, panos_u8=all_u8)
+                else:
+                    preds = call_depth_model(self.depth_model, pers, camera_params, seg)    # a stage that wants them also gets the views' poses
                 poses = xyz_euler_to_four_by_four_matrix_batch(torch.tensor(temp_cam, dtype=torch.float32), relative=True)
                 outdir, glb, save_png = out.memory(seg)
                 panos = RP.predictions_to_target_view(preds, poses.numpy(), conf_thres=50.0, prediction_mode="depth_unproject",

@@ -10,6 +10,15 @@ depth network's predictions.  It is opt-in (`--depth_stage mvs`); how it compare
   sweep_setup      sources per view, inverse depths, homographies (host, float64)
   PlaneSweepDepth  the callable: uint8 views [F,H,W,3] on the device -> predictions dict (device tensors)
   python -m evoworld_amd.mvs cloud --frames DIR --poses camera_poses.txt --segment K --output scene.ply|.glb
+
+The same stage on the panoramas themselves (`--depth_stage mvs_pano`): the views above are 90-degree crops cut near the
+direction of motion, where parallax is least; the sphere sweep reads the whole equirectangular frame (ew_mvs_sphere_sweep,
+ew_mvs_sphere_consistency) and lifts spherically (ew_pano_unproject), so the cloud covers every direction.
+
+  pano_poses        the world->camera matrices of the panorama cameras, in the frame view_poses(..., relative=True) defines
+  sphere_setup      sources per panorama, inverse distances, relative poses (host, float64)
+  SphereSweepDepth  the callable: uint8 panoramas [F,He,We,3] on the device -> predictions dict with world_points_from_depth
+  python -m evoworld_amd.mvs cloud --stage sphere [--sweep_size H W] ...
 """
 import argparse
 import json
@@ -49,6 +58,26 @@ def view_poses(camera_params, n_frames, segment_id, relative=True):
         c2w[i] = c2w[i] @ turn
     if relative:
         c2w = np.linalg.inv(c2w[0])[None] @ c2w
+    return np.linalg.inv(c2w)[:, :3, :4]
+
+
+def pano_poses(camera_params, n_frames, segment_id):
+    """float64 [F,3,4] world->camera of the panorama cameras of the first n_frames frames (x right, y down, z forward: the frame in which
+    ew_equi2pers' direction <-> pixel map is stated).  The panorama camera is xyz_euler_to_four_by_four_matrix_batch on the UNSCALED
+    poses; world = the frame of the first perspective VIEW, exactly as view_poses(..., relative=True) defines it -- so a sphere cloud and
+    a plane-sweep cloud of one episode share a frame, and the camera centres equal those of the views (a view only turns its panorama's
+    camera on the spot)."""
+    from . import reprojection as RP
+    cam = np.asarray(camera_params, dtype=np.float64)
+    if n_frames < 1 or n_frames > len(cam):
+        raise ValueError(f"n_frames = {n_frames} must be 1 .. {len(cam)} (the poses of the episode)")
+    c2w = xyz_euler_to_four_by_four_matrix_batch(torch.tensor(cam[:n_frames], dtype=torch.float64), relative=False).numpy()
+    yaw0 = RP.calculate_target_yaws(cam, n_frames, segment_id)[0]
+    first_view = c2w[0].copy()
+    turn = np.eye(4)
+    turn[:3, :3] = RP.Equi2Pers.rotation({"pitch": 0, "roll": 0, "yaw": float(yaw0)}).astype(np.float64)
+    first_view = first_view @ turn
+    c2w = np.linalg.inv(first_view)[None] @ c2w
     return np.linalg.inv(c2w)[:, :3, :4]
 
 
@@ -123,9 +152,47 @@ def sweep_setup(w2c, K, n_src, D, z_near=None, z_far=None, min_baseline=1e-6):
                            rel_pose_f32=rel[:, :, :3, :4].astype(np.float32))
 
 
-def call_depth_model(depth_model, pers_u8, camera_params, segment_id):
-    """How process_episode calls its depth stage: a stage that declares `wants_view_poses` also gets the views' world->camera
-    matrices (view_poses); any other callable is called with the frames alone, exactly as before."""
+def sphere_setup(pano_w2c, We, n_src, D, d_near=None, d_far=None, min_baseline=1e-6):
+    """What ew_mvs_sphere_sweep and ew_mvs_sphere_consistency need, computed on the host in float64 (the *_f32 members are the uploads):
+      src_index [F,n_src] int32 (choose_sources); baseline [F,n_src]; d_near, d_far [F]; inv_dist [F,D], uniform in inverse distance from
+      1 / d_far (hypothesis 0) to 1 / d_near (hypothesis D - 1); rel_pose [F,n_src,3,4], reference panorama camera -> source panorama
+      camera.  Default range per view: d_far = b_max We / (2 pi) -- one pixel of angular disparity over the view's widest baseline -- and
+      d_near = d_far / D.  A view without a source sweeps the single distance d_far of the nearest view that has one (1.0 when none has),
+      as sweep_setup does."""
+    E = _w2c_4x4(pano_w2c)
+    F = len(E)
+    if n_src < 1 or D < 1 or We < 1:
+        raise ValueError(f"n_src = {n_src}, D = {D} and We = {We} must be positive")
+    c2w = np.linalg.inv(E)
+    centres = c2w[:, :3, 3]
+    src = choose_sources(centres, n_src, min_baseline)
+    base = np.where(src >= 0, np.linalg.norm(centres[np.maximum(src, 0)] - centres[:, None], axis=-1), 0.0)
+    has = (src >= 0).any(1)
+    far = np.where(has, base.max(1) * We / (2 * np.pi), 0.0) if d_far is None else np.broadcast_to(np.asarray(d_far, np.float64), (F,)).copy()
+    for i in np.flatnonzero(~has):                 # nothing to sweep against: the neighbour's far sphere
+        with_src = np.flatnonzero(has)
+        far[i] = far[with_src[np.argmin(np.abs(with_src - i))]] if len(with_src) else 1.0
+    near = far / D if d_near is None else np.broadcast_to(np.asarray(d_near, np.float64), (F,)).copy()
+    near = np.where(has, near, far)
+    t = np.linspace(0.0, 1.0, D) if D > 1 else np.zeros(1)
+    inv_dist = 1.0 / far[:, None] + t[None] * (1.0 / near - 1.0 / far)[:, None]
+    rel = np.tile(np.eye(4), (F, n_src, 1, 1))
+    for i in range(F):
+        for s in range(n_src):
+            if src[i, s] >= 0:
+                rel[i, s] = E[src[i, s]] @ c2w[i]
+    return SimpleNamespace(src_index=src, baseline=base, d_near=near, d_far=far, inv_dist=inv_dist, rel_pose=rel[:, :, :3, :4].copy(),
+                           has_source=has, inv_dist_f32=inv_dist.astype(np.float32), rel_pose_f32=rel[:, :, :3, :4].astype(np.float32))
+
+
+def call_depth_model(depth_model, pers_u8, camera_params, segment_id, panos_u8=None):
+    """How process_episode calls its depth stage: a stage that declares `wants_panoramas` is called with the episode's panoramas so far
+    (panos_u8) and their world->camera matrices (pano_poses) instead of the views; one that declares `wants_view_poses` gets the views and
+    their world->camera matrices (view_poses); any other callable is called with the views alone, exactly as before."""
+    if getattr(depth_model, "wants_panoramas", False):
+        if panos_u8 is None:
+            raise ValueError("a depth stage that declares wants_panoramas needs panos_u8, the panoramas the views were cut from")
+        return depth_model(panos_u8, pano_w2c=pano_poses(camera_params, len(panos_u8), segment_id))
     if getattr(depth_model, "wants_view_poses", False):
         return depth_model(pers_u8, view_w2c=view_poses(camera_params, len(pers_u8), segment_id))
     return depth_model(pers_u8)
@@ -184,6 +251,67 @@ class PlaneSweepDepth:
                 "extrinsic": up(E.astype(np.float32)), "intrinsic": up(np.repeat(K[None].astype(np.float32), F, 0))}
 
 
+class SphereSweepDepth:
+    """The depth stage on the panoramas: `__call__(panoramas uint8 [F,He,We,3] on the device, pano_w2c [F,3,4])` -> the predictions dict
+    predictions_to_target_view(..., prediction_mode="depth_unproject") consumes, as device tensors: world_points_from_depth [F,h,w,3]
+    (ew_pano_unproject, in the frame pano_w2c is given in), depth_conf [F,h,w], depth [F,h,w,1] (the RADIAL distance), images [F,3,h,w]
+    (the swept frames / 255), extrinsic [F,3,4] (pano_w2c).  There is no `intrinsic`: the lift is spherical and already done.  n_src
+    sources per panorama, `planes` distance hypotheses (sphere_setup); patch_radius as ew_mvs_sphere_sweep; a pixel keeps its confidence
+    when at least min_consistent sources hold a distance within rel_tol of its own (capped at the number of sources a view has; 0
+    switches the check off).  sweep_size = (h, w): the panoramas are first resized on the device (ops.resize_linear_u8); default: native
+    size.  Without pano_w2c the poses come from pano_poses(camera_params, F, segment_id), the segment inferred from F = 25 + 24 k."""
+    wants_panoramas = True
+
+    def __init__(self, camera_params=None, n_src=4, planes=64, patch_radius=2, min_consistent=2, rel_tol=0.02, d_near=None, d_far=None,
+                 sweep_size=None, segment_id=None, min_baseline=1e-6):
+        if patch_radius not in (0, 1, 2, 3):
+            raise ValueError(f"patch_radius must be 0 .. 3, got {patch_radius!r}")
+        if n_src < 1 or planes < 1:
+            raise ValueError(f"n_src = {n_src} and planes = {planes} must be positive")
+        if sweep_size is not None and (len(sweep_size) != 2 or min(sweep_size) < 1):
+            raise ValueError(f"sweep_size must be (h, w), got {sweep_size!r}")
+        self.camera_params = None if camera_params is None else np.asarray(camera_params, np.float64)
+        self.n_src, self.planes, self.patch_radius = int(n_src), int(planes), int(patch_radius)
+        self.min_consistent, self.rel_tol = int(min_consistent), float(rel_tol)
+        self.d_near, self.d_far, self.min_baseline, self.segment_id = d_near, d_far, min_baseline, segment_id
+        self.sweep_size = None if sweep_size is None else (int(sweep_size[0]), int(sweep_size[1]))
+        self.last_setup = None
+
+    def _poses(self, n):
+        if self.camera_params is None:
+            raise ValueError("SphereSweepDepth needs pano_w2c, or camera_params to derive it from")
+        seg = self.segment_id
+        if seg is None:
+            if n < 25 or (n - 25) % 24:
+                raise ValueError(f"cannot infer the segment from {n} panoramas (25 + 24 k expected): pass segment_id or pano_w2c")
+            seg = (n - 25) // 24
+        return pano_poses(self.camera_params, n, seg)
+
+    def __call__(self, panos_u8, pano_w2c=None):
+        from . import ops
+        if not isinstance(panos_u8, torch.Tensor) or panos_u8.dtype != torch.uint8 or panos_u8.ndim != 4 or panos_u8.shape[3] != 3:
+            raise TypeError("SphereSweepDepth: the panoramas must be a device uint8 [F,He,We,3] tensor")
+        F = panos_u8.shape[0]
+        dev = panos_u8.device
+        w2c = self._poses(F) if pano_w2c is None else pano_w2c
+        frames = panos_u8.contiguous()
+        if self.sweep_size is not None and self.sweep_size != tuple(frames.shape[1:3]):
+            frames = ops.resize_linear_u8(frames, *self.sweep_size)
+        He, We = frames.shape[1:3]
+        st = sphere_setup(w2c, We, self.n_src, self.planes, self.d_near, self.d_far, self.min_baseline)
+        self.last_setup = st
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        src, rel = up(st.src_index), up(st.rel_pose_f32)
+        dist, conf, _, _ = ops.mvs_sphere_sweep(ops.mvs_luma(frames), rel, src, up(st.inv_dist_f32), self.patch_radius)
+        need = min(self.min_consistent, int((st.src_index >= 0).sum(1).max()))
+        if need > 0:
+            ops.mvs_sphere_consistency(dist, rel, src, conf, self.rel_tol, need)
+        E = _w2c_4x4(w2c)
+        pts = ops.pano_unproject(dist, up(np.linalg.inv(E)[:, :3, :4].astype(np.float32)))
+        return {"world_points_from_depth": pts, "depth_conf": conf, "depth": dist[..., None],
+                "images": frames.permute(0, 3, 1, 2).float() / 255, "extrinsic": up(E[:, :3, :4].astype(np.float32))}
+
+
 # ------------------------------------------------------------------ command line
 def _load_frames(folder, n, device):
     from .frames import list_images, read_frames
@@ -203,11 +331,15 @@ def _cloud_main(args):
     frames = _load_frames(args.frames, n, "cuda")
     n = min(n, len(frames), len(cam))
     frames = frames[:n]
-    yaws = RP.calculate_target_yaws(cam, n, args.segment)
-    views = RP.Equi2Pers(height=args.view_height, width=args.view_width, fov_x=90.0).batch(
-        frames, [{"pitch": 0, "roll": 0, "yaw": float(y)} for y in yaws])
-    stage = PlaneSweepDepth(cam, n_src=args.sources, planes=args.planes, patch_radius=args.patch_radius)
-    preds = stage(views, view_w2c=view_poses(cam, n, args.segment))
+    if args.stage == "sphere":
+        stage = SphereSweepDepth(cam, n_src=args.sources, planes=args.planes, patch_radius=args.patch_radius, sweep_size=args.sweep_size)
+        preds = stage(frames, pano_w2c=pano_poses(cam, n, args.segment))
+    else:
+        yaws = RP.calculate_target_yaws(cam, n, args.segment)
+        views = RP.Equi2Pers(height=args.view_height, width=args.view_width, fov_x=90.0).batch(
+            frames, [{"pitch": 0, "roll": 0, "yaw": float(y)} for y in yaws])
+        stage = PlaneSweepDepth(cam, n_src=args.sources, planes=args.planes, patch_radius=args.patch_radius)
+        preds = stage(views, view_w2c=view_poses(cam, n, args.segment))
     mem = SceneMemory.from_predictions(preds, conf_thres=args.conf_thres, show_cam=args.show_cam, prediction_mode="depth_unproject")
     n_in = len(mem)
     if args.voxel_size is not None:
@@ -219,13 +351,13 @@ def _cloud_main(args):
     else:
         raise SystemExit(f"--output must end in .glb or .ply (got {args.output})")
     print(json.dumps({"output": args.output, "views": int(n), "points_in": n_in, "points_out": len(mem), "scene_scale": mem.scene_scale,
-                      "planes": args.planes, "sources": args.sources}))
+                      "planes": args.planes, "sources": args.sources, "stage": args.stage}))
 
 
 def build_parser():
     p = argparse.ArgumentParser(prog="python -m evoworld_amd.mvs", description=__doc__.split("\n\n")[0])
     sub = p.add_subparsers(dest="command", required=True)
-    c = sub.add_parser("cloud", help="panorama frames + poses -> perspective views -> plane-sweep depth -> filtered cloud (.ply | .glb)")
+    c = sub.add_parser("cloud", help="panorama frames + poses -> plane-sweep depth on perspective views, or sphere-sweep depth on the panoramas -> filtered cloud (.ply | .glb)")
     c.add_argument("--frames", required=True, help="folder of panorama frames (NNN.png, sorted by name), e.g. an episode's predictions/")
     c.add_argument("--poses", required=True, help="camera_poses.txt (or the folder that holds it)")
     c.add_argument("--segment", type=int, default=0, help="segment K: the first 25 + 24 K frames, looking at the segment's target pose")
@@ -238,6 +370,10 @@ def build_parser():
     c.add_argument("--show_cam", action="store_true", help="add one pyramid marker per camera (GLB)")
     c.add_argument("--view_height", type=int, default=384)
     c.add_argument("--view_width", type=int, default=512)
+    c.add_argument("--stage", choices=("plane", "sphere"), default="plane",
+                   help="plane: plane sweep on the 90-degree views (DESIGN.md 4.8); sphere: sphere sweep on the panoramas themselves (4.9)")
+    c.add_argument("--sweep_size", type=int, nargs=2, metavar=("H", "W"), default=None,
+                   help="--stage sphere: resize the panoramas to H x W on the device before the sweep (default: native size)")
     return p
 
 

@@ -867,6 +867,72 @@ def mvs_consistency(depth, rel_pose, src_index, conf, fx, fy, cx, cy, rel_tol=0.
     return conf
 
 
+def mvs_sphere_sweep(grey, rel_pose, src_index, inv_dist, patch_radius=2, out=None):
+    """grey uint8 [F,He,We] (equirectangular), rel_pose fp32 [F,S,3,4] (reference panorama camera -> source panorama camera), src_index
+    int32 [F,S] (-1: absent), inv_dist fp32 [F,D] -> (radial distance fp32, conf fp32, winner int32, winner cost fp32), each [F,He,We]
+    (ew_mvs_sphere_sweep).  out: the four output tensors to write into."""
+    if grey.ndim != 3 or grey.numel() == 0:
+        raise ValueError(f"grey must be a non-empty [F,He,We], got {tuple(grey.shape)}")
+    _req(grey, torch.uint8, "grey")
+    F_, H, W = grey.shape
+    S = _mvs_sources(src_index, F_)
+    if inv_dist.ndim != 2 or inv_dist.shape[0] != F_ or inv_dist.shape[1] < 1:
+        raise ValueError(f"inv_dist must be [F = {F_}, D >= 1], got {tuple(inv_dist.shape)}")
+    D = inv_dist.shape[1]
+    if tuple(rel_pose.shape) != (F_, S, 3, 4):
+        raise ValueError(f"rel_pose must be {(F_, S, 3, 4)}, got {tuple(rel_pose.shape)}")
+    if patch_radius not in (0, 1, 2, 3):
+        raise ValueError(f"patch_radius must be 0 .. 3, got {patch_radius!r}")
+    if W < 2 * patch_radius + 1:
+        raise ValueError(f"We = {W} is narrower than the window of 2 x {patch_radius} + 1 columns")
+    _req(rel_pose, torch.float32, "rel_pose"); _req(inv_dist, torch.float32, "inv_dist")
+    dev = grey.device
+    given = out if out is not None else (None,) * 4
+    dist = _mvs_out(given[0], (F_, H, W), torch.float32, dev, "out[0]")
+    conf = _mvs_out(given[1], (F_, H, W), torch.float32, dev, "out[1]")
+    winner = _mvs_out(given[2], (F_, H, W), torch.int32, dev, "out[2]")
+    cost = _mvs_out(given[3], (F_, H, W), torch.float32, dev, "out[3]")
+    _call("ew_mvs_sphere_sweep", _ptr(grey), _ptr(rel_pose), _ptr(src_index), _ptr(inv_dist), _ptr(dist), _ptr(conf), _ptr(winner),
+          _ptr(cost), F_, H, W, S, D, int(patch_radius))
+    return dist, conf, winner, cost
+
+
+def mvs_sphere_consistency(dist, rel_pose, src_index, conf, rel_tol=0.02, min_consistent=2):
+    """dist fp32 [F,He,We] (radial), rel_pose fp32 [F,S,3,4], src_index int32 [F,S]; conf fp32 [F,He,We] is set to 0 IN PLACE where fewer
+    than min_consistent present sources hold, in the lifted pixel's direction, a distance within rel_tol of the pixel's own
+    (ew_mvs_sphere_consistency).  Returns conf."""
+    if dist.ndim != 3 or dist.numel() == 0:
+        raise ValueError(f"dist must be a non-empty [F,He,We], got {tuple(dist.shape)}")
+    _req(dist, torch.float32, "dist")
+    F_, H, W = dist.shape
+    S = _mvs_sources(src_index, F_)
+    if tuple(rel_pose.shape) != (F_, S, 3, 4):
+        raise ValueError(f"rel_pose must be {(F_, S, 3, 4)}, got {tuple(rel_pose.shape)}")
+    if tuple(conf.shape) != (F_, H, W):
+        raise ValueError(f"conf must be {(F_, H, W)}, got {tuple(conf.shape)}")
+    if not rel_tol >= 0:
+        raise ValueError(f"rel_tol = {rel_tol!r} must not be negative")
+    _req(rel_pose, torch.float32, "rel_pose"); _req(conf, torch.float32, "conf")
+    _call("ew_mvs_sphere_consistency", _ptr(dist), _ptr(rel_pose), _ptr(src_index), _ptr(conf), F_, H, W, S, float(rel_tol),
+          int(min_consistent))
+    return conf
+
+
+def pano_unproject(dist, c2w, out=None):
+    """dist fp32 [F,He,We] (radial distance per equirectangular pixel), c2w fp32 [F,3,4] (panorama camera -> world) -> world points fp32
+    [F,He,We,3] = R (dir dist) + t (ew_pano_unproject): the spherical counterpart of depth_unproject."""
+    if dist.ndim != 3 or dist.numel() == 0:
+        raise ValueError(f"dist must be a non-empty [F,He,We], got {tuple(dist.shape)}")
+    _req(dist, torch.float32, "dist")
+    F_, H, W = dist.shape
+    if tuple(c2w.shape) != (F_, 3, 4):
+        raise ValueError(f"c2w must be {(F_, 3, 4)}, got {tuple(c2w.shape)}")
+    _req(c2w, torch.float32, "c2w")
+    out = _mvs_out(out, (F_, H, W, 3), torch.float32, dist.device, "out")
+    _call("ew_pano_unproject", _ptr(dist), _ptr(c2w), _ptr(out), F_, H, W)
+    return out
+
+
 def equi2pers(equi, rot, Hp, Wp, fov_x):
     _req(equi, torch.uint8, "equi"); _req(rot, torch.float32, "rot")
     F_, He, We, _ = equi.shape

@@ -123,14 +123,15 @@ class HipStages(SyntheticStages):
         return torch.cat([self.vae.decode(z[i:i + c], num_frames=min(c, z.shape[0] - i)).sample for i in range(0, z.shape[0], c)])
 
 
-DEPTH_STAGES = ("synthetic", "mvs")
+DEPTH_STAGES = ("synthetic", "mvs", "mvs_pano")
 
 
 def load_stages(spec, args, depth_stage=None, **kw):
     """spec 'pkg.mod:factory' -> factory(args); 'hip' -> HipStages (VAE + CLIP on the HIP kernels); None -> SyntheticStages.
     depth_stage (opt-in): 'mvs' replaces ONLY `depth_model` of whichever stages object was chosen by the plane-sweep stereo stage
     (evoworld_amd.mvs.PlaneSweepDepth; planes and sources from args.mvs_planes / args.mvs_sources when they are set); None or
-    'synthetic' leaves the object as it is."""
+    'synthetic' leaves the object as it is.  'mvs_pano' does the same with the sphere sweep on the panoramas themselves
+    (evoworld_amd.mvs.SphereSweepDepth, same two options)."""
     if depth_stage not in (None,) + DEPTH_STAGES:
         raise ValueError(f"depth_stage must be one of {DEPTH_STAGES}, got {depth_stage!r}")
     camera_params = kw.get("camera_params")
@@ -147,4 +148,8 @@ def load_stages(spec, args, depth_stage=None, **kw):
         from .mvs import PlaneSweepDepth
         opt = {k: v for k, v in (("planes", getattr(args, "mvs_planes", None)), ("n_src", getattr(args, "mvs_sources", None))) if v is not None}
         stages.depth_model = PlaneSweepDepth(camera_params, **opt)
+    elif depth_stage == "mvs_pano":
+        from .mvs import SphereSweepDepth
+        opt = {k: v for k, v in (("planes", getattr(args, "mvs_planes", None)), ("n_src", getattr(args, "mvs_sources", None))) if v is not None}
+        stages.depth_model = SphereSweepDepth(camera_params, **opt)
     return stages

@@ -526,6 +526,42 @@ ew_status ew_mvs_plane_sweep(const uint8_t* grey, const float* homographies, con
 ew_status ew_mvs_consistency(const float* depth, const float* rel_pose, const int* src_index, float* conf, int F, int H, int W, int S,
                              float fx, float fy, float cx, float cy, float rel_tol, int min_consistent, void* stream);
 
+/* Sphere-sweep multi-view stereo on posed equirectangular panoramas (csrc/mvs_sphere.hip; added to ABI 20 without a bump: new symbols
+ * only).  The stage above without the 90-degree crop: concentric spheres around each panorama camera take the place of the
+ * planes, the warp goes through the sphere, the lift is spherical.  Stands in for the same lines of the reference
+ * (unified_loop_consistency.py:336-368).  fp32 in the order written below; no atomics: two calls return identical bits, and a view's
+ * outputs depend only on that view and its sources.  PI = 3.14159265358979323846f, Wf = (float)We, Hf = (float)He.
+ * Pixel <-> direction, the map of ew_equi2pers (x right, y down, z forward):
+ *   dir(x, y), integer indices: lon = ((x - Wf 0.5) - 0.5) ((2 PI) / Wf), lat = ((y - Hf 0.5) - 0.5) (PI / Hf), dir = (cosf(lat) sinf(lon),
+ *     sinf(lat), cosf(lat) cosf(lon)).
+ *   pix(X, Y, Z): nrm = sqrtf((X X + Y Y) + Z Z), lon = atan2f(X, Z), lat = asinf(clamp(Y / nrm, -1, 1)), u = ((lon Wf) / (2 PI) + Wf 0.5)
+ *     + 0.5, v = ((lat Hf) / PI + Hf 0.5) + 0.5.
+ *   bilinear(I, u, v): u <- u - floorf(u / Wf) Wf, v <- clamp(v, 0, He - 1); x0 = floor(u) (We -> 0), ax = u - floor(u), x1 = (x0 + 1) mod
+ *     We; y0 = floor(v), ay = v - y0, y1 = min(y0 + 1, He - 1); top = v00 (1 - ax) + v01 ax, bot = v10 (1 - ax) + v11 ax, value = top (1 -
+ *     ay) + bot ay -- as ew_equi2pers samples.
+ * ew_mvs_sphere_sweep: grey uint8 [F,He,We] (ew_mvs_luma_u8); rel_pose fp32 [F,S,3,4], reference panorama camera -> source panorama
+ *   camera (R | t); src_index int32 [F,S] (outside [0, F): the slot is absent); inv_dist fp32 [F,D].  For the reference pixel (x, y) and
+ *   hypothesis k: rad = 1 / inv_dist[k], P = dir(x, y) rad (three products), Ps = R P + t, each row ((r0 px + r1 py) + r2 pz) + t; AD =
+ *   |I_ref(x, y) - bilinear(I_src, pix(Ps))|, and AD = 0 where |Ps| is 0 or not finite.  Every direction lands in the source: there is no
+ *   out-of-image cost.  A = the sum of AD over the present slots in slot order; C(k) = (the sum over the window's rows inside [0, He), top
+ *   to bottom, of the sum over a row's 2 patch_radius + 1 taps, left to right, columns taken modulo We, of A) / ((2 patch_radius + 1) x
+ *   rows inside x present slots).  Winner, ties, parabola refinement (here of the inverse distance), runner-up C2 among |k - k*| > 1,
+ *   conf = (C2 - C1) / max(C2, 1e-6) and conf = 0 without such a hypothesis or without a present slot: word for word the rules of
+ *   ew_mvs_plane_sweep.  Outputs dist (the RADIAL distance 1 / inverse distance, not z), conf, winner_cost fp32 [F,He,We], winner int32
+ *   [F,He,We].  patch_radius 0 .. 3, We >= 2 patch_radius + 1.
+ * ew_mvs_sphere_consistency: dist fp32 [F,He,We]; rel_pose, src_index as above.  Per pixel: P = dir(x, y) dist, Ps = R P + t as above, nrm
+ *   = |Ps| as in pix; a slot agrees when nrm > 0 and finite and |dist_src[yi, xi] - nrm| <= rel_tol nrm at the nearest pixel of Ps'
+ *   direction, xi = floor(u + 0.5) mod We, yi = clamp(floor(v + 0.5), 0, He - 1) with (u, v) = pix(Ps).  conf [F,He,We] is set to 0, in
+ *   place, where fewer than min_consistent slots agree.
+ * ew_pano_unproject (the spherical counterpart of ew_depth_unproject): dist fp32 [F,He,We]; c2w fp32 [F,3,4], panorama camera -> world
+ *   (R | t) -> xyz fp32 [F,He,We,3] = R (dir(x, y) dist) + t, rows in the order above. */
+ew_status ew_mvs_sphere_sweep(const uint8_t* grey, const float* rel_pose, const int* src_index, const float* inv_dist, float* dist,
+                              float* conf, int* winner, float* winner_cost, int F, int He, int We, int S, int D, int patch_radius,
+                              void* stream);
+ew_status ew_mvs_sphere_consistency(const float* dist, const float* rel_pose, const int* src_index, float* conf, int F, int He, int We,
+                                    int S, float rel_tol, int min_consistent, void* stream);
+ew_status ew_pano_unproject(const float* dist, const float* c2w, float* xyz, int F, int He, int We, void* stream);
+
 /* Equirect -> perspective bilinear gather (pyequilib Equi2Pers restatement; unified_loop_consistency.py:299-334).
  * equi uint8 [F,He,We,3]; rot [F,3,3] f32 (camera->pano rotation); out uint8 [F,Hp,Wp,3]. */
 ew_status ew_equi2pers(const uint8_t* equi, const float* rot, uint8_t* out, int F, int He, int We, int Hp, int Wp,

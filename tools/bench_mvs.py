@@ -2,6 +2,9 @@
 hands it: 25 and 73 perspective views of 384 x 512 (the hand-offs after segments 0 and 2).
 
   python tools/bench_mvs.py [--iters 3] [--views 25 73] [--planes 64] [--sources 4] [--patch_radius 2] [--out profiles/mvs_bench.json]
+  python tools/bench_mvs.py --sphere [...]      the sphere-sweep stage (csrc/mvs_sphere.hip) on 25 and 73 PANORAMAS of
+                                                576 x 1024: ew_mvs_sphere_sweep, ew_mvs_sphere_consistency, ew_pano_unproject
+                                                (default --out profiles/mvs_sphere_bench.json)
 
 The views: bench_video.synthetic_clip (gradients, a texture of sinusoids, noise of sigma 4) -- the timing does not depend on what the
 sweep finds -- at the poses view_poses gives for the curved synthetic episode of unified_loop_consistency.py.  Device events around
@@ -65,27 +68,83 @@ def run(V, H, W, D, S, r, it):
             "host_setup_ms": round(setup_ms, 1), "stage_call_wall_ms": round(min(wall) * 1e3, 1), "homography_bytes": homog.numel() * 4}
 
 
+def run_sphere(V, H, W, D, S, r, it):
+    import unified_loop_consistency as cli
+    from evoworld_amd import mvs, ops
+    seg = max(0, (V - 25) // 24)
+    cam = cli.synthetic_episode(max(V, 24 * (seg + 2) + 8))
+    clip = synthetic_clip(V, H, W)
+    w2c = mvs.pano_poses(cam, V, seg)
+    t0 = time.perf_counter()
+    st = mvs.sphere_setup(w2c, W, S, D)
+    setup_ms = (time.perf_counter() - t0) * 1e3
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    src, invd, pose = up(st.src_index), up(st.inv_dist_f32), up(st.rel_pose_f32)
+    c2w = up(np.linalg.inv(mvs._w2c_4x4(w2c))[:, :3, :4].astype(np.float32))
+    grey = ops.mvs_luma(clip)
+    dist, conf, win, cost = ops.mvs_sphere_sweep(grey, pose, src, invd, r)
+    xyz = ops.pano_unproject(dist, c2w)
+    P = ops._ptr
+    px = V * H * W
+    samples = int((st.src_index >= 0).sum(1).astype(np.int64).sum()) * H * W * D
+    stages = [
+        stage("sphere_sweep", timed(lambda: ops._call("ew_mvs_sphere_sweep", P(grey), P(pose), P(src), P(invd), P(dist), P(conf), P(win), P(cost),
+                                                      V, H, W, S, D, r), it),
+              px + 16 * px, "grey in once, four planes out; the gathers from the sources hit the caches"),
+        stage("sphere_consistency", timed(lambda: ops._call("ew_mvs_sphere_consistency", P(dist), P(pose), P(src), P(conf), V, H, W, S, 0.02, 2), it),
+              8 * px, "distance and confidence in, confidence out; one gathered distance per present source"),
+        stage("pano_unproject", timed(lambda: ops._call("ew_pano_unproject", P(dist), P(c2w), P(xyz), V, H, W), it), 16 * px,
+              "distance in, three coordinates out"),
+    ]
+    sweep_us = stages[0]["us"]
+    stage_obj = mvs.SphereSweepDepth(n_src=S, planes=D, patch_radius=r)
+    wall = []
+    for _ in range(2):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        stage_obj(clip, pano_w2c=w2c)
+        torch.cuda.synchronize()
+        wall.append(time.perf_counter() - t0)
+    return {"panoramas": V, "height": H, "width": W, "hypotheses": D, "sources": S, "patch_radius": r, "segment": seg, "stages": stages,
+            "warped_samples": samples, "sweep_Gsamples_per_s": round(samples / sweep_us / 1e3, 2), "kernels_ms": round(sum(s["us"] for s in stages) / 1e3, 2),
+            "host_setup_ms": round(setup_ms, 1), "stage_call_wall_ms": round(min(wall) * 1e3, 1)}
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     p.add_argument("--iters", type=int, default=3)
     p.add_argument("--views", type=int, nargs="+", default=[25, 73])
-    p.add_argument("--height", type=int, default=384)
-    p.add_argument("--width", type=int, default=512)
+    p.add_argument("--sphere", action="store_true", help="time the sphere-sweep stage on panoramas (576 x 1024 unless --height / --width say otherwise)")
+    p.add_argument("--height", type=int, default=None, help="default 384 (576 with --sphere)")
+    p.add_argument("--width", type=int, default=None, help="default 512 (1024 with --sphere)")
     p.add_argument("--planes", type=int, default=64)
     p.add_argument("--sources", type=int, default=4)
     p.add_argument("--patch_radius", type=int, default=2)
     p.add_argument("--out", type=str, default=None)
     args = p.parse_args(argv)
+    if args.sphere:
+        H, W = args.height or 576, args.width or 1024
+        rec = {"tool": "bench_mvs --sphere", "device": torch.cuda.get_device_name(0), "iters": args.iters, "hbm_TBps": HBM_TBS,
+               "runs": [run_sphere(V, H, W, args.planes, args.sources, args.patch_radius, args.iters) for V in args.views],
+               "note": "device events around whole entry calls; stage_call_wall_ms is the best of two synchronised SphereSweepDepth calls with "
+                       "the host set-up (host_setup_ms, timed alone), the uploads, the luma pass and the lift.  Per warped sample the sweep "
+                       "evaluates an atan2f, an asinf, a square root and a division besides the bilinear blend and the LDS box filter.  No gate."}
+        return _emit(rec, args.out or os.path.join(ROOT, "profiles", "mvs_sphere_bench.json"))
+    args.height, args.width = args.height or 384, args.width or 512
     rec = {"tool": "bench_mvs", "device": torch.cuda.get_device_name(0), "iters": args.iters, "hbm_TBps": HBM_TBS,
            "runs": [run(V, args.height, args.width, args.planes, args.sources, args.patch_radius, args.iters) for V in args.views],
            "note": "device events around whole entry calls; stage_call_wall_ms is the best of two synchronised PlaneSweepDepth calls with the "
                    "host's float64 homographies (host_setup_ms, timed alone) and their upload.  The sweep is compute-bound: per warped sample two "
                    "IEEE divisions, a bilinear blend of four gathered bytes and the LDS box filter.  No gate."}
+    _emit(rec, args.out)
+
+
+def _emit(rec, out):
     line = json.dumps(rec)
     print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as fh:
             fh.write(line + "\n")
 
 

@@ -55,10 +55,11 @@ def parse_arguments(argv=None):
     p.add_argument("--video_quality", type=int, default=90, help="JPEG quality (1..100) of the --save_video files")
     p.add_argument("--device_png", action="store_true",
                    help="encode the --save_frames PNG files on the device (same names, same pixels, file bytes other than Pillow's)")
-    p.add_argument("--depth_stage", choices=("synthetic", "mvs"), default="synthetic",
-                   help="depth source of the memory hand-off: the stand-in's fixed room, or plane-sweep stereo on the generated frames (opt-in)")
-    p.add_argument("--mvs_planes", type=int, default=64, help="depth planes of --depth_stage mvs")
-    p.add_argument("--mvs_sources", type=int, default=4, help="source views per reference view of --depth_stage mvs")
+    p.add_argument("--depth_stage", choices=("synthetic", "mvs", "mvs_pano"), default="synthetic",
+                   help="depth source of the memory hand-off: the stand-in's fixed room, plane-sweep stereo on the 90-degree views cut from the "
+                        "generated frames (mvs, opt-in), or sphere-sweep stereo on the generated panoramas themselves (mvs_pano, opt-in)")
+    p.add_argument("--mvs_planes", type=int, default=64, help="depth planes (mvs) / distance hypotheses (mvs_pano) of --depth_stage")
+    p.add_argument("--mvs_sources", type=int, default=4, help="source views per reference view of --depth_stage mvs / mvs_pano")
     return p.parse_args(argv)
 
 
