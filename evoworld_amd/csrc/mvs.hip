@@ -10,9 +10,13 @@
 //                        commutes with the mean over the sources because a source is present for a whole view.  The four lowest costs,
 //                        the winner's two neighbours and the previous plane's cost stay in registers, so the volume is never stored.
 //                        Two workgroup barriers per plane; no atomics, no communication between workgroups, every loop bound an argument.
+//   ew_mvs_plane_sweep_volume   the same tile kernel instantiated with VOLUME = true: the same C(k), quantised and staged in LDS
+//                        (mvs_volume.h) so that the uint16 [n,H,W,D] volume is written in runs of hypotheses per pixel -- the input of the
+//                        opt-in semi-global aggregation (mvs_sgm.hip).
 //   ew_mvs_consistency   per pixel: lift, move into each present source with the relative pose, compare with the source's depth at the
 //                        nearest pixel; the confidence is zeroed in place where fewer than min_consistent sources agree.
 #include "common.h"
+#include "mvs_volume.h"
 
 namespace {
 
@@ -20,6 +24,7 @@ constexpr int NT = 256;
 constexpr int TW = 32, TH = 8;                     // tile of one workgroup
 constexpr int RMAX = 3;
 constexpr int HW_MAX = TW + 2 * RMAX, HH_MAX = TH + 2 * RMAX;
+static_assert(NT == 256 && TW == 32 && TH == 8, "mvs_volume.h stages the costs of this tile");
 
 __global__ __launch_bounds__(NT) void luma_kernel(const uint8_t* __restrict__ rgb, uint8_t* __restrict__ grey, long long n) {
     for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < n; i += (long long)gridDim.x * NT) {
@@ -50,15 +55,19 @@ __device__ __forceinline__ float warped_ad(const uint8_t* __restrict__ src, cons
     return fabsf(ref - (top * (1.0f - ay) + bot * ay));
 }
 
+// VOLUME = false: the fused sweep (ew_mvs_plane_sweep), f = blockIdx.z.  VOLUME = true: the same C(k), quantised and stored
+// (ew_mvs_plane_sweep_volume): f = view_begin + blockIdx.z, `vol` [gridDim.z,H,W,D]; the four output planes are not touched.
+template <bool VOLUME>
 __global__ __launch_bounds__(NT) void plane_sweep_kernel(const uint8_t* __restrict__ grey, const float* __restrict__ homog,
                                                          const int* __restrict__ src_index, const float* __restrict__ inv_depth,
                                                          float* __restrict__ depth, float* __restrict__ conf, int* __restrict__ winner,
-                                                         float* __restrict__ win_cost, int F, int H, int W, int S, int D, int r, float oob) {
+                                                         float* __restrict__ win_cost, int F, int H, int W, int S, int D, int r, float oob,
+                                                         uint16_t* __restrict__ vol, float cost_scale, int view_begin) {
     __shared__ float s_ref[HH_MAX * HW_MAX];       // the reference tile with its halo
     __shared__ float s_ad[HH_MAX * HW_MAX];        // per plane: the sum over the sources of the absolute differences
     __shared__ float s_rs[HH_MAX * TW];            // per plane: s_ad summed over the 2r + 1 horizontal taps
     const int t = threadIdx.x;
-    const int f = blockIdx.z;
+    const int f = (VOLUME ? view_begin : 0) + blockIdx.z;
     const int x_org = blockIdx.x * TW - r, y_org = blockIdx.y * TH - r;       // image position of the halo'd tile's corner
     const int hw = TW + 2 * r, hh = TH + 2 * r;
     const long long plane = (long long)H * W;
@@ -119,6 +128,10 @@ __global__ __launch_bounds__(NT) void plane_sweep_kernel(const uint8_t* __restri
         for (int d = 0; d <= 2 * r; ++d) c += s_rs[(ty + d) * TW + tx];
         c = c / denom;
         // s_rs is written again only behind the next plane's first barrier
+        if constexpr (VOLUME) {
+            ew_mvs_stage_cost(c, cost_scale, k, D, vol + (long long)blockIdx.z * plane * D, H, W);
+            continue;
+        }
 
         if (has_left && !has_right && k == k0 + 1) { right = c; has_right = true; }
         if (c < b0) {
@@ -133,7 +146,7 @@ __global__ __launch_bounds__(NT) void plane_sweep_kernel(const uint8_t* __restri
         }
         prev = c;
     }
-    if (!live) return;
+    if (VOLUME || !live) return;
 
     if (k0 < 0) { k0 = 0; b0 = prev; has_right = false; }          // every cost a NaN (non-finite homographies): plane 0, no refinement
     const float* invd = inv_depth + (long long)f * D;
@@ -215,9 +228,32 @@ extern "C" ew_status ew_mvs_plane_sweep(const uint8_t* grey, const float* homogr
                  (uintptr_t)winner_cost) & 3) == 0, "ew_mvs_plane_sweep: the fp32 and int32 arrays must be 4-byte aligned");
     const unsigned gx = (unsigned)((W + TW - 1) / TW), gy = (unsigned)((H + TH - 1) / TH);
     EW_REQUIRE(gy <= 65535, "ew_mvs_plane_sweep: H = %d gives more than 65535 tile rows", H);
-    hipLaunchKernelGGL(plane_sweep_kernel, dim3(gx, gy, (unsigned)F), dim3(NT), 0, (hipStream_t)stream, grey, homographies, src_index, inv_depth,
-                       depth, conf, winner, winner_cost, F, H, W, S, D, patch_radius, oob_cost);
+    hipLaunchKernelGGL(plane_sweep_kernel<false>, dim3(gx, gy, (unsigned)F), dim3(NT), 0, (hipStream_t)stream, grey, homographies, src_index,
+                       inv_depth, depth, conf, winner, winner_cost, F, H, W, S, D, patch_radius, oob_cost, (uint16_t*)nullptr, 0.0f, 0);
     return ew_check_launch("mvs plane_sweep_kernel");
+}
+
+extern "C" ew_status ew_mvs_plane_sweep_volume(const uint8_t* grey, const float* homographies, const int* src_index, const float* inv_depth,
+                                               uint16_t* cost, int F, int H, int W, int S, int D, int patch_radius, float oob_cost,
+                                               float cost_scale, int view_begin, int n_views, void* stream) {
+    EW_REQUIRE(grey && homographies && src_index && inv_depth && cost, "ew_mvs_plane_sweep_volume: NULL pointer");
+    EW_REQUIRE(F >= 1 && F <= 65535 && H >= 1 && W >= 1 && (long long)H * W < (1LL << 31),
+               "ew_mvs_plane_sweep_volume: F = %d must be 1 .. 65535, H = %d and W = %d positive with H W below 2^31", F, H, W);
+    EW_REQUIRE(S >= 1 && D >= 1 && (long long)F * S * D < (1LL << 31),
+               "ew_mvs_plane_sweep_volume: S = %d and D = %d must be positive, F S D below 2^31", S, D);
+    EW_REQUIRE(patch_radius >= 0 && patch_radius <= RMAX, "ew_mvs_plane_sweep_volume: patch_radius = %d must be 0 .. %d", patch_radius, RMAX);
+    EW_REQUIRE(cost_scale > 0.0f && cost_scale < INFINITY, "ew_mvs_plane_sweep_volume: cost_scale = %g must be positive and finite",
+               (double)cost_scale);
+    EW_REQUIRE(view_begin >= 0 && n_views >= 1 && n_views <= F - view_begin,
+               "ew_mvs_plane_sweep_volume: views %d .. %d + %d - 1 must lie in [0, F = %d)", view_begin, view_begin, n_views, F);
+    EW_REQUIRE((((uintptr_t)homographies | (uintptr_t)src_index | (uintptr_t)inv_depth) & 3) == 0 && ((uintptr_t)cost & 1) == 0,
+               "ew_mvs_plane_sweep_volume: the fp32 and int32 arrays must be 4-byte aligned, the volume 2-byte aligned");
+    const unsigned gx = (unsigned)((W + TW - 1) / TW), gy = (unsigned)((H + TH - 1) / TH);
+    EW_REQUIRE(gy <= 65535, "ew_mvs_plane_sweep_volume: H = %d gives more than 65535 tile rows", H);
+    hipLaunchKernelGGL(plane_sweep_kernel<true>, dim3(gx, gy, (unsigned)n_views), dim3(NT), EW_MVS_STAGE_BYTES, (hipStream_t)stream, grey,
+                       homographies, src_index, inv_depth, (float*)nullptr, (float*)nullptr, (int*)nullptr, (float*)nullptr, F, H, W, S, D,
+                       patch_radius, oob_cost, cost, cost_scale, view_begin);
+    return ew_check_launch("mvs plane_sweep_kernel<volume>");
 }
 
 extern "C" ew_status ew_mvs_consistency(const float* depth, const float* rel_pose, const int* src_index, float* conf, int F, int H, int W,

@@ -11,10 +11,13 @@
 //                              2r + 1 horizontal taps (rs), a column pass the 2r + 1 vertical ones.  The four lowest costs, the winner's two
 //                              neighbours and the previous hypothesis' cost stay in registers, so the volume is never stored.  Two workgroup
 //                              barriers per hypothesis; no atomics, no communication between workgroups, every loop bound an argument.
+//   ew_mvs_sphere_sweep_volume the same tile kernel instantiated with VOLUME = true: the same C(k), quantised and staged in LDS
+//                              (mvs_volume.h), written as the uint16 [n,He,We,D] volume the semi-global aggregation reads (mvs_sgm.hip).
 //   ew_mvs_sphere_consistency  per pixel: lift along the pixel's direction, move into each present source with the relative pose, compare the
 //                              point's distance there with the source's distance at the nearest pixel of its direction.
 //   ew_pano_unproject          per pixel: R (dir dist) + t.
 #include "common.h"
+#include "mvs_volume.h"
 
 namespace {
 
@@ -23,6 +26,7 @@ constexpr int TW = 32, TH = 8;                     // tile of one workgroup
 constexpr int RMAX = 3;
 constexpr int HW_MAX = TW + 2 * RMAX, HH_MAX = TH + 2 * RMAX;
 constexpr int CELLS = (HW_MAX * HH_MAX + NT - 1) / NT;      // halo'd cells per thread at most: 3
+static_assert(NT == 256 && TW == 32 && TH == 8, "mvs_volume.h stages the costs of this tile");
 constexpr float PI_F = 3.14159265358979323846f;
 
 // pixel (x, y) -> unit direction in the panorama camera (x right, y down, z forward): the inverse of the map of ew_equi2pers
@@ -75,14 +79,18 @@ __device__ __forceinline__ float warped_ad(const uint8_t* __restrict__ src, cons
     return fabsf(ref - (top * (1.0f - ay) + bot * ay));
 }
 
+// VOLUME = false: the fused sweep (ew_mvs_sphere_sweep), f = blockIdx.z.  VOLUME = true: the same C(k), quantised and stored
+// (ew_mvs_sphere_sweep_volume): f = view_begin + blockIdx.z, `vol` [gridDim.z,He,We,D]; the four output planes are not touched.
+template <bool VOLUME>
 __global__ __launch_bounds__(NT) void sphere_sweep_kernel(const uint8_t* __restrict__ grey, const float* __restrict__ rel_pose,
                                                           const int* __restrict__ src_index, const float* __restrict__ inv_dist,
                                                           float* __restrict__ dist, float* __restrict__ conf, int* __restrict__ winner,
-                                                          float* __restrict__ win_cost, int F, int He, int We, int S, int D, int r) {
+                                                          float* __restrict__ win_cost, int F, int He, int We, int S, int D, int r,
+                                                          uint16_t* __restrict__ vol, float cost_scale, int view_begin) {
     __shared__ float s_ad[HH_MAX * HW_MAX];        // per hypothesis: the sum over the sources of the absolute differences
     __shared__ float s_rs[HH_MAX * TW];            // per hypothesis: s_ad summed over the 2r + 1 horizontal taps
     const int t = threadIdx.x;
-    const int f = blockIdx.z;
+    const int f = (VOLUME ? view_begin : 0) + blockIdx.z;
     const int x_org = blockIdx.x * TW - r, y_org = blockIdx.y * TH - r;       // panorama position of the halo'd tile's corner
     const int hw = TW + 2 * r, hh = TH + 2 * r;
     const long long plane = (long long)He * We;
@@ -157,6 +165,10 @@ __global__ __launch_bounds__(NT) void sphere_sweep_kernel(const uint8_t* __restr
         for (int d = 0; d <= 2 * r; ++d) c += s_rs[(ty + d) * TW + tx];
         c = c / denom;
         // s_rs is written again only behind the next hypothesis' first barrier
+        if constexpr (VOLUME) {
+            ew_mvs_stage_cost(c, cost_scale, k, D, vol + (long long)blockIdx.z * plane * D, He, We);
+            continue;
+        }
 
         if (has_left && !has_right && k == k0 + 1) { right = c; has_right = true; }
         if (c < b0) {
@@ -171,7 +183,7 @@ __global__ __launch_bounds__(NT) void sphere_sweep_kernel(const uint8_t* __restr
         }
         prev = c;
     }
-    if (!live) return;
+    if (VOLUME || !live) return;
 
     if (k0 < 0) { k0 = 0; b0 = prev; has_right = false; }          // every cost a NaN (non-finite poses): hypothesis 0, no refinement
     float inv = invd[k0];
@@ -272,9 +284,34 @@ extern "C" ew_status ew_mvs_sphere_sweep(const uint8_t* grey, const float* rel_p
                  (uintptr_t)winner_cost) & 3) == 0, "ew_mvs_sphere_sweep: the fp32 and int32 arrays must be 4-byte aligned");
     const unsigned gx = (unsigned)((We + TW - 1) / TW), gy = (unsigned)((He + TH - 1) / TH);
     EW_REQUIRE(gy <= 65535, "ew_mvs_sphere_sweep: He = %d gives more than 65535 tile rows", He);
-    hipLaunchKernelGGL(sphere_sweep_kernel, dim3(gx, gy, (unsigned)F), dim3(NT), 0, (hipStream_t)stream, grey, rel_pose, src_index, inv_dist,
-                       dist, conf, winner, winner_cost, F, He, We, S, D, patch_radius);
+    hipLaunchKernelGGL(sphere_sweep_kernel<false>, dim3(gx, gy, (unsigned)F), dim3(NT), 0, (hipStream_t)stream, grey, rel_pose, src_index,
+                       inv_dist, dist, conf, winner, winner_cost, F, He, We, S, D, patch_radius, (uint16_t*)nullptr, 0.0f, 0);
     return ew_check_launch("mvs_sphere sphere_sweep_kernel");
+}
+
+extern "C" ew_status ew_mvs_sphere_sweep_volume(const uint8_t* grey, const float* rel_pose, const int* src_index, const float* inv_dist,
+                                                uint16_t* cost, int F, int He, int We, int S, int D, int patch_radius, float cost_scale,
+                                                int view_begin, int n_views, void* stream) {
+    EW_REQUIRE(grey && rel_pose && src_index && inv_dist && cost, "ew_mvs_sphere_sweep_volume: NULL pointer");
+    EW_REQUIRE(F >= 1 && F <= 65535 && He >= 1 && We >= 1 && (long long)He * We < (1LL << 31),
+               "ew_mvs_sphere_sweep_volume: F = %d must be 1 .. 65535, He = %d and We = %d positive with He We below 2^31", F, He, We);
+    EW_REQUIRE(S >= 1 && D >= 1 && (long long)F * S < (1LL << 27) && (long long)F * D < (1LL << 31),
+               "ew_mvs_sphere_sweep_volume: S = %d and D = %d must be positive, F S below 2^27 and F D below 2^31", S, D);
+    EW_REQUIRE(patch_radius >= 0 && patch_radius <= RMAX, "ew_mvs_sphere_sweep_volume: patch_radius = %d must be 0 .. %d", patch_radius, RMAX);
+    EW_REQUIRE(We >= 2 * patch_radius + 1, "ew_mvs_sphere_sweep_volume: We = %d is narrower than the window of 2 x %d + 1 columns", We,
+               patch_radius);
+    EW_REQUIRE(cost_scale > 0.0f && cost_scale < INFINITY, "ew_mvs_sphere_sweep_volume: cost_scale = %g must be positive and finite",
+               (double)cost_scale);
+    EW_REQUIRE(view_begin >= 0 && n_views >= 1 && n_views <= F - view_begin,
+               "ew_mvs_sphere_sweep_volume: views %d .. %d + %d - 1 must lie in [0, F = %d)", view_begin, view_begin, n_views, F);
+    EW_REQUIRE((((uintptr_t)rel_pose | (uintptr_t)src_index | (uintptr_t)inv_dist) & 3) == 0 && ((uintptr_t)cost & 1) == 0,
+               "ew_mvs_sphere_sweep_volume: the fp32 and int32 arrays must be 4-byte aligned, the volume 2-byte aligned");
+    const unsigned gx = (unsigned)((We + TW - 1) / TW), gy = (unsigned)((He + TH - 1) / TH);
+    EW_REQUIRE(gy <= 65535, "ew_mvs_sphere_sweep_volume: He = %d gives more than 65535 tile rows", He);
+    hipLaunchKernelGGL(sphere_sweep_kernel<true>, dim3(gx, gy, (unsigned)n_views), dim3(NT), EW_MVS_STAGE_BYTES, (hipStream_t)stream, grey,
+                       rel_pose, src_index, inv_dist, (float*)nullptr, (float*)nullptr, (int*)nullptr, (float*)nullptr, F, He, We, S, D,
+                       patch_radius, cost, cost_scale, view_begin);
+    return ew_check_launch("mvs_sphere sphere_sweep_kernel<volume>");
 }
 
 extern "C" ew_status ew_mvs_sphere_consistency(const float* dist, const float* rel_pose, const int* src_index, float* conf, int F, int He,

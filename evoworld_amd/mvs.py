@@ -19,6 +19,14 @@ ew_mvs_sphere_consistency) and lifts spherically (ew_pano_unproject), so the clo
   sphere_setup      sources per panorama, inverse distances, relative poses (host, float64)
   SphereSweepDepth  the callable: uint8 panoramas [F,He,We,3] on the device -> predictions dict with world_points_from_depth
   python -m evoworld_amd.mvs cloud --stage sphere [--sweep_size H W] ...
+
+Both stages take the winner of a box-filtered cost; `aggregate="sgm"` (opt-in) puts semi-global aggregation between the
+cost and the winner, for surfaces with little texture: the sweep stores its quantised cost volume (ew_mvs_*_sweep_volume), 1-D dynamic
+programmes along 4 or 8 path directions are summed (ew_mvs_sgm_aggregate), and the sweeps' winner, parabola and confidence rules run on
+the sum (ew_mvs_sgm_select), in chunks of views that fit a workspace.
+
+  sgm_options / sgm_chunk_views / sgm_sweep    the checked options, the views per chunk, the chunked volume -> aggregate -> select path
+  python -m evoworld_amd.mvs cloud --aggregate sgm [--sgm_p1 1 --sgm_p2 8 --sgm_paths 4] ...
 """
 import argparse
 import json
@@ -185,6 +193,57 @@ def sphere_setup(pano_w2c, We, n_src, D, d_near=None, d_far=None, min_baseline=1
                            has_source=has, inv_dist_f32=inv_dist.astype(np.float32), rel_pose_f32=rel[:, :, :3, :4].astype(np.float32))
 
 
+AGGREGATES = ("box", "sgm")
+
+
+def sgm_options(aggregate="box", sgm_p1=1.0, sgm_p2=8.0, sgm_paths=4, cost_scale=32.0, workspace_bytes=2 << 30):
+    """The checked semi-global options of the two stages (DESIGN.md 4.10) -> SimpleNamespace(aggregate, sgm_p1, sgm_p2 in grey levels;
+    P1, P2 = int(round(p cost_scale)), the penalties in the units of the quantised volume; paths; cost_scale; workspace_bytes).
+    aggregate outside ("box", "sgm"), 0 <= P1 <= P2 <= 4095 violated, paths outside {4, 8}, a cost_scale that is not positive and
+    finite or a workspace below one byte: ValueError."""
+    if aggregate not in AGGREGATES:
+        raise ValueError(f"aggregate must be one of {AGGREGATES}, got {aggregate!r}")
+    cost_scale = float(cost_scale)
+    if not (cost_scale > 0 and np.isfinite(cost_scale)):
+        raise ValueError(f"cost_scale = {cost_scale!r} must be positive and finite")
+    if not (np.isfinite(sgm_p1) and np.isfinite(sgm_p2)):
+        raise ValueError(f"sgm_p1 = {sgm_p1!r} and sgm_p2 = {sgm_p2!r} must be finite")
+    P1, P2 = int(round(float(sgm_p1) * cost_scale)), int(round(float(sgm_p2) * cost_scale))
+    if not 0 <= P1 <= P2 <= 4095:
+        raise ValueError(f"0 <= P1 <= P2 <= 4095 does not hold for sgm_p1 = {sgm_p1!r}, sgm_p2 = {sgm_p2!r} at cost_scale = {cost_scale!r} "
+                         f"(P1 = {P1}, P2 = {P2})")
+    if sgm_paths not in (4, 8):
+        raise ValueError(f"sgm_paths must be 4 or 8, got {sgm_paths!r}")
+    if int(workspace_bytes) < 1:
+        raise ValueError(f"workspace_bytes = {workspace_bytes!r} must be positive")
+    return SimpleNamespace(aggregate=aggregate, sgm_p1=float(sgm_p1), sgm_p2=float(sgm_p2), P1=P1, P2=P2, paths=int(sgm_paths),
+                           cost_scale=cost_scale, workspace_bytes=int(workspace_bytes))
+
+
+def sgm_chunk_views(workspace_bytes, H, W, D):
+    """Views per chunk of the semi-global path: the cost volume and the aggregated one, uint16 [n,H,W,D] each, fit workspace_bytes --
+    max(1, workspace_bytes // (4 H W D))."""
+    return max(1, int(workspace_bytes) // (4 * int(H) * int(W) * int(D)))
+
+
+def sgm_sweep(volume, inv, src_index, F, H, W, D, opt):
+    """The semi-global path of both stages, in chunks of sgm_chunk_views views: volume(view_begin, n_views, out) -> the chunk's cost
+    volume, then ops.mvs_sgm_aggregate, then ops.mvs_sgm_select into the chunk's slice of the four outputs.  Views are aggregated
+    independently, so the chunk size does not change a bit of the result.  -> (depth, conf, winner, winner cost), each [F,H,W]."""
+    from . import ops
+    dev = inv.device
+    n = min(F, sgm_chunk_views(opt.workspace_bytes, H, W, D))
+    cost = torch.empty((n, H, W, D), dtype=torch.uint16, device=dev)
+    agg = torch.empty((n, H, W, D), dtype=torch.uint16, device=dev)
+    outs = [torch.empty((F, H, W), dtype=dt, device=dev) for dt in (torch.float32, torch.float32, torch.int32, torch.float32)]
+    for b in range(0, F, n):
+        m = min(n, F - b)
+        volume(b, m, cost[:m])
+        ops.mvs_sgm_aggregate(cost[:m], opt.P1, opt.P2, opt.paths, out=agg[:m])
+        ops.mvs_sgm_select(agg[:m], inv, src_index, view_begin=b, out=[o[b:b + m] for o in outs])
+    return tuple(outs)
+
+
 def call_depth_model(depth_model, pers_u8, camera_params, segment_id, panos_u8=None):
     """How process_episode calls its depth stage: a stage that declares `wants_panoramas` is called with the episode's panoramas so far
     (panos_u8) and their world->camera matrices (pano_poses) instead of the views; one that declares `wants_view_poses` gets the views and
@@ -204,11 +263,19 @@ class PlaneSweepDepth:
     intrinsic [F,3,3] (pinhole).  n_src sources per view, `planes` depth planes (sweep_setup); patch_radius and oob_cost as
     ew_mvs_plane_sweep; a pixel keeps its confidence when at least min_consistent sources hold a depth within rel_tol of its own
     (min_consistent is capped at the number of sources a view has; 0 switches the check off).  Without view_w2c the poses come from
-    view_poses(camera_params, F, segment_id), the segment inferred from F = 25 + 24 k when it is not given."""
+    view_poses(camera_params, F, segment_id), the segment inferred from F = 25 + 24 k when it is not given.
+    aggregate="sgm" (opt-in; "box", the default, is the fused sweep as before): the winner is taken after semi-global aggregation of the
+    quantised cost volume (sgm_options, sgm_sweep) -- sgm_p1 / sgm_p2 the penalties in grey levels, sgm_paths 4 or 8,
+    cost_scale the volume's units per grey level, workspace_bytes what the two volumes of a chunk of views may take."""
     wants_view_poses = True
 
     def __init__(self, camera_params=None, n_src=4, planes=64, patch_radius=2, oob_cost=48.0, min_consistent=2, rel_tol=0.02,
-                 z_near=None, z_far=None, min_baseline=1e-6, segment_id=None):
+                 z_near=None, z_far=None, min_baseline=1e-6, segment_id=None, aggregate="box", sgm_p1=1.0, sgm_p2=8.0, sgm_paths=4,
+                 cost_scale=32.0, workspace_bytes=2 << 30):
+        self.sgm = sgm_options(aggregate, sgm_p1, sgm_p2, sgm_paths, cost_scale, workspace_bytes)
+        self.aggregate = aggregate
+        if aggregate == "sgm" and not 1 <= planes <= 256:
+            raise ValueError(f"aggregate = 'sgm' takes 1 .. 256 planes, got {planes!r}")
         if patch_radius not in (0, 1, 2, 3):
             raise ValueError(f"patch_radius must be 0 .. 3, got {patch_radius!r}")
         if n_src < 1 or planes < 1:
@@ -242,7 +309,13 @@ class PlaneSweepDepth:
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         src = up(st.src_index)
         grey = ops.mvs_luma(pers_u8.contiguous())
-        depth, conf, _, _ = ops.mvs_plane_sweep(grey, up(st.homographies_f32), src, up(st.inv_depth_f32), self.patch_radius, self.oob_cost)
+        if self.aggregate == "sgm":
+            homog, inv = up(st.homographies_f32), up(st.inv_depth_f32)
+            depth, conf, _, _ = sgm_sweep(lambda b, m, out: ops.mvs_plane_sweep_volume(grey, homog, src, inv, self.patch_radius, self.oob_cost,
+                                                                                       self.sgm.cost_scale, b, m, out=out),
+                                          inv, src, F, H, W, self.planes, self.sgm)
+        else:
+            depth, conf, _, _ = ops.mvs_plane_sweep(grey, up(st.homographies_f32), src, up(st.inv_depth_f32), self.patch_radius, self.oob_cost)
         need = min(self.min_consistent, int((st.src_index >= 0).sum(1).max()))
         if need > 0:
             ops.mvs_consistency(depth, up(st.rel_pose_f32), src, conf, K[0, 0], K[1, 1], K[0, 2], K[1, 2], self.rel_tol, need)
@@ -259,11 +332,17 @@ class SphereSweepDepth:
     sources per panorama, `planes` distance hypotheses (sphere_setup); patch_radius as ew_mvs_sphere_sweep; a pixel keeps its confidence
     when at least min_consistent sources hold a distance within rel_tol of its own (capped at the number of sources a view has; 0
     switches the check off).  sweep_size = (h, w): the panoramas are first resized on the device (ops.resize_linear_u8); default: native
-    size.  Without pano_w2c the poses come from pano_poses(camera_params, F, segment_id), the segment inferred from F = 25 + 24 k."""
+    size.  Without pano_w2c the poses come from pano_poses(camera_params, F, segment_id), the segment inferred from F = 25 + 24 k.
+    aggregate, sgm_p1, sgm_p2, sgm_paths, cost_scale, workspace_bytes: as PlaneSweepDepth (the paths do not wrap across the seam)."""
     wants_panoramas = True
 
     def __init__(self, camera_params=None, n_src=4, planes=64, patch_radius=2, min_consistent=2, rel_tol=0.02, d_near=None, d_far=None,
-                 sweep_size=None, segment_id=None, min_baseline=1e-6):
+                 sweep_size=None, segment_id=None, min_baseline=1e-6, aggregate="box", sgm_p1=1.0, sgm_p2=8.0, sgm_paths=4,
+                 cost_scale=32.0, workspace_bytes=2 << 30):
+        self.sgm = sgm_options(aggregate, sgm_p1, sgm_p2, sgm_paths, cost_scale, workspace_bytes)
+        self.aggregate = aggregate
+        if aggregate == "sgm" and not 1 <= planes <= 256:
+            raise ValueError(f"aggregate = 'sgm' takes 1 .. 256 planes, got {planes!r}")
         if patch_radius not in (0, 1, 2, 3):
             raise ValueError(f"patch_radius must be 0 .. 3, got {patch_radius!r}")
         if n_src < 1 or planes < 1:
@@ -302,7 +381,13 @@ class SphereSweepDepth:
         self.last_setup = st
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         src, rel = up(st.src_index), up(st.rel_pose_f32)
-        dist, conf, _, _ = ops.mvs_sphere_sweep(ops.mvs_luma(frames), rel, src, up(st.inv_dist_f32), self.patch_radius)
+        if self.aggregate == "sgm":
+            grey, inv = ops.mvs_luma(frames), up(st.inv_dist_f32)
+            dist, conf, _, _ = sgm_sweep(lambda b, m, out: ops.mvs_sphere_sweep_volume(grey, rel, src, inv, self.patch_radius,
+                                                                                       self.sgm.cost_scale, b, m, out=out),
+                                         inv, src, F, He, We, self.planes, self.sgm)
+        else:
+            dist, conf, _, _ = ops.mvs_sphere_sweep(ops.mvs_luma(frames), rel, src, up(st.inv_dist_f32), self.patch_radius)
         need = min(self.min_consistent, int((st.src_index >= 0).sum(1).max()))
         if need > 0:
             ops.mvs_sphere_consistency(dist, rel, src, conf, self.rel_tol, need)
@@ -331,14 +416,15 @@ def _cloud_main(args):
     frames = _load_frames(args.frames, n, "cuda")
     n = min(n, len(frames), len(cam))
     frames = frames[:n]
+    sgm = dict(aggregate=args.aggregate, sgm_p1=args.sgm_p1, sgm_p2=args.sgm_p2, sgm_paths=args.sgm_paths)
     if args.stage == "sphere":
-        stage = SphereSweepDepth(cam, n_src=args.sources, planes=args.planes, patch_radius=args.patch_radius, sweep_size=args.sweep_size)
+        stage = SphereSweepDepth(cam, n_src=args.sources, planes=args.planes, patch_radius=args.patch_radius, sweep_size=args.sweep_size, **sgm)
         preds = stage(frames, pano_w2c=pano_poses(cam, n, args.segment))
     else:
         yaws = RP.calculate_target_yaws(cam, n, args.segment)
         views = RP.Equi2Pers(height=args.view_height, width=args.view_width, fov_x=90.0).batch(
             frames, [{"pitch": 0, "roll": 0, "yaw": float(y)} for y in yaws])
-        stage = PlaneSweepDepth(cam, n_src=args.sources, planes=args.planes, patch_radius=args.patch_radius)
+        stage = PlaneSweepDepth(cam, n_src=args.sources, planes=args.planes, patch_radius=args.patch_radius, **sgm)
         preds = stage(views, view_w2c=view_poses(cam, n, args.segment))
     mem = SceneMemory.from_predictions(preds, conf_thres=args.conf_thres, show_cam=args.show_cam, prediction_mode="depth_unproject")
     n_in = len(mem)
@@ -351,7 +437,8 @@ def _cloud_main(args):
     else:
         raise SystemExit(f"--output must end in .glb or .ply (got {args.output})")
     print(json.dumps({"output": args.output, "views": int(n), "points_in": n_in, "points_out": len(mem), "scene_scale": mem.scene_scale,
-                      "planes": args.planes, "sources": args.sources, "stage": args.stage}))
+                      "planes": args.planes, "sources": args.sources, "stage": args.stage, "aggregate": args.aggregate, "sgm_p1": args.sgm_p1,
+                      "sgm_p2": args.sgm_p2, "sgm_paths": args.sgm_paths}))
 
 
 def build_parser():
@@ -374,6 +461,11 @@ def build_parser():
                    help="plane: plane sweep on the 90-degree views (DESIGN.md 4.8); sphere: sphere sweep on the panoramas themselves (4.9)")
     c.add_argument("--sweep_size", type=int, nargs=2, metavar=("H", "W"), default=None,
                    help="--stage sphere: resize the panoramas to H x W on the device before the sweep (default: native size)")
+    c.add_argument("--aggregate", choices=AGGREGATES, default="box",
+                   help="box: the winner of the box-filtered cost (default); sgm: after semi-global aggregation of the cost volume (DESIGN.md 4.10)")
+    c.add_argument("--sgm_p1", type=float, default=1.0, help="--aggregate sgm: the penalty of a one-step change of hypothesis, in grey levels")
+    c.add_argument("--sgm_p2", type=float, default=8.0, help="--aggregate sgm: the penalty of a larger jump, in grey levels")
+    c.add_argument("--sgm_paths", type=int, choices=(4, 8), default=4, help="--aggregate sgm: path directions")
     return p
 
 

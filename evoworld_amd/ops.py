@@ -933,6 +933,131 @@ def pano_unproject(dist, c2w, out=None):
     return out
 
 
+MVS_COST_MAX, MVS_SGM_MAX_D = _lib.EW_MVS_COST_MAX, _lib.EW_MVS_SGM_MAX_D
+
+
+def _mvs_view_range(view_begin, n_views, F_):
+    """(view_begin, n_views) of the views a volume call writes; n_views None: all from view_begin on"""
+    view_begin = int(view_begin)
+    n_views = F_ - view_begin if n_views is None else int(n_views)
+    if view_begin < 0 or n_views < 1 or view_begin + n_views > F_:
+        raise ValueError(f"views {view_begin} .. {view_begin} + {n_views} - 1 must lie in [0, F = {F_})")
+    return view_begin, n_views
+
+
+def _mvs_cost_scale(cost_scale):
+    cost_scale = float(cost_scale)
+    if not (cost_scale > 0 and np.isfinite(cost_scale)):
+        raise ValueError(f"cost_scale = {cost_scale!r} must be positive and finite")
+    return cost_scale
+
+
+def mvs_plane_sweep_volume(grey, homographies, src_index, inv_depth, patch_radius=2, oob_cost=48.0, cost_scale=32.0, view_begin=0,
+                           n_views=None, out=None):
+    """The inputs of mvs_plane_sweep -> the quantised cost volume uint16 [n_views,H,W,D] of the views view_begin .. view_begin + n_views - 1
+    (default: all from view_begin on): q = min(4095, floor(C cost_scale + 0.5)) of the very C(k) mvs_plane_sweep takes its winner from
+    (ew_mvs_plane_sweep_volume).  grey holds all F views.  out: the volume to write into."""
+    if grey.ndim != 3 or grey.numel() == 0:
+        raise ValueError(f"grey must be a non-empty [F,H,W], got {tuple(grey.shape)}")
+    _req(grey, torch.uint8, "grey")
+    F_, H, W = grey.shape
+    S = _mvs_sources(src_index, F_)
+    if inv_depth.ndim != 2 or inv_depth.shape[0] != F_ or inv_depth.shape[1] < 1:
+        raise ValueError(f"inv_depth must be [F = {F_}, D >= 1], got {tuple(inv_depth.shape)}")
+    D = inv_depth.shape[1]
+    if tuple(homographies.shape) != (F_, S, D, 3, 3):
+        raise ValueError(f"homographies must be {(F_, S, D, 3, 3)}, got {tuple(homographies.shape)}")
+    if patch_radius not in (0, 1, 2, 3):
+        raise ValueError(f"patch_radius must be 0 .. 3, got {patch_radius!r}")
+    cost_scale = _mvs_cost_scale(cost_scale)
+    view_begin, n_views = _mvs_view_range(view_begin, n_views, F_)
+    _req(homographies, torch.float32, "homographies"); _req(inv_depth, torch.float32, "inv_depth")
+    cost = _mvs_out(out, (n_views, H, W, D), torch.uint16, grey.device, "out")
+    _call("ew_mvs_plane_sweep_volume", _ptr(grey), _ptr(homographies), _ptr(src_index), _ptr(inv_depth), _ptr(cost), F_, H, W, S, D,
+          int(patch_radius), float(oob_cost), cost_scale, view_begin, n_views)
+    return cost
+
+
+def mvs_sphere_sweep_volume(grey, rel_pose, src_index, inv_dist, patch_radius=2, cost_scale=32.0, view_begin=0, n_views=None, out=None):
+    """The inputs of mvs_sphere_sweep -> the quantised cost volume uint16 [n_views,He,We,D] of the panoramas view_begin .. view_begin +
+    n_views - 1, as mvs_plane_sweep_volume (ew_mvs_sphere_sweep_volume).  out: the volume to write into."""
+    if grey.ndim != 3 or grey.numel() == 0:
+        raise ValueError(f"grey must be a non-empty [F,He,We], got {tuple(grey.shape)}")
+    _req(grey, torch.uint8, "grey")
+    F_, H, W = grey.shape
+    S = _mvs_sources(src_index, F_)
+    if inv_dist.ndim != 2 or inv_dist.shape[0] != F_ or inv_dist.shape[1] < 1:
+        raise ValueError(f"inv_dist must be [F = {F_}, D >= 1], got {tuple(inv_dist.shape)}")
+    D = inv_dist.shape[1]
+    if tuple(rel_pose.shape) != (F_, S, 3, 4):
+        raise ValueError(f"rel_pose must be {(F_, S, 3, 4)}, got {tuple(rel_pose.shape)}")
+    if patch_radius not in (0, 1, 2, 3):
+        raise ValueError(f"patch_radius must be 0 .. 3, got {patch_radius!r}")
+    if W < 2 * patch_radius + 1:
+        raise ValueError(f"We = {W} is narrower than the window of 2 x {patch_radius} + 1 columns")
+    cost_scale = _mvs_cost_scale(cost_scale)
+    view_begin, n_views = _mvs_view_range(view_begin, n_views, F_)
+    _req(rel_pose, torch.float32, "rel_pose"); _req(inv_dist, torch.float32, "inv_dist")
+    cost = _mvs_out(out, (n_views, H, W, D), torch.uint16, grey.device, "out")
+    _call("ew_mvs_sphere_sweep_volume", _ptr(grey), _ptr(rel_pose), _ptr(src_index), _ptr(inv_dist), _ptr(cost), F_, H, W, S, D,
+          int(patch_radius), cost_scale, view_begin, n_views)
+    return cost
+
+
+def _mvs_volume(vol, name):
+    if vol.ndim != 4 or vol.numel() == 0:
+        raise ValueError(f"{name} must be a non-empty [N,H,W,D], got {tuple(vol.shape)}")
+    _req(vol, torch.uint16, name)
+    if not 1 <= vol.shape[3] <= MVS_SGM_MAX_D:
+        raise ValueError(f"{name}: D = {vol.shape[3]} must be 1 .. {MVS_SGM_MAX_D}")
+    return tuple(vol.shape)
+
+
+def mvs_sgm_check_penalties(P1, P2, paths):
+    """0 <= P1 <= P2 <= 4095 as integers and paths in {4, 8}, or ValueError -> (P1, P2, paths) as ints"""
+    if int(P1) != P1 or int(P2) != P2 or not 0 <= P1 <= P2 <= MVS_COST_MAX:
+        raise ValueError(f"0 <= P1 = {P1!r} <= P2 = {P2!r} <= {MVS_COST_MAX} (integers) does not hold")
+    if paths not in (4, 8):
+        raise ValueError(f"paths must be 4 or 8, got {paths!r}")
+    return int(P1), int(P2), int(paths)
+
+
+def mvs_sgm_aggregate(cost, P1, P2, paths=4, out=None):
+    """cost uint16 [N,H,W,D] with values <= 4095 -> agg uint16 [N,H,W,D]: the sum over 4 or 8 path directions of the semi-global
+    recurrence with the penalties 0 <= P1 <= P2 <= 4095, in the volume's units (ew_mvs_sgm_aggregate).  The values are
+    not checked: a cost above 4095 can wrap the 16-bit sum.  out: the volume to write into (not `cost`)."""
+    shape = _mvs_volume(cost, "cost")
+    P1, P2, paths = mvs_sgm_check_penalties(P1, P2, paths)
+    agg = _mvs_out(out, shape, torch.uint16, cost.device, "out")
+    if agg.data_ptr() == cost.data_ptr():
+        raise ValueError("out must not be the cost volume itself")
+    N, H, W, D = shape
+    _call("ew_mvs_sgm_aggregate", _ptr(cost), _ptr(agg), N, H, W, D, P1, P2, paths)
+    return agg
+
+
+def mvs_sgm_select(agg, inv, src_index, view_begin=0, out=None):
+    """agg uint16 [N,H,W,D] of the views view_begin .. view_begin + N - 1, inv fp32 [F,D] (inverse depths or distances), src_index int32
+    [F,S] -> (depth or distance fp32, conf fp32, winner int32, winner cost fp32 in aggregated units), each [N,H,W]: mvs_plane_sweep's
+    winner, parabola and confidence rules on the aggregated costs (ew_mvs_sgm_select).  out: the four output tensors to write into."""
+    N, H, W, D = _mvs_volume(agg, "agg")
+    if inv.ndim != 2 or inv.shape[1] != D or inv.shape[0] < 1:
+        raise ValueError(f"inv must be [F, D = {D}], got {tuple(inv.shape)}")
+    F_ = inv.shape[0]
+    S = _mvs_sources(src_index, F_)
+    view_begin, _ = _mvs_view_range(view_begin, N, F_)
+    _req(inv, torch.float32, "inv")
+    dev = agg.device
+    given = out if out is not None else (None,) * 4
+    depth = _mvs_out(given[0], (N, H, W), torch.float32, dev, "out[0]")
+    conf = _mvs_out(given[1], (N, H, W), torch.float32, dev, "out[1]")
+    winner = _mvs_out(given[2], (N, H, W), torch.int32, dev, "out[2]")
+    cost = _mvs_out(given[3], (N, H, W), torch.float32, dev, "out[3]")
+    _call("ew_mvs_sgm_select", _ptr(agg), _ptr(inv), _ptr(src_index), _ptr(depth), _ptr(conf), _ptr(winner), _ptr(cost), F_, H, W, S, D,
+          view_begin, N)
+    return depth, conf, winner, cost
+
+
 def equi2pers(equi, rot, Hp, Wp, fov_x):
     _req(equi, torch.uint8, "equi"); _req(rot, torch.float32, "rot")
     F_, He, We, _ = equi.shape

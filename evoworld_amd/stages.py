@@ -124,6 +124,13 @@ class HipStages(SyntheticStages):
 
 
 DEPTH_STAGES = ("synthetic", "mvs", "mvs_pano")
+# option of the two sweep stages <- attribute of the parsed arguments; one that is absent or None leaves the stage's default
+MVS_OPTIONS = (("planes", "mvs_planes"), ("n_src", "mvs_sources"), ("aggregate", "mvs_aggregate"), ("sgm_p1", "mvs_p1"), ("sgm_p2", "mvs_p2"),
+               ("sgm_paths", "mvs_paths"))
+
+
+def _mvs_options(args):
+    return {k: getattr(args, a) for k, a in MVS_OPTIONS if getattr(args, a, None) is not None}
 
 
 def load_stages(spec, args, depth_stage=None, **kw):
@@ -131,7 +138,8 @@ def load_stages(spec, args, depth_stage=None, **kw):
     depth_stage (opt-in): 'mvs' replaces ONLY `depth_model` of whichever stages object was chosen by the plane-sweep stereo stage
     (evoworld_amd.mvs.PlaneSweepDepth; planes and sources from args.mvs_planes / args.mvs_sources when they are set); None or
     'synthetic' leaves the object as it is.  'mvs_pano' does the same with the sphere sweep on the panoramas themselves
-    (evoworld_amd.mvs.SphereSweepDepth, same two options)."""
+    (evoworld_amd.mvs.SphereSweepDepth, same two options).  Both also take args.mvs_aggregate ('box' | 'sgm'), args.mvs_p1, args.mvs_p2 and
+    args.mvs_paths, the opt-in semi-global aggregation (MVS_OPTIONS)."""
     if depth_stage not in (None,) + DEPTH_STAGES:
         raise ValueError(f"depth_stage must be one of {DEPTH_STAGES}, got {depth_stage!r}")
     camera_params = kw.get("camera_params")
@@ -146,10 +154,10 @@ def load_stages(spec, args, depth_stage=None, **kw):
         stages = getattr(importlib.import_module(mod), fn or "make_stages")(args)
     if depth_stage == "mvs":
         from .mvs import PlaneSweepDepth
-        opt = {k: v for k, v in (("planes", getattr(args, "mvs_planes", None)), ("n_src", getattr(args, "mvs_sources", None))) if v is not None}
+        opt = _mvs_options(args)
         stages.depth_model = PlaneSweepDepth(camera_params, **opt)
     elif depth_stage == "mvs_pano":
         from .mvs import SphereSweepDepth
-        opt = {k: v for k, v in (("planes", getattr(args, "mvs_planes", None)), ("n_src", getattr(args, "mvs_sources", None))) if v is not None}
+        opt = _mvs_options(args)
         stages.depth_model = SphereSweepDepth(camera_params, **opt)
     return stages

@@ -562,6 +562,43 @@ ew_status ew_mvs_sphere_consistency(const float* dist, const float* rel_pose, co
                                     int S, float rel_tol, int min_consistent, void* stream);
 ew_status ew_pano_unproject(const float* dist, const float* c2w, float* xyz, int F, int He, int We, void* stream);
 
+/* Semi-global aggregation of the sweeps' cost volume (csrc/mvs_sgm.hip and the volume variants in csrc/mvs.hip, csrc/mvs_sphere.hip;
+ * added to ABI 20 without a bump: new symbols only).  Opt-in: between the cost and the winner, 1-D dynamic programmes
+ * along 4 or 8 path directions tie neighbouring pixels together (Hirschmueller's semi-global matching); ew_mvs_plane_sweep and
+ * ew_mvs_sphere_sweep are untouched.  A cost volume is uint16 [N,H,W,D], hypothesis innermost, values <= EW_MVS_COST_MAX; it holds the
+ * views view_begin .. view_begin + N - 1 of a batch of F.  No atomics anywhere: two calls return identical bits, and a view's outputs
+ * depend only on that view and its sources.
+ * ew_mvs_plane_sweep_volume / ew_mvs_sphere_sweep_volume: the inputs of ew_mvs_plane_sweep / ew_mvs_sphere_sweep (grey holds all F views:
+ *   the sources may lie outside the range written) -> cost uint16 [n_views,H,W,D] of the views view_begin .. view_begin + n_views - 1 (0
+ *   <= view_begin, 1 <= n_views <= F - view_begin).  C(k) is exactly the C(k) defined above for the fused sweep -- one cost routine is
+ *   instantiated for both, so the bits of C agree -- and the entry stored is q = min(4095, (int)floorf(C cost_scale + 0.5f)) (product and
+ *   sum rounded separately; cost_scale positive and finite); a NaN stores 4095.  A view without a present slot stores 0 everywhere.
+ * ew_mvs_sgm_aggregate: cost -> agg uint16 [N,H,W,D] (another buffer).  0 <= P1 <= P2 <= 4095, paths 4 or 8, 1 <= D <= EW_MVS_SGM_MAX_D.
+ *   Path directions r = (dx, dy), in order: (+1, 0), (-1, 0), (0, +1), (0, -1), (+1, +1), (-1, -1), (-1, +1), (+1, -1); the last four only
+ *   with paths = 8.  For the pixel p and its predecessor q = p - r: L_r(p, k) = C(p, k) when q is outside the image; otherwise, with m =
+ *   min_j L_r(q, j): L_r(p, k) = C(p, k) + min(L_r(q, k), L_r(q, k - 1) + P1 [k > 0], L_r(q, k + 1) + P1 [k < D - 1], m + P2) - m.
+ *   agg(p, k) = the sum over r of L_r(p, k).  Integers throughout: L <= 4095 + P2 <= 8190, agg <= 65520; exact and independent of any
+ *   order.  The columns of a panorama do NOT wrap here: a ring has no start, so column 0 has no predecessor for (+1, 0) and column W - 1
+ *   none for (-1, 0), whichever sweep made the volume.  Views are aggregated independently of one another.
+ * ew_mvs_sgm_select: agg uint16 [n_views,H,W,D] of the views view_begin .. ; inv fp32 [F,D] (inverse depths or distances); src_index int32
+ *   [F,S] (only the number of present slots of a view is used).  The rules of ew_mvs_plane_sweep, word for word, on S(k) = (float)agg(k)
+ *   in place of C(k): winner k* = the lowest S, ties to the lowest k; with 0 < k* < D - 1 and curv = (S(k* - 1) + S(k* + 1)) - 2 S(k*) > 0:
+ *   off = clamp(0.5 (S(k* - 1) - S(k* + 1)) / curv, -0.5, 0.5) and the inverse moves from inv[k*] by |off| of the way to the neighbour on
+ *   that side; out = 1 / inverse; conf = (S2 - S1) / max(S2, 1e-6), S1 = S(k*), S2 = the lowest S among |k - k*| > 1; conf = 0 without such
+ *   a hypothesis or when the view has no present slot.  Outputs depth (or distance), conf, winner_cost fp32 and winner int32, each
+ *   [n_views,H,W]; winner_cost = S1 is in AGGREGATED units (the sum over the paths of quantised costs), not in grey levels. */
+#define EW_MVS_COST_MAX 4095
+#define EW_MVS_SGM_MAX_D 256
+ew_status ew_mvs_plane_sweep_volume(const uint8_t* grey, const float* homographies, const int* src_index, const float* inv_depth,
+                                    uint16_t* cost, int F, int H, int W, int S, int D, int patch_radius, float oob_cost, float cost_scale,
+                                    int view_begin, int n_views, void* stream);
+ew_status ew_mvs_sphere_sweep_volume(const uint8_t* grey, const float* rel_pose, const int* src_index, const float* inv_dist, uint16_t* cost,
+                                     int F, int He, int We, int S, int D, int patch_radius, float cost_scale, int view_begin, int n_views,
+                                     void* stream);
+ew_status ew_mvs_sgm_aggregate(const uint16_t* cost, uint16_t* agg, int N, int H, int W, int D, int P1, int P2, int paths, void* stream);
+ew_status ew_mvs_sgm_select(const uint16_t* agg, const float* inv, const int* src_index, float* depth, float* conf, int* winner,
+                            float* winner_cost, int F, int H, int W, int S, int D, int view_begin, int n_views, void* stream);
+
 /* Equirect -> perspective bilinear gather (pyequilib Equi2Pers restatement; unified_loop_consistency.py:299-334).
  * equi uint8 [F,He,We,3]; rot [F,3,3] f32 (camera->pano rotation); out uint8 [F,Hp,Wp,3]. */
 ew_status ew_equi2pers(const uint8_t* equi, const float* rot, uint8_t* out, int F, int He, int We, int Hp, int Wp,

@@ -34,6 +34,10 @@ CMD="unified_loop_consistency.py --unet_path $CKPT --svd_path $CKPT --base_folde
 [ -n "$DEPTH_STAGE" ] && CMD="$CMD --depth_stage $DEPTH_STAGE"   # opt-in: mvs = plane-sweep stereo depth from the generated frames (default: synthetic)
 [ -n "$MVS_PLANES" ] && CMD="$CMD --mvs_planes $MVS_PLANES"
 [ -n "$MVS_SOURCES" ] && CMD="$CMD --mvs_sources $MVS_SOURCES"
+[ -n "$MVS_AGGREGATE" ] && CMD="$CMD --mvs_aggregate $MVS_AGGREGATE"   # opt-in: sgm = semi-global aggregation of the sweep's cost volume (default: box)
+[ -n "$MVS_P1" ] && CMD="$CMD --mvs_p1 $MVS_P1"
+[ -n "$MVS_P2" ] && CMD="$CMD --mvs_p2 $MVS_P2"
+[ -n "$MVS_PATHS" ] && CMD="$CMD --mvs_paths $MVS_PATHS"
 [ -n "$VIDEO_FPS" ] && CMD="$CMD --video_fps $VIDEO_FPS"
 [ -n "$VIDEO_QUALITY" ] && CMD="$CMD --video_quality $VIDEO_QUALITY"
 

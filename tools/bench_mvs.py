@@ -5,6 +5,10 @@ hands it: 25 and 73 perspective views of 384 x 512 (the hand-offs after segments
   python tools/bench_mvs.py --sphere [...]      the sphere-sweep stage (csrc/mvs_sphere.hip) on 25 and 73 PANORAMAS of
                                                 576 x 1024: ew_mvs_sphere_sweep, ew_mvs_sphere_consistency, ew_pano_unproject
                                                 (default --out profiles/mvs_sphere_bench.json)
+  python tools/bench_mvs.py --sgm [--sphere] [--sgm_paths 4]    the opt-in semi-global path (csrc/mvs_sgm.hip) at the same
+                                                shapes, in the chunks of views the stage classes use: ew_mvs_*_sweep_volume,
+                                                ew_mvs_sgm_aggregate, ew_mvs_sgm_select, and their sum against the fused sweep timed in
+                                                the same run (default --out profiles/mvs_sgm_bench.json, one entry per sweep kind)
 
 The views: bench_video.synthetic_clip (gradients, a texture of sinusoids, noise of sigma 4) -- the timing does not depend on what the
 sweep finds -- at the poses view_poses gives for the curved synthetic episode of unified_loop_consistency.py.  Device events around
@@ -110,6 +114,53 @@ def run_sphere(V, H, W, D, S, r, it):
             "host_setup_ms": round(setup_ms, 1), "stage_call_wall_ms": round(min(wall) * 1e3, 1)}
 
 
+def run_sgm(V, H, W, D, S, r, it, sphere, paths, p1=1.0, p2=8.0, cost_scale=32.0, workspace_bytes=2 << 30):
+    """volume -> aggregate -> select over all V views in the chunks sgm_sweep uses, each stage timed over all its chunks; the fused sweep
+    of the same inputs is timed in the same run.  Least bytes: the volume is written once (2 B per cell) next to the grey image read;
+    the aggregation must read the cost and write agg once (2 B + 2 B per cell: the floor DESIGN.md 4.10 sets its passes against); the
+    select reads agg once and writes four planes."""
+    import unified_loop_consistency as cli
+    from evoworld_amd import mvs, ops
+    seg = max(0, (V - 25) // 24)
+    cam = cli.synthetic_episode(max(V, 24 * (seg + 2) + 8))
+    clip = synthetic_clip(V, H, W)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    P = ops._ptr
+    grey = ops.mvs_luma(clip)
+    opt = mvs.sgm_options("sgm", p1, p2, paths, cost_scale, workspace_bytes)
+    n = min(V, mvs.sgm_chunk_views(workspace_bytes, H, W, D))
+    chunks = [(b, min(n, V - b)) for b in range(0, V, n)]
+    cost = torch.empty((n, H, W, D), dtype=torch.uint16, device="cuda")
+    agg = torch.empty_like(cost)
+    outs = [torch.empty((V, H, W), dtype=dt, device="cuda") for dt in (torch.float32, torch.float32, torch.int32, torch.float32)]
+    if sphere:
+        st = mvs.sphere_setup(mvs.pano_poses(cam, V, seg), W, S, D)
+        src, inv, pose = up(st.src_index), up(st.inv_dist_f32), up(st.rel_pose_f32)
+        fused = lambda: ops._call("ew_mvs_sphere_sweep", P(grey), P(pose), P(src), P(inv), *[P(o) for o in outs], V, H, W, S, D, r)
+        vol = lambda b, m: ops._call("ew_mvs_sphere_sweep_volume", P(grey), P(pose), P(src), P(inv), P(cost), V, H, W, S, D, r, cost_scale, b, m)
+    else:
+        st = mvs.sweep_setup(mvs.view_poses(cam, V, seg), mvs.pinhole(H, W), S, D)
+        src, inv, homog = up(st.src_index), up(st.inv_depth_f32), up(st.homographies_f32)
+        fused = lambda: ops._call("ew_mvs_plane_sweep", P(grey), P(homog), P(src), P(inv), *[P(o) for o in outs], V, H, W, S, D, r, 48.0)
+        vol = lambda b, m: ops._call("ew_mvs_plane_sweep_volume", P(grey), P(homog), P(src), P(inv), P(cost), V, H, W, S, D, r, 48.0, cost_scale, b, m)
+    each = lambda f: [f(b, m) for b, m in chunks]
+    vol(*chunks[-1])                                       # the aggregation is timed on real costs (the last chunk's)
+    cells, px = V * H * W * D, V * H * W
+    fused_us = timed(fused, it)
+    stages = [
+        stage("sweep_volume", timed(lambda: each(vol), it), px + 2 * cells, "grey in once, the uint16 volume out; the gathers from the sources hit the caches"),
+        stage("sgm_aggregate", timed(lambda: each(lambda b, m: ops._call("ew_mvs_sgm_aggregate", P(cost), P(agg), m, H, W, D, opt.P1, opt.P2, paths)), it),
+              4 * cells, f"the floor: cost read once, agg written once; the {paths} passes move {4 + 6 * (paths - 1)} B per cell"),
+        stage("sgm_select", timed(lambda: each(lambda b, m: ops._call("ew_mvs_sgm_select", P(agg), P(inv), P(src), *[P(o[b:b + m]) for o in outs],
+                                                                      V, H, W, S, D, b, m)), it),
+              2 * cells + 16 * px, "agg in once, four planes out"),
+    ]
+    total = sum(s["us"] for s in stages)
+    return {"views": V, "height": H, "width": W, "planes": D, "sources": S, "patch_radius": r, "paths": paths, "P1": opt.P1, "P2": opt.P2,
+            "cost_scale": cost_scale, "views_per_chunk": n, "chunks": len(chunks), "volume_bytes_per_chunk": 2 * n * H * W * D, "stages": stages,
+            "sgm_path_ms": round(total / 1e3, 2), "fused_sweep_ms": round(fused_us / 1e3, 2), "ratio_to_fused_sweep": round(total / fused_us, 3)}
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     p.add_argument("--iters", type=int, default=3)
@@ -121,7 +172,24 @@ def main(argv=None):
     p.add_argument("--sources", type=int, default=4)
     p.add_argument("--patch_radius", type=int, default=2)
     p.add_argument("--out", type=str, default=None)
+    p.add_argument("--sgm", action="store_true", help="time the semi-global path (volume, aggregate, select) against the fused sweep of the same shape")
+    p.add_argument("--sgm_paths", type=int, choices=(4, 8), default=4)
     args = p.parse_args(argv)
+    if args.sgm:
+        H, W = (args.height or 576, args.width or 1024) if args.sphere else (args.height or 384, args.width or 512)
+        kind = "sphere" if args.sphere else "plane"
+        out = args.out or os.path.join(ROOT, "profiles", "mvs_sgm_bench.json")
+        rec = {}
+        if os.path.exists(out):                            # one file, one entry per sweep kind: keep the other kind's
+            with open(out) as fh:
+                rec = json.loads(fh.read())
+        rec.update({"tool": "bench_mvs --sgm", "device": torch.cuda.get_device_name(0), "hbm_TBps": HBM_TBS,
+                    "note": "device events around whole entry calls, each stage over all its chunks of views; min_bytes is the least a stage must "
+                            "move, GBps and hbm_fraction are that over the time; ratio_to_fused_sweep = (volume + aggregate + select) / the fused "
+                            "sweep of the same inputs in the same run.  No gate.",
+                    kind: {"iters": args.iters,
+                           "runs": [run_sgm(V, H, W, args.planes, args.sources, args.patch_radius, args.iters, args.sphere, args.sgm_paths) for V in args.views]}})
+        return _emit(rec, out)
     if args.sphere:
         H, W = args.height or 576, args.width or 1024
         rec = {"tool": "bench_mvs --sphere", "device": torch.cuda.get_device_name(0), "iters": args.iters, "hbm_TBps": HBM_TBS,

@@ -60,6 +60,11 @@ def parse_arguments(argv=None):
                         "generated frames (mvs, opt-in), or sphere-sweep stereo on the generated panoramas themselves (mvs_pano, opt-in)")
     p.add_argument("--mvs_planes", type=int, default=64, help="depth planes (mvs) / distance hypotheses (mvs_pano) of --depth_stage")
     p.add_argument("--mvs_sources", type=int, default=4, help="source views per reference view of --depth_stage mvs / mvs_pano")
+    p.add_argument("--mvs_aggregate", choices=("box", "sgm"), default="box",
+                   help="--depth_stage mvs / mvs_pano: the winner of the box-filtered cost (box), or after semi-global aggregation of the cost volume (sgm, opt-in)")
+    p.add_argument("--mvs_p1", type=float, default=1.0, help="--mvs_aggregate sgm: the penalty of a one-step change of hypothesis, in grey levels")
+    p.add_argument("--mvs_p2", type=float, default=8.0, help="--mvs_aggregate sgm: the penalty of a larger jump, in grey levels")
+    p.add_argument("--mvs_paths", type=int, choices=(4, 8), default=4, help="--mvs_aggregate sgm: path directions")
     return p.parse_args(argv)
 
 
