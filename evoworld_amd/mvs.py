@@ -27,6 +27,13 @@ the sum (ew_mvs_sgm_select), in chunks of views that fit a workspace.
 
   sgm_options / sgm_chunk_views / sgm_sweep    the checked options, the views per chunk, the chunked volume -> aggregate -> select path
   python -m evoworld_amd.mvs cloud --aggregate sgm [--sgm_p1 1 --sgm_p2 8 --sgm_paths 4] ...
+
+Both match views by the absolute difference of grey levels; `cost="zncc"` (opt-in) matches by zero-mean normalised
+cross-correlation over the same window instead (ew_mvs_*_sweep_zncc, ew_mvs_*_sweep_zncc_volume), which does not move when a frame's
+exposure, contrast or tone drifts against its neighbours'.  Winner, parabola, confidence, consistency and the semi-global path are unchanged.
+
+  cost_options    the checked options
+  python -m evoworld_amd.mvs cloud --cost zncc ...
 """
 import argparse
 import json
@@ -194,10 +201,30 @@ def sphere_setup(pano_w2c, We, n_src, D, d_near=None, d_far=None, min_baseline=1
 
 
 AGGREGATES = ("box", "sgm")
+COSTS = ("sad", "zncc")
+COST_SCALES = {"sad": 32.0, "zncc": 16.0}          # volume units per grey level (sad: 127.97 grey levels clip) / per percent (zncc: 200 % -> 3200)
+
+
+def cost_options(cost="sad", patch_radius=2, var_floor=1.0, cost_scale=None):
+    """The checked matching-cost options of the two stages -> SimpleNamespace(cost, var_floor, cost_scale): cost_scale
+    None resolves to COST_SCALES[cost].  A cost outside COSTS, patch_radius 0 with "zncc" (a single tap has no variance), a var_floor that
+    is negative or not finite: ValueError naming the value."""
+    if cost not in COSTS:
+        raise ValueError(f"cost must be one of {COSTS}, got {cost!r}")
+    if cost == "zncc" and patch_radius == 0:
+        raise ValueError(f"cost = 'zncc' takes patch_radius 1 .. 3 (a single tap has no variance), got {patch_radius!r}")
+    try:
+        vf = float(var_floor)
+    except (TypeError, ValueError):
+        raise ValueError(f"var_floor = {var_floor!r} must be a number") from None
+    if not (vf >= 0 and np.isfinite(vf)):
+        raise ValueError(f"var_floor = {var_floor!r} must be finite and not negative")
+    return SimpleNamespace(cost=cost, var_floor=vf, cost_scale=COST_SCALES[cost] if cost_scale is None else cost_scale)
 
 
 def sgm_options(aggregate="box", sgm_p1=1.0, sgm_p2=8.0, sgm_paths=4, cost_scale=32.0, workspace_bytes=2 << 30):
-    """The checked semi-global options of the two stages (DESIGN.md 4.10) -> SimpleNamespace(aggregate, sgm_p1, sgm_p2 in grey levels;
+    """The checked semi-global options of the two stages -> SimpleNamespace(aggregate, sgm_p1, sgm_p2 in the cost's own
+    units -- grey levels for the sad cost, percent of 1 - ZNCC for the zncc cost (DESIGN.md 4.11);
     P1, P2 = int(round(p cost_scale)), the penalties in the units of the quantised volume; paths; cost_scale; workspace_bytes).
     aggregate outside ("box", "sgm"), 0 <= P1 <= P2 <= 4095 violated, paths outside {4, 8}, a cost_scale that is not positive and
     finite or a workspace below one byte: ValueError."""
@@ -266,13 +293,19 @@ class PlaneSweepDepth:
     view_poses(camera_params, F, segment_id), the segment inferred from F = 25 + 24 k when it is not given.
     aggregate="sgm" (opt-in; "box", the default, is the fused sweep as before): the winner is taken after semi-global aggregation of the
     quantised cost volume (sgm_options, sgm_sweep) -- sgm_p1 / sgm_p2 the penalties in grey levels, sgm_paths 4 or 8,
-    cost_scale the volume's units per grey level, workspace_bytes what the two volumes of a chunk of views may take."""
+    cost_scale the volume's units per grey level, workspace_bytes what the two volumes of a chunk of views may take.
+    cost="zncc" (opt-in; "sad", the default, is the sweep as before): the matching cost is 100 (1 - ZNCC) over the window instead of the
+    mean absolute difference, for views whose exposure, contrast or tone drift (cost_options) -- var_floor in grey levels
+    squared, zncc_oob_cost the cost in percent of a source whose window leaves it (oob_cost stays the sad cost's, in grey levels);
+    sgm_p1 / sgm_p2 are then in percent, and cost_scale (None: 32 for sad, 16 for zncc) in volume units per percent."""
     wants_view_poses = True
 
     def __init__(self, camera_params=None, n_src=4, planes=64, patch_radius=2, oob_cost=48.0, min_consistent=2, rel_tol=0.02,
                  z_near=None, z_far=None, min_baseline=1e-6, segment_id=None, aggregate="box", sgm_p1=1.0, sgm_p2=8.0, sgm_paths=4,
-                 cost_scale=32.0, workspace_bytes=2 << 30):
-        self.sgm = sgm_options(aggregate, sgm_p1, sgm_p2, sgm_paths, cost_scale, workspace_bytes)
+                 cost_scale=None, workspace_bytes=2 << 30, cost="sad", var_floor=1.0, zncc_oob_cost=100.0):
+        self.match = cost_options(cost, patch_radius, var_floor, cost_scale)
+        self.cost, self.var_floor, self.zncc_oob_cost = cost, self.match.var_floor, float(zncc_oob_cost)
+        self.sgm = sgm_options(aggregate, sgm_p1, sgm_p2, sgm_paths, self.match.cost_scale, workspace_bytes)
         self.aggregate = aggregate
         if aggregate == "sgm" and not 1 <= planes <= 256:
             raise ValueError(f"aggregate = 'sgm' takes 1 .. 256 planes, got {planes!r}")
@@ -311,9 +344,16 @@ class PlaneSweepDepth:
         grey = ops.mvs_luma(pers_u8.contiguous())
         if self.aggregate == "sgm":
             homog, inv = up(st.homographies_f32), up(st.inv_depth_f32)
-            depth, conf, _, _ = sgm_sweep(lambda b, m, out: ops.mvs_plane_sweep_volume(grey, homog, src, inv, self.patch_radius, self.oob_cost,
-                                                                                       self.sgm.cost_scale, b, m, out=out),
-                                          inv, src, F, H, W, self.planes, self.sgm)
+            if self.cost == "zncc":
+                volume = lambda b, m, out: ops.mvs_plane_sweep_zncc_volume(grey, homog, src, inv, self.patch_radius, self.zncc_oob_cost,
+                                                                           self.var_floor, self.sgm.cost_scale, b, m, out=out)
+            else:
+                volume = lambda b, m, out: ops.mvs_plane_sweep_volume(grey, homog, src, inv, self.patch_radius, self.oob_cost,
+                                                                      self.sgm.cost_scale, b, m, out=out)
+            depth, conf, _, _ = sgm_sweep(volume, inv, src, F, H, W, self.planes, self.sgm)
+        elif self.cost == "zncc":
+            depth, conf, _, _ = ops.mvs_plane_sweep_zncc(grey, up(st.homographies_f32), src, up(st.inv_depth_f32), self.patch_radius,
+                                                         self.zncc_oob_cost, self.var_floor)
         else:
             depth, conf, _, _ = ops.mvs_plane_sweep(grey, up(st.homographies_f32), src, up(st.inv_depth_f32), self.patch_radius, self.oob_cost)
         need = min(self.min_consistent, int((st.src_index >= 0).sum(1).max()))
@@ -333,13 +373,16 @@ class SphereSweepDepth:
     when at least min_consistent sources hold a distance within rel_tol of its own (capped at the number of sources a view has; 0
     switches the check off).  sweep_size = (h, w): the panoramas are first resized on the device (ops.resize_linear_u8); default: native
     size.  Without pano_w2c the poses come from pano_poses(camera_params, F, segment_id), the segment inferred from F = 25 + 24 k.
-    aggregate, sgm_p1, sgm_p2, sgm_paths, cost_scale, workspace_bytes: as PlaneSweepDepth (the paths do not wrap across the seam)."""
+    aggregate, sgm_p1, sgm_p2, sgm_paths, cost_scale, workspace_bytes: as PlaneSweepDepth (the paths do not wrap across the seam).
+    cost, var_floor: as PlaneSweepDepth (every direction lands in a source panorama: there is no out-of-image cost)."""
     wants_panoramas = True
 
     def __init__(self, camera_params=None, n_src=4, planes=64, patch_radius=2, min_consistent=2, rel_tol=0.02, d_near=None, d_far=None,
                  sweep_size=None, segment_id=None, min_baseline=1e-6, aggregate="box", sgm_p1=1.0, sgm_p2=8.0, sgm_paths=4,
-                 cost_scale=32.0, workspace_bytes=2 << 30):
-        self.sgm = sgm_options(aggregate, sgm_p1, sgm_p2, sgm_paths, cost_scale, workspace_bytes)
+                 cost_scale=None, workspace_bytes=2 << 30, cost="sad", var_floor=1.0):
+        self.match = cost_options(cost, patch_radius, var_floor, cost_scale)
+        self.cost, self.var_floor = cost, self.match.var_floor
+        self.sgm = sgm_options(aggregate, sgm_p1, sgm_p2, sgm_paths, self.match.cost_scale, workspace_bytes)
         self.aggregate = aggregate
         if aggregate == "sgm" and not 1 <= planes <= 256:
             raise ValueError(f"aggregate = 'sgm' takes 1 .. 256 planes, got {planes!r}")
@@ -383,9 +426,14 @@ class SphereSweepDepth:
         src, rel = up(st.src_index), up(st.rel_pose_f32)
         if self.aggregate == "sgm":
             grey, inv = ops.mvs_luma(frames), up(st.inv_dist_f32)
-            dist, conf, _, _ = sgm_sweep(lambda b, m, out: ops.mvs_sphere_sweep_volume(grey, rel, src, inv, self.patch_radius,
-                                                                                       self.sgm.cost_scale, b, m, out=out),
-                                         inv, src, F, He, We, self.planes, self.sgm)
+            if self.cost == "zncc":
+                volume = lambda b, m, out: ops.mvs_sphere_sweep_zncc_volume(grey, rel, src, inv, self.patch_radius, self.var_floor,
+                                                                            self.sgm.cost_scale, b, m, out=out)
+            else:
+                volume = lambda b, m, out: ops.mvs_sphere_sweep_volume(grey, rel, src, inv, self.patch_radius, self.sgm.cost_scale, b, m, out=out)
+            dist, conf, _, _ = sgm_sweep(volume, inv, src, F, He, We, self.planes, self.sgm)
+        elif self.cost == "zncc":
+            dist, conf, _, _ = ops.mvs_sphere_sweep_zncc(ops.mvs_luma(frames), rel, src, up(st.inv_dist_f32), self.patch_radius, self.var_floor)
         else:
             dist, conf, _, _ = ops.mvs_sphere_sweep(ops.mvs_luma(frames), rel, src, up(st.inv_dist_f32), self.patch_radius)
         need = min(self.min_consistent, int((st.src_index >= 0).sum(1).max()))
@@ -416,7 +464,7 @@ def _cloud_main(args):
     frames = _load_frames(args.frames, n, "cuda")
     n = min(n, len(frames), len(cam))
     frames = frames[:n]
-    sgm = dict(aggregate=args.aggregate, sgm_p1=args.sgm_p1, sgm_p2=args.sgm_p2, sgm_paths=args.sgm_paths)
+    sgm = dict(aggregate=args.aggregate, sgm_p1=args.sgm_p1, sgm_p2=args.sgm_p2, sgm_paths=args.sgm_paths, cost=args.cost)
     if args.stage == "sphere":
         stage = SphereSweepDepth(cam, n_src=args.sources, planes=args.planes, patch_radius=args.patch_radius, sweep_size=args.sweep_size, **sgm)
         preds = stage(frames, pano_w2c=pano_poses(cam, n, args.segment))
@@ -438,7 +486,7 @@ def _cloud_main(args):
         raise SystemExit(f"--output must end in .glb or .ply (got {args.output})")
     print(json.dumps({"output": args.output, "views": int(n), "points_in": n_in, "points_out": len(mem), "scene_scale": mem.scene_scale,
                       "planes": args.planes, "sources": args.sources, "stage": args.stage, "aggregate": args.aggregate, "sgm_p1": args.sgm_p1,
-                      "sgm_p2": args.sgm_p2, "sgm_paths": args.sgm_paths}))
+                      "sgm_p2": args.sgm_p2, "sgm_paths": args.sgm_paths, "cost": args.cost}))
 
 
 def build_parser():
@@ -463,9 +511,12 @@ def build_parser():
                    help="--stage sphere: resize the panoramas to H x W on the device before the sweep (default: native size)")
     c.add_argument("--aggregate", choices=AGGREGATES, default="box",
                    help="box: the winner of the box-filtered cost (default); sgm: after semi-global aggregation of the cost volume (DESIGN.md 4.10)")
-    c.add_argument("--sgm_p1", type=float, default=1.0, help="--aggregate sgm: the penalty of a one-step change of hypothesis, in grey levels")
-    c.add_argument("--sgm_p2", type=float, default=8.0, help="--aggregate sgm: the penalty of a larger jump, in grey levels")
+    c.add_argument("--sgm_p1", type=float, default=1.0,
+                   help="--aggregate sgm: the penalty of a one-step change of hypothesis, in the cost's units: grey levels (--cost sad), percent of 1 - ZNCC (--cost zncc)")
+    c.add_argument("--sgm_p2", type=float, default=8.0, help="--aggregate sgm: the penalty of a larger jump, in the same units; with --cost zncc a larger one, 32, recovered more of a weak, noisy, flickering scene than 8 (DESIGN.md 4.11)")
     c.add_argument("--sgm_paths", type=int, choices=(4, 8), default=4, help="--aggregate sgm: path directions")
+    c.add_argument("--cost", choices=COSTS, default="sad",
+                   help="sad: the mean absolute difference of grey levels (default); zncc: 100 (1 - ZNCC) over the window, for frames whose exposure or tone drifts (DESIGN.md 4.11)")
     return p
 
 

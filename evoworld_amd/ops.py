@@ -1004,6 +1004,107 @@ def mvs_sphere_sweep_volume(grey, rel_pose, src_index, inv_dist, patch_radius=2,
     return cost
 
 
+def _mvs_zncc_options(patch_radius, var_floor):
+    """patch_radius 1 .. 3 (a single tap has no variance) and a finite var_floor >= 0, or ValueError -> (int, float)"""
+    if patch_radius not in (1, 2, 3):
+        raise ValueError(f"patch_radius must be 1 .. 3 for the zncc cost, got {patch_radius!r}")
+    var_floor = float(var_floor)
+    if not (var_floor >= 0 and np.isfinite(var_floor)):
+        raise ValueError(f"var_floor = {var_floor!r} must be finite and not negative")
+    return int(patch_radius), var_floor
+
+
+def _mvs_plane_inputs(grey, homographies, src_index, inv_depth):
+    """the shape and dtype checks of mvs_plane_sweep -> (F, H, W, S, D)"""
+    if grey.ndim != 3 or grey.numel() == 0:
+        raise ValueError(f"grey must be a non-empty [F,H,W], got {tuple(grey.shape)}")
+    _req(grey, torch.uint8, "grey")
+    F_, H, W = grey.shape
+    S = _mvs_sources(src_index, F_)
+    if inv_depth.ndim != 2 or inv_depth.shape[0] != F_ or inv_depth.shape[1] < 1:
+        raise ValueError(f"inv_depth must be [F = {F_}, D >= 1], got {tuple(inv_depth.shape)}")
+    D = inv_depth.shape[1]
+    if tuple(homographies.shape) != (F_, S, D, 3, 3):
+        raise ValueError(f"homographies must be {(F_, S, D, 3, 3)}, got {tuple(homographies.shape)}")
+    _req(homographies, torch.float32, "homographies"); _req(inv_depth, torch.float32, "inv_depth")
+    return F_, H, W, S, D
+
+
+def _mvs_sphere_inputs(grey, rel_pose, src_index, inv_dist, patch_radius):
+    """the shape and dtype checks of mvs_sphere_sweep -> (F, He, We, S, D)"""
+    if grey.ndim != 3 or grey.numel() == 0:
+        raise ValueError(f"grey must be a non-empty [F,He,We], got {tuple(grey.shape)}")
+    _req(grey, torch.uint8, "grey")
+    F_, H, W = grey.shape
+    S = _mvs_sources(src_index, F_)
+    if inv_dist.ndim != 2 or inv_dist.shape[0] != F_ or inv_dist.shape[1] < 1:
+        raise ValueError(f"inv_dist must be [F = {F_}, D >= 1], got {tuple(inv_dist.shape)}")
+    D = inv_dist.shape[1]
+    if tuple(rel_pose.shape) != (F_, S, 3, 4):
+        raise ValueError(f"rel_pose must be {(F_, S, 3, 4)}, got {tuple(rel_pose.shape)}")
+    if W < 2 * patch_radius + 1:
+        raise ValueError(f"We = {W} is narrower than the window of 2 x {patch_radius} + 1 columns")
+    _req(rel_pose, torch.float32, "rel_pose"); _req(inv_dist, torch.float32, "inv_dist")
+    return F_, H, W, S, D
+
+
+def _mvs_four_outputs(out, shape, dev):
+    given = out if out is not None else (None,) * 4
+    return [_mvs_out(g, shape, dt, dev, f"out[{i}]") for i, (g, dt) in enumerate(zip(given, (torch.float32, torch.float32, torch.int32, torch.float32)))]
+
+
+def mvs_plane_sweep_zncc(grey, homographies, src_index, inv_depth, patch_radius=2, oob_cost=100.0, var_floor=1.0, out=None):
+    """The inputs of mvs_plane_sweep -> (depth fp32, conf fp32, winner int32, winner cost fp32 in percent), each [F,H,W], with
+    100 (1 - ZNCC) over the window as the matching cost (ew_mvs_plane_sweep_zncc).  patch_radius 1 .. 3; oob_cost: the cost,
+    in percent, of a source whose window leaves it; var_floor: grey levels squared.  out: the four output tensors to write into."""
+    patch_radius, var_floor = _mvs_zncc_options(patch_radius, var_floor)
+    F_, H, W, S, D = _mvs_plane_inputs(grey, homographies, src_index, inv_depth)
+    depth, conf, winner, cost = _mvs_four_outputs(out, (F_, H, W), grey.device)
+    _call("ew_mvs_plane_sweep_zncc", _ptr(grey), _ptr(homographies), _ptr(src_index), _ptr(inv_depth), _ptr(depth), _ptr(conf), _ptr(winner),
+          _ptr(cost), F_, H, W, S, D, patch_radius, float(oob_cost), var_floor)
+    return depth, conf, winner, cost
+
+
+def mvs_plane_sweep_zncc_volume(grey, homographies, src_index, inv_depth, patch_radius=2, oob_cost=100.0, var_floor=1.0, cost_scale=16.0,
+                                view_begin=0, n_views=None, out=None):
+    """The inputs of mvs_plane_sweep_zncc -> the quantised cost volume uint16 [n_views,H,W,D] of the views view_begin .. view_begin +
+    n_views - 1: q = min(4095, floor(C cost_scale + 0.5)) of the very C(k) mvs_plane_sweep_zncc takes its winner from
+    (ew_mvs_plane_sweep_zncc_volume).  out: the volume to write into."""
+    patch_radius, var_floor = _mvs_zncc_options(patch_radius, var_floor)
+    F_, H, W, S, D = _mvs_plane_inputs(grey, homographies, src_index, inv_depth)
+    cost_scale = _mvs_cost_scale(cost_scale)
+    view_begin, n_views = _mvs_view_range(view_begin, n_views, F_)
+    cost = _mvs_out(out, (n_views, H, W, D), torch.uint16, grey.device, "out")
+    _call("ew_mvs_plane_sweep_zncc_volume", _ptr(grey), _ptr(homographies), _ptr(src_index), _ptr(inv_depth), _ptr(cost), F_, H, W, S, D,
+          patch_radius, float(oob_cost), var_floor, cost_scale, view_begin, n_views)
+    return cost
+
+
+def mvs_sphere_sweep_zncc(grey, rel_pose, src_index, inv_dist, patch_radius=2, var_floor=1.0, out=None):
+    """The inputs of mvs_sphere_sweep -> (radial distance fp32, conf fp32, winner int32, winner cost fp32 in percent), each [F,He,We], with
+    100 (1 - ZNCC) over the window as the matching cost (ew_mvs_sphere_sweep_zncc).  patch_radius 1 .. 3."""
+    patch_radius, var_floor = _mvs_zncc_options(patch_radius, var_floor)
+    F_, H, W, S, D = _mvs_sphere_inputs(grey, rel_pose, src_index, inv_dist, patch_radius)
+    dist, conf, winner, cost = _mvs_four_outputs(out, (F_, H, W), grey.device)
+    _call("ew_mvs_sphere_sweep_zncc", _ptr(grey), _ptr(rel_pose), _ptr(src_index), _ptr(inv_dist), _ptr(dist), _ptr(conf), _ptr(winner),
+          _ptr(cost), F_, H, W, S, D, patch_radius, var_floor)
+    return dist, conf, winner, cost
+
+
+def mvs_sphere_sweep_zncc_volume(grey, rel_pose, src_index, inv_dist, patch_radius=2, var_floor=1.0, cost_scale=16.0, view_begin=0,
+                                 n_views=None, out=None):
+    """The inputs of mvs_sphere_sweep_zncc -> the quantised cost volume uint16 [n_views,He,We,D], as mvs_plane_sweep_zncc_volume
+    (ew_mvs_sphere_sweep_zncc_volume).  out: the volume to write into."""
+    patch_radius, var_floor = _mvs_zncc_options(patch_radius, var_floor)
+    F_, H, W, S, D = _mvs_sphere_inputs(grey, rel_pose, src_index, inv_dist, patch_radius)
+    cost_scale = _mvs_cost_scale(cost_scale)
+    view_begin, n_views = _mvs_view_range(view_begin, n_views, F_)
+    cost = _mvs_out(out, (n_views, H, W, D), torch.uint16, grey.device, "out")
+    _call("ew_mvs_sphere_sweep_zncc_volume", _ptr(grey), _ptr(rel_pose), _ptr(src_index), _ptr(inv_dist), _ptr(cost), F_, H, W, S, D,
+          patch_radius, var_floor, cost_scale, view_begin, n_views)
+    return cost
+
+
 def _mvs_volume(vol, name):
     if vol.ndim != 4 or vol.numel() == 0:
         raise ValueError(f"{name} must be a non-empty [N,H,W,D], got {tuple(vol.shape)}")

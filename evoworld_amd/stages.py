@@ -126,7 +126,7 @@ class HipStages(SyntheticStages):
 DEPTH_STAGES = ("synthetic", "mvs", "mvs_pano")
 # option of the two sweep stages <- attribute of the parsed arguments; one that is absent or None leaves the stage's default
 MVS_OPTIONS = (("planes", "mvs_planes"), ("n_src", "mvs_sources"), ("aggregate", "mvs_aggregate"), ("sgm_p1", "mvs_p1"), ("sgm_p2", "mvs_p2"),
-               ("sgm_paths", "mvs_paths"))
+               ("sgm_paths", "mvs_paths"), ("cost", "mvs_cost"))
 
 
 def _mvs_options(args):
@@ -139,7 +139,8 @@ def load_stages(spec, args, depth_stage=None, **kw):
     (evoworld_amd.mvs.PlaneSweepDepth; planes and sources from args.mvs_planes / args.mvs_sources when they are set); None or
     'synthetic' leaves the object as it is.  'mvs_pano' does the same with the sphere sweep on the panoramas themselves
     (evoworld_amd.mvs.SphereSweepDepth, same two options).  Both also take args.mvs_aggregate ('box' | 'sgm'), args.mvs_p1, args.mvs_p2 and
-    args.mvs_paths, the opt-in semi-global aggregation (MVS_OPTIONS)."""
+    args.mvs_paths, the opt-in semi-global aggregation (MVS_OPTIONS), and args.mvs_cost ('sad' | 'zncc'), the opt-in
+    matching cost for frames whose exposure or tone drifts."""
     if depth_stage not in (None,) + DEPTH_STAGES:
         raise ValueError(f"depth_stage must be one of {DEPTH_STAGES}, got {depth_stage!r}")
     camera_params = kw.get("camera_params")

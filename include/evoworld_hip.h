@@ -599,6 +599,47 @@ ew_status ew_mvs_sgm_aggregate(const uint16_t* cost, uint16_t* agg, int N, int H
 ew_status ew_mvs_sgm_select(const uint16_t* agg, const float* inv, const int* src_index, float* depth, float* conf, int* winner,
                             float* winner_cost, int F, int H, int W, int S, int D, int view_begin, int n_views, void* stream);
 
+/* Zero-mean normalised cross-correlation as the sweeps' matching cost (csrc/mvs_zncc.hip; added to ABI 20 without a bump: new symbols
+ * only).  Opt-in, for views whose exposure, contrast or tone drift against each other: a sum of absolute differences
+ * reads such a drift as a depth error, a correlation of zero-mean patches does not.  The four SAD entries above are untouched.  Stands in
+ * for the same lines of the reference (unified_loop_consistency.py:336-368).  fp32 in the order written below, sqrtf and IEEE division
+ * only; no atomics: two calls return identical bits, and a view's outputs depend only on that view and its sources.
+ * Notation: reference view f, pixel p, hypothesis k, present source slot s; nf = (float)n.
+ * Window: the (2 patch_radius + 1)^2 window of p.  Plane: only the taps inside the reference image count.  Sphere: only the rows inside
+ *   [0, He) count, and the columns are taken modulo We.  n = the taps that count.  patch_radius 1 .. 3 (a single tap has no variance: 0 is
+ *   refused with EW_ERR_INVALID_ARG); sphere: We >= 2 patch_radius + 1.
+ * Samples: a(t) = I_ref(t) - 128; b(t) = bilinear(I_src, warp_k(t)) - 128, the warp and the bilinear blend exactly those of
+ *   ew_mvs_plane_sweep / ew_mvs_sphere_sweep (same formulas, same order; the 128 is subtracted last).  Plane: a tap whose sample leaves
+ *   the source -- q2 <= 0 (or not a number) or (sx, sy) outside [0, W - 1] x [0, H - 1] -- makes the whole window of that slot invalid.
+ *   Sphere: a point on the source's centre or a non-finite point (|Ps| not positive and finite) gives b(t) = a(t), the neutral choice
+ *   ew_mvs_sphere_sweep makes with AD = 0; no window is invalid.
+ * Sums: Sa, Saa, Sb, Sbb, Sab = the sums of a, a a, b, b b, a b over the window, each product rounded, then added in the box filter's
+ *   order: a row's taps left to right starting from 0, then the row sums top to bottom starting from 0.
+ * Correlation: cov = nf Sab - Sa Sb; va = max(nf Saa - Sa Sa, 0), vb = max(nf Sbb - Sb Sb, 0); fl = var_floor (nf nf); den = sqrtf(va vb +
+ *   fl fl); zncc = cov / den, and 0 where den is 0 (possible only with var_floor = 0).  var_floor is in grey levels squared, finite and not
+ *   negative: with var_floor > 0 a flat window scores zncc = 0, never a NaN.
+ * Cost per slot: cost_s = 100 (1 - zncc), a percentage in [0, 200]; an invalid plane window gives cost_s = oob_cost (also in percent).
+ * Cost per hypothesis: C(k) = (the sum of cost_s over the present slots in slot order, starting from 0) / present slots.  A view without a
+ *   present slot: every C is 0, k* = 0, conf = 0, as in the SAD entries.
+ * ew_mvs_plane_sweep_zncc / ew_mvs_sphere_sweep_zncc: the arguments of ew_mvs_plane_sweep / ew_mvs_sphere_sweep plus var_floor.  Winner,
+ *   ties, parabola, runner-up, confidence and the four outputs follow the rules of ew_mvs_plane_sweep, word for word, on this C;
+ *   winner_cost is in percent.
+ * ew_mvs_plane_sweep_zncc_volume / ew_mvs_sphere_sweep_zncc_volume: the arguments of ew_mvs_plane_sweep_volume /
+ *   ew_mvs_sphere_sweep_volume plus var_floor -> cost uint16 [n_views,H,W,D]: q = min(4095, (int)floorf(C cost_scale + 0.5f)) of exactly the
+ *   C of the fused entry (one cost routine is instantiated for both).  cost_scale = 16 maps 200 % to 3200. */
+ew_status ew_mvs_plane_sweep_zncc(const uint8_t* grey, const float* homographies, const int* src_index, const float* inv_depth, float* depth,
+                                  float* conf, int* winner, float* winner_cost, int F, int H, int W, int S, int D, int patch_radius,
+                                  float oob_cost, float var_floor, void* stream);
+ew_status ew_mvs_plane_sweep_zncc_volume(const uint8_t* grey, const float* homographies, const int* src_index, const float* inv_depth,
+                                         uint16_t* cost, int F, int H, int W, int S, int D, int patch_radius, float oob_cost, float var_floor,
+                                         float cost_scale, int view_begin, int n_views, void* stream);
+ew_status ew_mvs_sphere_sweep_zncc(const uint8_t* grey, const float* rel_pose, const int* src_index, const float* inv_dist, float* dist,
+                                   float* conf, int* winner, float* winner_cost, int F, int He, int We, int S, int D, int patch_radius,
+                                   float var_floor, void* stream);
+ew_status ew_mvs_sphere_sweep_zncc_volume(const uint8_t* grey, const float* rel_pose, const int* src_index, const float* inv_dist,
+                                          uint16_t* cost, int F, int He, int We, int S, int D, int patch_radius, float var_floor,
+                                          float cost_scale, int view_begin, int n_views, void* stream);
+
 /* Equirect -> perspective bilinear gather (pyequilib Equi2Pers restatement; unified_loop_consistency.py:299-334).
  * equi uint8 [F,He,We,3]; rot [F,3,3] f32 (camera->pano rotation); out uint8 [F,Hp,Wp,3]. */
 ew_status ew_equi2pers(const uint8_t* equi, const float* rot, uint8_t* out, int F, int He, int We, int Hp, int Wp,

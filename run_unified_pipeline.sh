@@ -38,6 +38,7 @@ CMD="unified_loop_consistency.py --unet_path $CKPT --svd_path $CKPT --base_folde
 [ -n "$MVS_P1" ] && CMD="$CMD --mvs_p1 $MVS_P1"
 [ -n "$MVS_P2" ] && CMD="$CMD --mvs_p2 $MVS_P2"
 [ -n "$MVS_PATHS" ] && CMD="$CMD --mvs_paths $MVS_PATHS"
+[ -n "$MVS_COST" ] && CMD="$CMD --mvs_cost $MVS_COST"   # opt-in: zncc = match by normalised cross-correlation, for frames whose exposure or tone drifts (default: sad)
 [ -n "$VIDEO_FPS" ] && CMD="$CMD --video_fps $VIDEO_FPS"
 [ -n "$VIDEO_QUALITY" ] && CMD="$CMD --video_quality $VIDEO_QUALITY"
 

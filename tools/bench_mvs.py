@@ -9,6 +9,10 @@ hands it: 25 and 73 perspective views of 384 x 512 (the hand-offs after segments
                                                 shapes, in the chunks of views the stage classes use: ew_mvs_*_sweep_volume,
                                                 ew_mvs_sgm_aggregate, ew_mvs_sgm_select, and their sum against the fused sweep timed in
                                                 the same run (default --out profiles/mvs_sgm_bench.json, one entry per sweep kind)
+  python tools/bench_mvs.py --zncc              the opt-in ZNCC matching cost (csrc/mvs_zncc.hip): its four entries next to
+                                                their SAD twins, in one process and on the same inputs -- 25 views of 384 x 512 and 25
+                                                panoramas of 288 x 512, 64 hypotheses, 4 sources, patch radius 2 (default --out
+                                                profiles/mvs_zncc_bench.json)
 
 The views: bench_video.synthetic_clip (gradients, a texture of sinusoids, noise of sigma 4) -- the timing does not depend on what the
 sweep finds -- at the poses view_poses gives for the curved synthetic episode of unified_loop_consistency.py.  Device events around
@@ -161,6 +165,41 @@ def run_sgm(V, H, W, D, S, r, it, sphere, paths, p1=1.0, p2=8.0, cost_scale=32.0
             "sgm_path_ms": round(total / 1e3, 2), "fused_sweep_ms": round(fused_us / 1e3, 2), "ratio_to_fused_sweep": round(total / fused_us, 3)}
 
 
+def run_zncc(V, H, W, D, S, r, it, sphere, cost_scale=16.0):
+    """The fused sweep and the volume entry of one sweep kind with the SAD cost and with the ZNCC cost, all V views in one call each"""
+    import unified_loop_consistency as cli
+    from evoworld_amd import mvs, ops
+    seg = max(0, (V - 25) // 24)
+    cam = cli.synthetic_episode(max(V, 24 * (seg + 2) + 8))
+    clip = synthetic_clip(V, H, W)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    P = ops._ptr
+    grey = ops.mvs_luma(clip)
+    vol = torch.empty((V, H, W, D), dtype=torch.uint16, device="cuda")
+    outs = [torch.empty((V, H, W), dtype=dt, device="cuda") for dt in (torch.float32, torch.float32, torch.int32, torch.float32)]
+    if sphere:
+        st = mvs.sphere_setup(mvs.pano_poses(cam, V, seg), W, S, D)
+        src, inv, pose = up(st.src_index), up(st.inv_dist_f32), up(st.rel_pose_f32)
+        head, dims = (P(grey), P(pose), P(src), P(inv)), (V, H, W, S, D, r)
+        calls = {"sad": lambda: ops._call("ew_mvs_sphere_sweep", *head, *[P(o) for o in outs], *dims),
+                 "zncc": lambda: ops._call("ew_mvs_sphere_sweep_zncc", *head, *[P(o) for o in outs], *dims, 1.0),
+                 "sad_volume": lambda: ops._call("ew_mvs_sphere_sweep_volume", *head, P(vol), *dims, 32.0, 0, V),
+                 "zncc_volume": lambda: ops._call("ew_mvs_sphere_sweep_zncc_volume", *head, P(vol), *dims, 1.0, cost_scale, 0, V)}
+    else:
+        st = mvs.sweep_setup(mvs.view_poses(cam, V, seg), mvs.pinhole(H, W), S, D)
+        src, inv, homog = up(st.src_index), up(st.inv_depth_f32), up(st.homographies_f32)
+        head, dims = (P(grey), P(homog), P(src), P(inv)), (V, H, W, S, D, r)
+        calls = {"sad": lambda: ops._call("ew_mvs_plane_sweep", *head, *[P(o) for o in outs], *dims, 48.0),
+                 "zncc": lambda: ops._call("ew_mvs_plane_sweep_zncc", *head, *[P(o) for o in outs], *dims, 100.0, 1.0),
+                 "sad_volume": lambda: ops._call("ew_mvs_plane_sweep_volume", *head, P(vol), *dims, 48.0, 32.0, 0, V),
+                 "zncc_volume": lambda: ops._call("ew_mvs_plane_sweep_zncc_volume", *head, P(vol), *dims, 100.0, 1.0, cost_scale, 0, V)}
+    us = {name: round(timed(fn, it), 1) for name, fn in calls.items()}
+    samples = int((st.src_index >= 0).sum(1).astype(np.int64).sum()) * H * W * D
+    return {"views": V, "height": H, "width": W, "hypotheses": D, "sources": S, "patch_radius": r, "us": us, "warped_samples": samples,
+            "zncc_Gsamples_per_s": round(samples / us["zncc"] / 1e3, 2), "sad_Gsamples_per_s": round(samples / us["sad"] / 1e3, 2),
+            "ratio_fused_zncc_to_sad": round(us["zncc"] / us["sad"], 3), "ratio_volume_zncc_to_sad": round(us["zncc_volume"] / us["sad_volume"], 3)}
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     p.add_argument("--iters", type=int, default=3)
@@ -174,7 +213,17 @@ def main(argv=None):
     p.add_argument("--out", type=str, default=None)
     p.add_argument("--sgm", action="store_true", help="time the semi-global path (volume, aggregate, select) against the fused sweep of the same shape")
     p.add_argument("--sgm_paths", type=int, choices=(4, 8), default=4)
+    p.add_argument("--zncc", action="store_true", help="time the four ZNCC entries next to their SAD twins, on 25 views of 384 x 512 and 25 panoramas of 288 x 512")
     args = p.parse_args(argv)
+    if args.zncc:
+        V = args.views[0]
+        rec = {"tool": "bench_mvs --zncc", "device": torch.cuda.get_device_name(0), "iters": args.iters,
+               "note": "device events around whole entry calls, SAD and ZNCC entries in one process on the same inputs; us per call over all "
+                       "views.  Per (hypothesis, source) the ZNCC sweep runs its own box filter of three sums behind two workgroup barriers, "
+                       "where the SAD sweep runs one filter of one sum per hypothesis.  No gate and no speed claim.",
+               "plane": run_zncc(V, args.height or 384, args.width or 512, args.planes, args.sources, args.patch_radius, args.iters, False),
+               "sphere": run_zncc(V, args.height or 288, args.width or 512, args.planes, args.sources, args.patch_radius, args.iters, True)}
+        return _emit(rec, args.out or os.path.join(ROOT, "profiles", "mvs_zncc_bench.json"))
     if args.sgm:
         H, W = (args.height or 576, args.width or 1024) if args.sphere else (args.height or 384, args.width or 512)
         kind = "sphere" if args.sphere else "plane"

@@ -62,9 +62,13 @@ def parse_arguments(argv=None):
     p.add_argument("--mvs_sources", type=int, default=4, help="source views per reference view of --depth_stage mvs / mvs_pano")
     p.add_argument("--mvs_aggregate", choices=("box", "sgm"), default="box",
                    help="--depth_stage mvs / mvs_pano: the winner of the box-filtered cost (box), or after semi-global aggregation of the cost volume (sgm, opt-in)")
-    p.add_argument("--mvs_p1", type=float, default=1.0, help="--mvs_aggregate sgm: the penalty of a one-step change of hypothesis, in grey levels")
-    p.add_argument("--mvs_p2", type=float, default=8.0, help="--mvs_aggregate sgm: the penalty of a larger jump, in grey levels")
+    p.add_argument("--mvs_p1", type=float, default=1.0,
+                   help="--mvs_aggregate sgm: the penalty of a one-step change of hypothesis, in the cost's units: grey levels (--mvs_cost sad), percent of 1 - ZNCC (--mvs_cost zncc)")
+    p.add_argument("--mvs_p2", type=float, default=8.0, help="--mvs_aggregate sgm: the penalty of a larger jump, in the same units; with --mvs_cost zncc a larger one, 32, recovered more of a weak, noisy, flickering scene than 8 (DESIGN.md 4.11)")
     p.add_argument("--mvs_paths", type=int, choices=(4, 8), default=4, help="--mvs_aggregate sgm: path directions")
+    p.add_argument("--mvs_cost", choices=("sad", "zncc"), default="sad",
+                   help="--depth_stage mvs / mvs_pano: match by the absolute difference of grey levels (sad), or by zero-mean normalised cross-correlation "
+                        "over the same window (zncc, opt-in), which does not move when a frame's exposure or tone drifts")
     return p.parse_args(argv)
 
 
