@@ -472,6 +472,14 @@ GEN3_CASES = {
     # lose 2.3 % of three rounds and run whole tiles)
     "G12": dict(kind="conv", tiles=550, per_wg=(3, 4), n=110, H=64, W=80, C=128, O=256, stride=2, shift=1,
                 schedule="tail", dp_rounds=1, sk_tiles=294),
+    # the 256-wide instance on the VAE attention's score schedule (M = N = 9216 there, c_acc = 1 / sqrt(512)): split output WITHOUT a
+    # residual (<0, 17>), 20 x 13 tiles in three full bands of 4 columns and a ragged band of one, ragged last row tile
+    "G13": dict(kind="dense", tiles=260, per_wg=(1, 2), M=5000, N=3328, K=512, bias=False, split=True, band=4,
+                coef=(512 ** -0.5, 1.0, 1.0), epi="<0, 17>"),
+    # the 256-wide instance with TWO tile columns and a stream-K tail: the VAE res-block's conv2 (3x3, split r1, <1, 18>); 68 images
+    # of 32 x 32 = 272 x 2 tiles: one data-parallel round, 288 tail tiles
+    "G14": dict(kind="conv", tiles=544, per_wg=(3, 3), n=68, H=32, W=32, C=64, O=512, r1="s", split=True, epi="<1, 18>",
+                schedule="tail", dp_rounds=1, sk_tiles=288),
 }
 
 

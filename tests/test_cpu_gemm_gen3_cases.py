@@ -7,7 +7,8 @@ from gemm_cases import (GEN3_CASES, case_dims, case_operands, gen3_case_plan, ge
                         gen3_rowbias_rows, gen3_tile_ids, piece_diff, tile_coords)
 
 G = 256
-TAIL = ("G5", "G10", "G12")
+TAIL = ("G5", "G10", "G12", "G14")
+B256 = {"G12": "gemm3b_kernel<1, 0>", "G13": "gemm3b_kernel<0, 17>", "G14": "gemm3b_kernel<1, 18>"}      # the 256-wide instance
 
 
 def test_every_case_has_the_schedule_its_comment_claims():
@@ -15,8 +16,8 @@ def test_every_case_has_the_schedule_its_comment_claims():
         M, N, K, geglu, unit, _ = case_dims(c)
         pl = gen3_case_plan(c, G)
         assert pl.taken, cid
-        assert (pl.BM, pl.BN) == ((256, 256) if cid == "G12" else (256, 320)), cid
-        assert pl.kernel.startswith("gemm3b_kernel<1, " if cid == "G12" else "gemm3_kernel<"), (cid, pl.kernel)
+        assert (pl.BM, pl.BN) == ((256, 256) if cid in B256 else (256, 320)), cid
+        assert pl.kernel == B256[cid] if cid in B256 else pl.kernel.startswith("gemm3_kernel<"), (cid, pl.kernel)
         assert "epi" not in c or pl.kernel.endswith(c["epi"]), (cid, pl.kernel)
         assert pl.tiles == c["tiles"] > G and pl.tiles == pl.tiles_m * pl.tiles_n, (cid, pl.tiles)
         n_items = [len(it) for it in pl.items]
@@ -29,14 +30,30 @@ def test_every_case_has_the_schedule_its_comment_claims():
         assert p4.taken and p4.schedule == "whole" and (p4.kernel, p4.tiles_m, p4.tiles_n, p4.band) == (pl.kernel, pl.tiles_m, pl.tiles_n, pl.band), cid
     # the facts the table's comments rely on
     plan = lambda cid: gen3_case_plan(GEN3_CASES[cid], G)
-    assert (plan("G1").nk, plan("G3").nk, plan("G8").nk, plan("G11").nk, plan("G12").nk) == (1, 2, 9, 3, 18)
+    assert (plan("G1").nk, plan("G3").nk, plan("G8").nk, plan("G11").nk, plan("G12").nk, plan("G13").nk, plan("G14").nk) == (1, 2, 9, 3, 18, 8, 9)
     assert (plan("G2").tiles_n, plan("G3").tiles_n, plan("G6").tiles_n, plan("G7").tiles_n) == (2, 3, 8, 6)
+    assert (plan("G12").tiles_n, plan("G13").tiles_n, plan("G14").tiles_n) == (1, 13, 2)
     assert (plan("G2").epi & 6 and plan("G2").epi & 16) and plan("G4").epi == 23 and plan("G10").kernel == "gemm3_kernel<1, 19>"
     assert GEN3_CASES["G1"]["M"] % 256 and GEN3_CASES["G6"]["N"] * GEN3_CASES["G6"]["K"] * 2 <= 3 << 20
     # G7: a workgroup's consecutive tiles lie in different bands (band 0 holds ids < 4 * tiles_m)
     p7 = plan("G7")
     two = [it for it in p7.items if len(it) == 2]
     assert two and all(tile_coords(a[0], p7.tiles_m, 6, 4)[1] < 4 <= tile_coords(b[0], p7.tiles_m, 6, 4)[1] for a, b in two)
+    # G13: split output without a residual; 20 x 13 tiles in three full bands and a ragged band of ONE column (ids 240 .. 259 run down
+    # column 12); the last row tile is ragged; the workgroups with two items cross from band 0 into the ragged band
+    p13, c13 = plan("G13"), GEN3_CASES["G13"]
+    assert case_operands(c13) == {"lo"} and p13.epi == 17 and c13["M"] % 256 and c13["N"] * c13["K"] * 2 > 3 << 20
+    assert (p13.tiles_m, p13.tiles_n, p13.band) == (20, 13, 4) and 13 % 4 == 1
+    assert [tile_coords(i, 20, 13, 4) for i in (0, 3, 4, 79, 80, 239, 240, 259)] == [(0, 0), (0, 3), (1, 0), (19, 3), (0, 4), (19, 11), (0, 12), (19, 12)]
+    two = [it for it in p13.items if len(it) == 2]
+    assert len(two) == 4 and all(tile_coords(a[0], 20, 13, 4)[1] < 4 and tile_coords(b[0], 20, 13, 4)[1] == 12 for a, b in two)
+    # the VAE's own launches take the same instance, variant and band: scores (whole tiles, 5-6 per workgroup) and P V (half split)
+    ps = gen3_plan(9216, 9216, 512, "dense", {"lo"}, G)
+    assert ps.taken and (ps.kernel, ps.schedule, ps.tiles, ps.band) == (p13.kernel, "whole", 1296, 4)
+    assert sorted({len(it) for it in ps.items}) == [5, 6]
+    # G14: two tile columns on the 256-wide instance, split residual staged through LDS (EPI & 6), tail
+    p14 = plan("G14")
+    assert p14.epi == 18 and p14.epi & 6 and p14.epi & 16 and (p14.BN, p14.tiles_n) == (256, 2)
     # G8 / G9: 500 tiles lose 2.3 % of two rounds; the issue's 150-image form of G12 (750 tiles) loses 2.3 % of three and has no tail
     assert 1 - 500 / 512 <= 0.04 < 1 - 550 / 768
     assert gen3_plan(150 * 1280, 256, 1152, "conv", set(), G).schedule == "whole"
@@ -79,6 +96,17 @@ def test_plan_routing_rules():
     assert pl.taken and (pl.schedule, pl.grid, pl.sk_tiles, pl.dp_rounds) == ("half", 232, 116, 0)
     assert all(len(it) == 1 and it[0][2] - it[0][1] == 80 for it in pl.items)
     assert not take(7200, 1280, 8128, "dense", set(), G) and not take(7200, 1280, 10240, "dense", set(), G, debug=4)
+    # ... on the 256-wide instance: 8 tiles is the fewest (test_gpu_gemm_gen3.py's half_b256_min, also with a ragged last row tile), and
+    # the VAE attention's P V at 9216 tokens
+    for M in (1024, 1000):
+        pl = gen3_plan(M, 512, 8192, "dense", {"r1", "lo"}, G)
+        assert pl.taken and (pl.kernel, pl.schedule, pl.grid, pl.sk_tiles) == ("gemm3b_kernel<0, 19>", "half", 16, 8)
+        assert all(len(it) == 1 and it[0][2] - it[0][1] == 64 for it in pl.items)
+    assert not take(768, 512, 8192, "dense", {"r1", "lo"}, G) and not take(1024, 512, 8128, "dense", {"r1", "lo"}, G)
+    pl = gen3_plan(9216, 512, 9216, "dense", set(), G)
+    assert pl.taken and (pl.kernel, pl.schedule, pl.grid, pl.sk_tiles) == ("gemm3b_kernel<0, 0>", "half", 144, 72)
+    assert all(len(it) == 1 and it[0][2] - it[0][1] == 72 for it in pl.items)
+    assert not take(512, 9216, 512, "dense", set(), G)                   # V^T = W_v X^T: generation 2
 
 
 def _check_schedule(pl):
@@ -117,7 +145,8 @@ def test_schedules_cover_every_tile_once():
         _check_schedule(gen3_case_plan(c, G))
         _check_schedule(gen3_case_plan(c, G, debug=4))
     for args in [(256 * 900, 320, 576, "conv", set(), G), (7200, 1280, 10240, "dense", set(), G), (256 * 700, 640, 1280, "dense", set(), 64),
-                 (256 * 230, 320, 64, "dense", set(), G), (256 * 61, 1280, 64, "dense", set(), 64)]:
+                 (256 * 230, 320, 64, "dense", set(), G), (256 * 61, 1280, 64, "dense", set(), 64),
+                 (9216, 9216, 512, "dense", {"lo"}, G), (9216, 512, 9216, "dense", set(), G), (1000, 512, 8192, "dense", {"r1", "lo"}, G)]:
         pl = gen3_plan(*args)
         assert pl.taken, args
         _check_schedule(pl)

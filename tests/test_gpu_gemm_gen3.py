@@ -15,8 +15,9 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_l2
-from gemm_cases import _nhwc, _pack3, conv3x3_ref64, convt3_ref64, guarded
+from gemm_cases import _nhwc, _pack3, conv3x3_ref64, convt3_ref64, gen3_plan, guarded, guarded_planes
 from kernel_checks import report
+from vae_cases import denormal_fraction, softmax_rows_f16
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -93,6 +94,11 @@ WORST_ROW = {
     'stream-K dense_res ld+64': (1.8e-06, 9.5e-07),  # measured worst row; rel-L2 8.18e-07 row 28293
     'stream-K dense_k320 ld+8': (0.00047, 0.000237),  # measured worst row; rel-L2 0.000209 row 109435
     'stream-K half_dense ld+64': (1.8e-06, 9.04e-07),  # measured worst row; rel-L2 8.35e-07 row 1013
+    # the 256-wide instance on the half split: (bound, worst row of GENERATION 1 against fp64 measured on an MI355X), bound = 2 x that
+    # measurement rounded down to two digits, applied to generation 3, generation 2 and generation 1 (test_gpu_gemm_gen3_rounds.py's rule)
+    'stream-K half_b256_min M=1024 ld+64': (1.8e-06, 9.123e-07),  # generation 1 vs fp64: rel-L2 8.15e-07, worst row 459
+    'stream-K half_b256_min M=1000 ld+8': (1.8e-06, 9.127e-07),  # generation 1 vs fp64: rel-L2 8.16e-07, worst row 740
+    'stream-K half_b256_attn M=9216 ld+64': (0.00047, 0.0002392),  # generation 1 vs fp64: rel-L2 2.07e-04, worst row 2536
     'b256 dense 61237x256x320 bias ld+8': (0.00051, 0.000259),  # measured worst row; rel-L2 0.000208 row 21735
     'b256 dense 61237x256x320 bias ld+8 (gen-b)': (0.00051, 0.000259),  # measured worst row; rel-L2 0.000208 row 21735
     'b256 dense 52011x512x192 rb+r1 ld+8': (0.00048, 0.000243),  # measured worst row; rel-L2 0.000207 row 30010
@@ -345,13 +351,82 @@ def _conv_temporal_case(ops, lib, ld_pad):
 
 
 # ----------------------------------------------------------------------------- stream-K tail
-@pytest.mark.parametrize("case", ["dense_res", "conv", "convt", "dense_k320", "half_dense", "half_conv"])
+def _half_b256_case(ops, lib, case, M):
+    """The HALF split on the 256-wide instance (gemm3b_kernel), which half_dense / half_conv (N = 1280) never reach.
+    half_b256_min: M = 1024 / 1000 (ragged last row tile), N = 512, K = 8192 -- 8 tiles on a grid of 16, the smallest problem plan3
+    puts there; half_dense's operands (bias + split r1 -> <0, 19>).  half_b256_attn: the VAE attention's P V at 9216 tokens, M = 9216,
+    N = 512, K = 9216, no bias (<0, 0>, grid 144, 72 K-tiles per half); A = fp16 softmax rows of 2.3 * randn scores, most of whose
+    entries are fp16 denormals, W = randn V^T.
+    Guarded, twice-prefilled outputs; the restated plan and the kernel name; against the ew_set_gemm_debug(4) launch (generation 2)
+    under 1e-4; generation 3, generation 2 and generation 1 against the fp64 product per row."""
+    N = 512
+    attn = case == "half_b256_attn"
+    if attn:
+        K = 9216
+        x = softmax_rows_f16(M, K, device=DEV)
+        frac = denormal_fraction(x)
+        print(f"stream-K {case}: {frac:.3f} of A are non-zero fp16 denormals, row sums {float(x.float().sum(1).mean()):.4f}")
+        assert frac > 0.5                                            # a condition on the input
+        w = torch.randn(N, K, generator=torch.Generator().manual_seed(12)).half().to(DEV)
+        b = r1 = None
+        run = lambda out, ld: ops.gemm(x, w, out, M=M, N=N, c1=K, lda=K, ld_out=ld)
+        operands, split = set(), False
+    else:
+        K = 8192
+        g = torch.Generator().manual_seed(11)
+        rnd_ = lambda *s: (torch.rand(*s, generator=g) * 2 - 1)
+        x, w, b = rnd_(M, K).half().to(DEV), (rnd_(N, K) / 64).half().to(DEV), rnd_(N).half().to(DEV)
+        r1 = ops.Res.from_float(rnd_(M, N).to(DEV) * 3)
+        run = lambda out, ld: ops.gemm(x, w, out, M=M, N=N, c1=K, lda=K, bias=b, r1=r1, ld_r1=N, ld_out=ld)
+        operands, split = {"r1", "lo"}, True
+    ld_pad = 64 if M % 256 == 0 else 8
+    G = lib.ew_get_cu_budget()
+    plan = gen3_plan(M, N, K, "dense", operands, G, ld=N + ld_pad)
+    assert plan.taken and plan.schedule == "half" and plan.kernel.startswith("gemm3b_kernel<0, ") and plan.grid == 2 * plan.tiles <= G, \
+        (plan.kernel, plan.schedule, plan.tiles, G)
+    assert all(len(it) == 1 and it[0][2] - it[0][1] == K // 128 for it in plan.items)
+    assert not gen3_plan(M, N, K, "dense", operands, G, debug=4, ld=N + ld_pad).taken
+    dec = lambda hi, lo: ops.Res(hi, lo).float() if split else hi.float()
+    try:
+        hi, lo, name = guarded_planes(lib, 3, plan.kernel, run, M, N, ld_pad, split)
+        a = dec(hi, lo)
+        assert name == plan.kernel, (name, plan.kernel)
+        assert lib.ew_gemm_streamk_status() == 0
+        lib.ew_set_gemm_debug(4)                                 # no split: generation 2's tiles
+        c = guarded(lib, 3, "gemm2_kernel", run, M, N, ld_pad, split)
+    finally:
+        lib.ew_set_gemm_debug(0)
+    g1 = guarded(lib, 1, "gemm_kernel", run, M, N, ld_pad, split)
+    assert lib.ew_gemm_streamk_status() == 0
+    err = rel_l2(a.cpu(), c.cpu())
+    print(f"stream-K {case} M={M}: {name}, grid {plan.grid}; rel-L2 vs generation 2 {err:.2e}, max abs {float((a - c).abs().max()):.3e}")
+    y = x.double() @ w.double().T
+    if not attn:
+        y = y + b.double() + r1.float().double()
+    key = f"stream-K {case} M={M} ld+{ld_pad}"
+    tol = 2e-5 if split else 1e-3
+    failed = []
+    for label, got in (("generation 1", g1), ("generation 2", c), ("generation 3", a)):       # every figure is printed before the test fails
+        try:
+            report(f"{key} {label}", got, y, WORST_ROW[key][0], tol)
+        except AssertionError as e:
+            failed.append(str(e))
+    assert float(a.abs().mean()) > 1e-3
+    assert err < 1e-4
+    assert not failed, "\n".join(failed)
+
+
+@pytest.mark.parametrize("case", ["dense_res", "conv", "convt", "dense_k320", "half_dense", "half_conv", "half_b256_min", "half_b256_attn"])
 def test_streamk_tail_matches_whole_tile_schedule(case):
     """Generation 3 splits the last round of tiles along K (stream-K tail) when whole-tile rounds would idle > 4 % of the chip.
     Same problem with the split switched off (ew_set_gemm_debug bit 2): results may differ only by the fp32 summation order of the
     split tiles, i.e. by rare 1-ulp flips of the fp16 outputs; the split itself is deterministic (two runs bit-identical)."""
     from evoworld_amd import _lib, ops
     lib = _lib.load()
+    if case.startswith("half_b256"):
+        for M in ((1024, 1000) if case == "half_b256_min" else (9216,)):
+            _half_b256_case(ops, lib, case, M)
+        return
     g = torch.Generator().manual_seed(11)
     rnd = lambda *s: (torch.rand(*s, generator=g) * 2 - 1)
     if case == "dense_res":                  # level-1 feed-forward down projection: 900 tiles = 3.52 rounds
