@@ -248,7 +248,8 @@ def attn_spatial_log2(q, k, vt, o, n_seq, S, heads, ld_qk, ld_vt, ld_o):
 
 def quant_rows_fp8(x):
     """x fp16 [rows, K] -> (q uint8 [rows, K] holding OCP e4m3 bytes, scale fp32 [rows]): scale = amax(row) / 448 (1 for an all-zero
-    row), q = e4m3(x / scale) (ew_quant_rows_fp8).  K % 8 == 0, K <= 2048."""
+    row), q = e4m3(x * (1 / scale)), each of the three operations one fp32 rounding, the convert to nearest even (ew_quant_rows_fp8; not
+    e4m3(x / scale), which gives other bytes near ties).  K % 8 == 0, K <= 2048."""
     _req(x, torch.float16, "x")
     if x.ndim != 2:
         raise ValueError(f"x: expected fp16 [rows, K], got {tuple(x.shape)}")
